@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- ModCR hot path on MI355X: PMR training examples/s (4-choice, S = 180).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (child processes, one per GPU, started BEFORE
@@ -22,6 +22,9 @@ Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json +
                 cases (i) fused-attention fwd and (ii) one layer fwd+bwd
   parity_vs_oracle  answer-agreement RATE of the HIP path against the oracle over synthetic "val" examples, margin-aware
   config3_full_fwd_bwd  the same step with both encoders trained (every layer's backward on the HIP kernels)
+
+--dump-outputs DIR (rank 0) writes what the headline's LAST timed step handed its caller, as float32 .npy files (see dump_outputs):
+the inputs, weights and dropout streams are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -102,7 +105,32 @@ def parse_args():
                     help="N > 1: the type the gradient buckets cross the links in (fp32 = the default and the contract's `value`; bf16 = the "
                          "opt-in half-size buckets of FlatGrads(comm_dtype=), recorded in config.gradient_buckets)")
     ap.add_argument("--allow-knobs", action="store_true", help="run although MODCR_* environment variables are set (they are recorded)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (loss, logits, gradient norm, seeded samples of the "
+                         "updated trainable parameters and of AdamW's first moment) as DIR/<name>.npy, float32, a few MB in all")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 20       # elements of each sampled flat buffer in --dump-outputs (4 MB of float32)
+
+
+def dump_outputs(out_dir, loss, logits, opt):
+    """--dump-outputs: the headline step's results as its caller receives them -- tu.train_step's (loss, logits), the global
+    gradient norm the fused clip used, and the state the optimizer step left (the trainable parameters and AdamW's first moment,
+    which carries every step's gradients).  The two flat buffers are sampled at DUMP_SAMPLE fixed positions (seed 0, sorted)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = opt.flat_p.numel()
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    idx_t = torch.from_numpy(idx.astype(np.int64)).to(opt.flat_p.device)
+    arrays = {"loss": loss.detach().float().reshape(1), "logits": logits.detach().float(), "grad_norm": opt.sumsq.detach().sqrt().reshape(1),
+              "trainable_params_sample": opt.flat_p.detach()[idx_t], "adam_exp_avg_sample": opt.exp_avg.detach()[idx_t]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy().astype(np.float32))
 
 
 def free_port():
@@ -548,6 +576,7 @@ def main():
         for i in range(steps):
             loss, logits = tu.train_step(model, fetch(warmup + i), opt, None, flat, world)
         torch.cuda.synchronize()
+        run_timed.logits = logits
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -566,6 +595,8 @@ def main():
     with KernelTimer(mh, "qkv_attn", is_roofline_attention) as kt:
         elapsed, loss = run_timed(model, flat, opt, args.steps, args.warmup, kt)
         t_attn = kt.mean_seconds()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, run_timed.logits, opt)
     flat_buckets, launched_in_bwd = [list(b) for b in flat.buckets], flat.launched_in_backward
     per_rank_s = run_timed.per_rank_s
     if world > 1:
