@@ -150,6 +150,19 @@ int modcr_linear_fwd(const void* A, int64_t lda, const void* W, int64_t ldw, con
                      const void* residual, int64_t ldr, int32_t res_dtype, void* C, int64_t ldc,
                      int32_t M, int32_t N, int32_t K, int32_t act, int32_t dtype, int32_t out_dtype,
                      modcr_stream_t stream);
+/* The route modcr_linear_fwd takes for the same arguments (no stream), decided by the same host function.  Dereferences nothing:
+ * pointers are inspected for alignment only.  Returns MODCR_OK or the error modcr_linear_fwd would return, and fills
+ * info[0] = kernel (MODCR_ROUTE_F32_TILE ... MODCR_ROUTE_T192), info[1] = epilogue bits (MODCR_ROUTE_DIRECT: register epilogue,
+ * MODCR_ROUTE_SPEC: seamless ring; 0 = through LDS; persistent kernels only), info[2] = column tiles per group of the persistent
+ * 256 x 256 walk (0 = row-major walk), info[3] = 1 when a persistent kernel walks its tiles from the last to the first.
+ * The tuning build reports the route its MODCR_GEMM_* knobs select (MODCR_ROUTE_D4: that build's dual-workgroup kernel). */
+enum { MODCR_ROUTE_F32_TILE = 1, MODCR_ROUTE_F32_ROWDOT = 2, MODCR_ROUTE_RING128 = 3, MODCR_ROUTE_RING192 = 4, MODCR_ROUTE_RING256 = 5,
+       MODCR_ROUTE_P8 = 6, MODCR_ROUTE_T192 = 7, MODCR_ROUTE_D4 = 8 };
+enum { MODCR_ROUTE_DIRECT = 1, MODCR_ROUTE_SPEC = 2 };
+int modcr_linear_route(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias,
+                       const void* residual, int64_t ldr, int32_t res_dtype, const void* C, int64_t ldc,
+                       int32_t M, int32_t N, int32_t K, int32_t act, int32_t dtype, int32_t out_dtype,
+                       int32_t* info);
 /* The same product for the few-row GEMMs of the trainable heads (M = 256: one row of output tiles would fill 3-20 of the
  * 256 CUs): split-K work items into fp32 partials in the caller's workspace, then one pass that sums them and applies bias /
  * activation.  modcr_linear_splitk_workspace returns the bytes needed, 0 when the shape has no plan (use modcr_linear_fwd).

@@ -1864,12 +1864,16 @@ int launch_t192d(LinearArgs p, hipStream_t st) {
     hipLaunchKernelGGL((linear_bf16_t192_kernel<ACT, RES, OUT, DIRECT>), dim3(grid), dim3(512), T192::SMEM, st, p);
     return modcr_check_launch("linear_bf16_t192");
 }
-template <int ACT, int RES, int OUT>
-int launch_t192(const LinearArgs& p, hipStream_t st) {
+// epilogue of the 192 x 384 kernel: MODCR_ROUTE_DIRECT (register epilogue) or 0 (through LDS)
+int t192_variant(bool has_res) {
     const int direct = modcr_knob_int("MODCR_GEMM_DIRECT", 1);            // tuning build only
     // with a residual the register epilogue loses (86 -> 100 us at M = 46080, N = K = 768, fp32 out): its residual
     // loads sit behind the next tile's prologue DMAs in the in-order vmcnt queue; direct == 2 forces it anyway
-    return ((direct && RES == 0) || direct == 2) ? launch_t192d<ACT, RES, OUT, 1>(p, st) : launch_t192d<ACT, RES, OUT, 0>(p, st);
+    return ((direct && !has_res) || direct == 2) ? MODCR_ROUTE_DIRECT : 0;
+}
+template <int ACT, int RES, int OUT>
+int launch_t192(const LinearArgs& p, int variant, hipStream_t st) {
+    return (variant & MODCR_ROUTE_DIRECT) ? launch_t192d<ACT, RES, OUT, 1>(p, st) : launch_t192d<ACT, RES, OUT, 0>(p, st);
 }
 // shapes the 192 x 384 kernel takes
 bool t192_ok(const LinearArgs& p) {
@@ -1880,6 +1884,24 @@ bool t192_ok(const LinearArgs& p) {
     if (p.res && ((p.ldr % 8) != 0 || !modcr_aligned16(p.res))) return false;
     if (p.bias && !modcr_aligned16(p.bias)) return false;
     return true;
+}
+
+// Column groups of the 256 x 256 kernel's walk (FFN-up: N = 3072, K = 768, 17 rounds of tiles per workgroup).  Walked row-major, the
+// 32 workgroups of an XCD work on 2.7 tile rows x all 12 column tiles at a time: 4.7 MB of weights against 4 MB of L2, re-fetched every
+// round (profiles/r03_gemm_pmc_ffn_up.txt: 2 x FETCH_SIZE = 1.06 GB against 146 MB of operands).  Groups of tiles_n / 2 (or / 4)
+// columns whose weight slice is <= 2.5 MB keep that slice resident: the activations are then read once per group.  Returns the column
+// tiles per group, 0 = row-major walk.
+int p8_ngroup(const LinearArgs& p) {
+    const int tiles_m = (p.M + 255) / 256, tiles_n = p.N / 256;
+    int ngroup = 0;
+    if (!p.k_tiles_per_split && tiles_m >= 64) {
+        const int64_t wbytes = (int64_t)p.N * p.K * 2;
+        for (int parts = 2; parts <= 4 && wbytes > (3 << 20); parts *= 2)
+            if (tiles_n % parts == 0 && wbytes / parts <= (5 << 19)) { ngroup = tiles_n / parts; break; }
+    }
+    if (modcr_knob_set("MODCR_GEMM_NGROUP")) ngroup = modcr_knob_int("MODCR_GEMM_NGROUP", 0);       // tuning build only
+    if (ngroup < 0 || (ngroup > 0 && (tiles_n % ngroup) != 0)) ngroup = 0;                          // (a group count that does not divide: plain walk)
+    return ngroup;
 }
 
 template <int ACT, int RES, int OUT, int DIRECT, int TN = 0, int SPEC = 0>
@@ -1910,18 +1932,7 @@ int launch_p8d(LinearArgs p, hipStream_t st) {
     p.pf_next = modcr_knob_int("MODCR_GEMM_PF", 0);                      // tuning build only: A/B of the epilogue's L2 warm-up (off)
     p.stpol = modcr_knob_int("MODCR_GEMM_STPOL", 0);                     // tuning build only
     p.rev_walk = (p.k_tiles_per_split || TN) ? 0 : rev_walk_for(p);
-    // Column groups (FFN-up: N = 3072, K = 768, 17 rounds of tiles per workgroup).  Walked row-major, the 32 workgroups of an XCD
-    // work on 2.7 tile rows x all 12 column tiles at a time: 4.7 MB of weights against 4 MB of L2, re-fetched every round
-    // (profiles/r03_gemm_pmc_ffn_up.txt: 2 x FETCH_SIZE = 1.06 GB against 146 MB of operands).  Groups of tiles_n / 2 (or / 4)
-    // columns whose weight slice is <= 2.5 MB keep that slice resident: the activations are then read once per group.
-    p.ngroup = 0;
-    if (!p.k_tiles_per_split && p.tiles_m >= 64) {
-        const int64_t wbytes = (int64_t)p.N * p.K * 2;
-        for (int parts = 2; parts <= 4 && wbytes > (3 << 20); parts *= 2)
-            if (p.tiles_n % parts == 0 && wbytes / parts <= (5 << 19)) { p.ngroup = p.tiles_n / parts; break; }
-    }
-    if (modcr_knob_set("MODCR_GEMM_NGROUP")) p.ngroup = modcr_knob_int("MODCR_GEMM_NGROUP", 0);       // tuning build only
-    if (p.ngroup < 0 || (p.ngroup > 0 && (p.tiles_n % p.ngroup) != 0)) p.ngroup = 0;                  // (a group count that does not divide: plain walk)
+    p.ngroup = p8_ngroup(p);
     // persistent: one workgroup per CU (a multiple of 8 so a workgroup's tiles stay on one XCD's chunk)
     const int nwg = p.tiles_m * p.tiles_n * (p.k_tiles_per_split ? (p.K >> 6) / p.k_tiles_per_split : 1);
     const int ncu = modcr_device_cus();
@@ -1935,6 +1946,19 @@ inline bool d4_shape(const LinearArgs& p) {
     return (p.M % 256) == 0 && (p.N % 128) == 0 && (p.K % 192) == 0 && p.K >= 192 && !p.k_tiles_per_split && !p.res && (p.ldc % 8) == 0 &&
            (p.lda % 8) == 0 && (p.ldw % 8) == 0 && (!p.bias || modcr_aligned16(p.bias)) &&
            (int64_t)p.lda * 64 * 2 < (1ll << 31) && (int64_t)p.ldw * 64 * 2 < (1ll << 31) && (int64_t)p.ldc * 32 < (1ll << 31);
+}
+// column groups as in p8_ngroup (a group's weight slice <= 2.5 MB stays in the XCD's L2), over 128-column tiles
+int d4_ngroup(const LinearArgs& p) {
+    const int tiles_m = p.M / 256, tiles_n = p.N / 128;
+    int ngroup = 0;
+    if (tiles_m >= 64) {
+        const int64_t wbytes = (int64_t)p.N * p.K * 2;
+        for (int parts = 2; parts <= 4 && wbytes > (3 << 20); parts *= 2)
+            if (tiles_n % parts == 0 && wbytes / parts <= (5 << 19)) { ngroup = tiles_n / parts; break; }
+    }
+    if (modcr_knob_set("MODCR_GEMM_NGROUP")) ngroup = modcr_knob_int("MODCR_GEMM_NGROUP", 0);       // tuning build only
+    if (ngroup < 0 || (ngroup > 0 && (tiles_n % ngroup) != 0)) ngroup = 0;
+    return ngroup;
 }
 template <int ACT, int OUT>
 int launch_d4(LinearArgs p, hipStream_t st) {
@@ -1951,15 +1975,7 @@ int launch_d4(LinearArgs p, hipStream_t st) {
     }
     p.tiles_m = p.M / 256;
     p.tiles_n = p.N / 128;
-    // column groups as in launch_p8d (a group's weight slice <= 2.5 MB stays in the XCD's L2)
-    p.ngroup = 0;
-    if (p.tiles_m >= 64) {
-        const int64_t wbytes = (int64_t)p.N * p.K * 2;
-        for (int parts = 2; parts <= 4 && wbytes > (3 << 20); parts *= 2)
-            if (p.tiles_n % parts == 0 && wbytes / parts <= (5 << 19)) { p.ngroup = p.tiles_n / parts; break; }
-    }
-    if (modcr_knob_set("MODCR_GEMM_NGROUP")) p.ngroup = modcr_knob_int("MODCR_GEMM_NGROUP", 0);       // tuning build only
-    if (p.ngroup < 0 || (p.ngroup > 0 && (p.tiles_n % p.ngroup) != 0)) p.ngroup = 0;
+    p.ngroup = d4_ngroup(p);
     p.order = modcr_knob_int("MODCR_GEMM_ORDER", 0);                      // tuning build only
     const int nwg = p.tiles_m * p.tiles_n;
     const int slots = 2 * (modcr_device_cus() & ~7);          // two workgroups per CU
@@ -1968,20 +1984,34 @@ int launch_d4(LinearArgs p, hipStream_t st) {
     return modcr_check_launch("linear_bf16_d4");
 }
 #endif  // MODCR_TUNING (d4)
-template <int ACT, int RES, int OUT>
-int launch_p8(const LinearArgs& p, hipStream_t st) {
+// epilogue of the 256 x 256 kernel for a product with activation `act`, a residual or not, output `out`: MODCR_ROUTE_DIRECT (register
+// epilogue), | MODCR_ROUTE_SPEC (seamless ring), 0 (through LDS), or P8_D4 (tuning build only: the dual-workgroup kernel instead)
+constexpr int P8_D4 = 4;
+int p8_variant(const LinearArgs& p, int act, bool has_res, int out) {
     const int direct = modcr_knob_int("MODCR_GEMM_DIRECT", 1);            // tuning build only
     // the register epilogue reads / writes 8- and 16-byte pieces at column offsets that are multiples of 4
     const bool ok = (p.ldc % 8) == 0 && (!p.res || (p.ldr % 4) == 0) && (!p.bias || modcr_aligned16(p.bias));
     // seamless ring + stores behind vmcnt(0) (see the kernel): 16-bit output without a residual
-    if constexpr (RES == 0 && OUT != MODCR_F32 && (ACT == MODCR_ACT_NONE || ACT == MODCR_ACT_GELU || ACT == MODCR_ACT_TANH)) {
+    if (!has_res && out != MODCR_F32 && (act == MODCR_ACT_NONE || act == MODCR_ACT_GELU || act == MODCR_ACT_TANH)) {
 #ifdef MODCR_TUNING
-        if (direct && ok && d4_shape(p) && modcr_knob_int("MODCR_GEMM_D4", 0)) return launch_d4<ACT, OUT>(p, st);      // A/B only
+        if (direct && ok && d4_shape(p) && modcr_knob_int("MODCR_GEMM_D4", 0)) return P8_D4;      // A/B only
 #endif
         if (direct && ok && !p.k_tiles_per_split && (p.M % 256) == 0 && modcr_knob_int("MODCR_GEMM_SPEC", 1))
-            return launch_p8d<ACT, RES, OUT, 1, 0, 1>(p, st);
+            return MODCR_ROUTE_DIRECT | MODCR_ROUTE_SPEC;
     }
-    return (((direct && RES == 0) || direct == 2) && ok) ? launch_p8d<ACT, RES, OUT, 1>(p, st) : launch_p8d<ACT, RES, OUT, 0>(p, st);   // see launch_t192
+    return (((direct && !has_res) || direct == 2) && ok) ? MODCR_ROUTE_DIRECT : 0;     // see t192_variant
+}
+// variant < 0: the choice of p8_variant (the split-K and weight-gradient callers)
+template <int ACT, int RES, int OUT>
+int launch_p8(const LinearArgs& p, hipStream_t st, int variant = -1) {
+    if (variant < 0) variant = p8_variant(p, ACT, RES != 0, OUT);
+    if constexpr (RES == 0 && OUT != MODCR_F32 && (ACT == MODCR_ACT_NONE || ACT == MODCR_ACT_GELU || ACT == MODCR_ACT_TANH)) {
+#ifdef MODCR_TUNING
+        if (variant == P8_D4) return launch_d4<ACT, OUT>(p, st);
+#endif
+        if (variant & MODCR_ROUTE_SPEC) return launch_p8d<ACT, RES, OUT, 1, 0, 1>(p, st);
+    }
+    return (variant & MODCR_ROUTE_DIRECT) ? launch_p8d<ACT, RES, OUT, 1>(p, st) : launch_p8d<ACT, RES, OUT, 0>(p, st);
 }
 // shapes the half-tile kernel takes
 bool p8_ok(const LinearArgs& p) {
@@ -2043,8 +2073,10 @@ int choose_tile(const LinearArgs& p) {
     return eM >= eS ? 192 : 128;
 }
 
-template <int ACT, int RES, int OUT>
-int dispatch_tile(const LinearArgs& p, hipStream_t st) {
+// The route of a bf16 product (modcr_linear_fwd and modcr_linear_route): kernel, epilogue, walk.  The one place the choice is made.
+struct LinearRoute { int kernel, variant, ngroup, rev_walk; };
+LinearRoute route_bf16(const LinearArgs& p) {
+    LinearRoute r = {MODCR_ROUTE_RING128, 0, 0, 0};
     const int knob = modcr_knob_int("MODCR_GEMM_T192", -1);               // tuning build only: 0 off, 1 force
     if (knob != 0 && t192_ok(p)) {
         // whole-round efficiency of the persistent grids (one workgroup per CU).  At equal efficiency the
@@ -2055,12 +2087,45 @@ int dispatch_tile(const LinearArgs& p, hipStream_t st) {
         };
         const bool p8_fits = (p.N % 256) == 0 && p.M >= 256;
         const int64_t t192 = (int64_t)((p.M + 191) / 192) * (p.N / 384);       // small problems: the 128 x 128 tiles fill more CUs
-        if (knob == 1 || (t192 >= 192 && (!p8_fits || eff(192, 384) >= eff(256, 256) * 1.04))) return launch_t192<ACT, RES, OUT>(p, st);
+        if (knob == 1 || (t192 >= 192 && (!p8_fits || eff(192, 384) >= eff(256, 256) * 1.04))) {
+            r.kernel = MODCR_ROUTE_T192;
+            r.variant = t192_variant(p.res != nullptr);
+            r.rev_walk = rev_walk_for(p);
+            return r;
+        }
     }
     switch (choose_tile(p)) {
-        case 256: if (p8_ok(p)) return launch_p8<ACT, RES, OUT>(p, st);
-                  return launch_linear<TileL, ACT, RES, OUT>(p, st);
-        case 192: return launch_linear<TileM, ACT, RES, OUT>(p, st);
+        case 256:
+            if (p8_ok(p)) {
+                r.variant = p8_variant(p, p.act, p.res != nullptr, p.out_dtype == MODCR_F16 ? MODCR_F16 : p.out_dtype == MODCR_BF16 ? MODCR_BF16 : MODCR_F32);
+#ifdef MODCR_TUNING
+                if (r.variant == P8_D4) {       // (launch_d4: column groups, no reversed walk)
+                    r.kernel = MODCR_ROUTE_D4;
+                    r.variant = 0;
+                    r.ngroup = d4_ngroup(p);
+                    return r;
+                }
+#endif
+                r.kernel = MODCR_ROUTE_P8;
+                r.ngroup = p8_ngroup(p);
+                r.rev_walk = rev_walk_for(p);
+                return r;
+            }
+            r.kernel = MODCR_ROUTE_RING256;
+            return r;
+        case 192: r.kernel = MODCR_ROUTE_RING192; return r;
+    }
+    return r;
+}
+
+template <int ACT, int RES, int OUT>
+int dispatch_tile(const LinearArgs& p, hipStream_t st) {
+    const LinearRoute r = route_bf16(p);
+    switch (r.kernel) {
+        case MODCR_ROUTE_T192: return launch_t192<ACT, RES, OUT>(p, r.variant, st);
+        case MODCR_ROUTE_P8: case MODCR_ROUTE_D4: return launch_p8<ACT, RES, OUT>(p, st, r.kernel == MODCR_ROUTE_D4 ? P8_D4 : r.variant);
+        case MODCR_ROUTE_RING256: return launch_linear<TileL, ACT, RES, OUT>(p, st);
+        case MODCR_ROUTE_RING192: return launch_linear<TileM, ACT, RES, OUT>(p, st);
     }
     return launch_linear<TileS, ACT, RES, OUT>(p, st);
 }
@@ -2079,7 +2144,21 @@ int dispatch_res(const LinearArgs& p, hipStream_t st) {
     if (!p.res) return dispatch_out<ACT, 0>(p, st);
     return p.res_dtype == MODCR_BF16 ? dispatch_out<ACT, 1>(p, st) : dispatch_out<ACT, 2>(p, st);
 }
+// the (activation, residual, output) combinations the bf16 kernels are instantiated for
+int linear_kind_ok(const LinearArgs& p) {
+    if (p.act != MODCR_ACT_NONE && p.act != MODCR_ACT_GELU && p.act != MODCR_ACT_TANH) {
+        modcr_set_error("linear_fwd: unknown activation %d", p.act);
+        return MODCR_ERR_INVALID;
+    }
+    if (p.out_dtype == MODCR_F16 && (p.act != MODCR_ACT_NONE || (p.res && p.res_dtype != MODCR_BF16))) {
+        modcr_set_error("linear_fwd: fp16 output is implemented for act = none without an fp32 residual");
+        return MODCR_ERR_UNSUPPORTED;
+    }
+    return MODCR_OK;
+}
 int dispatch_linear(const LinearArgs& p, hipStream_t st) {
+    const int rc = linear_kind_ok(p);
+    if (rc != MODCR_OK) return rc;
     switch (p.act) {
         case MODCR_ACT_NONE: return dispatch_res<MODCR_ACT_NONE>(p, st);
         case MODCR_ACT_GELU: return dispatch_res<MODCR_ACT_GELU>(p, st);
@@ -2262,8 +2341,9 @@ __global__ __launch_bounds__(256) void rowdot_f32_kernel(GemmF32Args p) {
     }
 }
 
+inline bool rowdot_ok(const GemmF32Args& a) { return a.N <= 4 && a.sak == 1 && a.sbk == 1 && a.M >= 64; }
 int launch_gemm_f32(const GemmF32Args& a, hipStream_t st) {
-    if (a.N <= 4 && a.sak == 1 && a.sbk == 1 && a.M >= 64) {
+    if (rowdot_ok(a)) {
         hipLaunchKernelGGL(rowdot_f32_kernel, dim3((a.M + 3) / 4), dim3(256), 0, st, a);
         return modcr_check_launch("rowdot_f32");
     }
@@ -2272,6 +2352,35 @@ int launch_gemm_f32(const GemmF32Args& a, hipStream_t st) {
     return modcr_check_launch("gemm_f32");
 }
 
+// argument checks of modcr_linear_fwd / modcr_linear_route, and the arguments of the product: `p` (bf16) or `a` (fp32)
+int linear_setup(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const void* residual, int64_t ldr,
+                 int32_t res_dtype, const void* C, int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t act, int32_t dtype,
+                 int32_t out_dtype, LinearArgs& p, GemmF32Args& a) {
+    MODCR_REQUIRE(A && W && C, "linear_fwd: null pointer");
+    MODCR_REQUIRE(M > 0 && N > 0 && K > 0, "linear_fwd: bad shape M=%d N=%d K=%d", M, N, K);
+    MODCR_REQUIRE(lda >= K && ldw >= K && ldc >= N, "linear_fwd: strides smaller than the row");
+    MODCR_REQUIRE(!residual || ldr >= N, "linear_fwd: residual stride");
+    if (dtype == MODCR_BF16) {
+        MODCR_REQUIRE((K % 64) == 0 && (lda % 8) == 0 && (ldw % 8) == 0,
+                      "linear_fwd(bf16): K=%d must be a multiple of 64, lda=%lld ldw=%lld multiples of 8 "
+                      "(zero-pad with modcr_cast_pad)", K, (long long)lda, (long long)ldw);
+        MODCR_REQUIRE(modcr_aligned16(A) && modcr_aligned16(W), "linear_fwd(bf16): 16-byte alignment");
+        p.A = (const bf16*)A; p.lda = lda; p.W = (const bf16*)W; p.ldw = ldw; p.bias = bias;
+        p.res = residual; p.ldr = ldr; p.res_dtype = res_dtype; p.C = const_cast<void*>(C); p.ldc = ldc;
+        p.out_dtype = out_dtype; p.M = M; p.N = N; p.K = K; p.act = act;
+        p.tiles_m = p.tiles_n = 0;
+        p.vec_ok = (ldc % 4 == 0) && modcr_aligned16(C) && (!residual || ((ldr % 4 == 0) && modcr_aligned16(residual)));
+        p.k_tiles_per_split = 0; p.split_stride = 0;
+        return MODCR_OK;
+    }
+    MODCR_REQUIRE(dtype == MODCR_F32, "linear_fwd: unknown dtype %d", dtype);
+    a.A = A; a.sam = lda; a.sak = 1; a.a_dtype = MODCR_F32;
+    a.B = W; a.sbk = 1; a.sbn = ldw; a.b_dtype = MODCR_F32;
+    a.bias = bias; a.res = residual; a.ldr = ldr; a.res_dtype = res_dtype;
+    a.C = const_cast<void*>(C); a.ldc = ldc; a.out_dtype = out_dtype; a.M = M; a.N = N; a.K = K; a.act = act;
+    a.accumulate = 0;
+    return MODCR_OK;
+}
 }  // namespace
 
 extern "C" int modcr_linear_fwd(const void* A, int64_t lda, const void* W, int64_t ldw,
@@ -2279,33 +2388,32 @@ extern "C" int modcr_linear_fwd(const void* A, int64_t lda, const void* W, int64
                                 int32_t res_dtype, void* C, int64_t ldc, int32_t M, int32_t N,
                                 int32_t K, int32_t act, int32_t dtype, int32_t out_dtype,
                                 modcr_stream_t stream) {
-    MODCR_REQUIRE(A && W && C, "linear_fwd: null pointer");
-    MODCR_REQUIRE(M > 0 && N > 0 && K > 0, "linear_fwd: bad shape M=%d N=%d K=%d", M, N, K);
-    MODCR_REQUIRE(lda >= K && ldw >= K && ldc >= N, "linear_fwd: strides smaller than the row");
-    MODCR_REQUIRE(!residual || ldr >= N, "linear_fwd: residual stride");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MODCR_BF16) {
-        MODCR_REQUIRE((K % 64) == 0 && (lda % 8) == 0 && (ldw % 8) == 0,
-                      "linear_fwd(bf16): K=%d must be a multiple of 64, lda=%lld ldw=%lld multiples of 8 "
-                      "(zero-pad with modcr_cast_pad)", K, (long long)lda, (long long)ldw);
-        MODCR_REQUIRE(modcr_aligned16(A) && modcr_aligned16(W), "linear_fwd(bf16): 16-byte alignment");
-        LinearArgs p;
-        p.A = (const bf16*)A; p.lda = lda; p.W = (const bf16*)W; p.ldw = ldw; p.bias = bias;
-        p.res = residual; p.ldr = ldr; p.res_dtype = res_dtype; p.C = C; p.ldc = ldc;
-        p.out_dtype = out_dtype; p.M = M; p.N = N; p.K = K; p.act = act;
-        p.tiles_m = p.tiles_n = 0;
-        p.vec_ok = (ldc % 4 == 0) && modcr_aligned16(C) && (!residual || ((ldr % 4 == 0) && modcr_aligned16(residual)));
-        p.k_tiles_per_split = 0; p.split_stride = 0;
-        return dispatch_linear(p, st);
-    }
-    MODCR_REQUIRE(dtype == MODCR_F32, "linear_fwd: unknown dtype %d", dtype);
+    LinearArgs p;
     GemmF32Args a;
-    a.A = A; a.sam = lda; a.sak = 1; a.a_dtype = MODCR_F32;
-    a.B = W; a.sbk = 1; a.sbn = ldw; a.b_dtype = MODCR_F32;
-    a.bias = bias; a.res = residual; a.ldr = ldr; a.res_dtype = res_dtype;
-    a.C = C; a.ldc = ldc; a.out_dtype = out_dtype; a.M = M; a.N = N; a.K = K; a.act = act;
-    a.accumulate = 0;
-    return launch_gemm_f32(a, st);
+    const int rc = linear_setup(A, lda, W, ldw, bias, residual, ldr, res_dtype, C, ldc, M, N, K, act, dtype, out_dtype, p, a);
+    if (rc != MODCR_OK) return rc;
+    return dtype == MODCR_BF16 ? dispatch_linear(p, (hipStream_t)stream) : launch_gemm_f32(a, (hipStream_t)stream);
+}
+
+extern "C" int modcr_linear_route(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias,
+                                  const void* residual, int64_t ldr, int32_t res_dtype, const void* C, int64_t ldc,
+                                  int32_t M, int32_t N, int32_t K, int32_t act, int32_t dtype, int32_t out_dtype,
+                                  int32_t* info) {
+    MODCR_REQUIRE(info, "linear_route: null info");
+    LinearArgs p;
+    GemmF32Args a;
+    int rc = linear_setup(A, lda, W, ldw, bias, residual, ldr, res_dtype, C, ldc, M, N, K, act, dtype, out_dtype, p, a);
+    if (rc != MODCR_OK) return rc;
+    if (dtype != MODCR_BF16) {
+        info[0] = rowdot_ok(a) ? MODCR_ROUTE_F32_ROWDOT : MODCR_ROUTE_F32_TILE;
+        info[1] = info[2] = info[3] = 0;
+        return MODCR_OK;
+    }
+    rc = linear_kind_ok(p);
+    if (rc != MODCR_OK) return rc;
+    const LinearRoute r = route_bf16(p);
+    info[0] = r.kernel; info[1] = r.variant; info[2] = r.ngroup; info[3] = r.rev_walk;
+    return MODCR_OK;
 }
 
 extern "C" int modcr_ffn_up_gelu_fwd(const void* x, const void* w1, const float* b1, void* out,

@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the stream; every piece of a
 hot path is a hand-written HIP kernel behind the C ABI.  There is NO fallback: if the shared
 library is missing or a call fails, an exception is raised.
 """
+import collections
 import ctypes
 import os
 
@@ -14,6 +15,9 @@ LIB_PATH = os.path.join(_HERE, "libmodcr_hip.so")
 
 BF16, F32, F16 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_TANH = 0, 1, 2
+# modcr_linear_route: kernel ids (MODCR_ROUTE_*) and epilogue bits
+ROUTE_KERNELS = {1: "f32_tile", 2: "f32_rowdot", 3: "ring128", 4: "ring192", 5: "ring256", 6: "p8", 7: "t192", 8: "d4"}
+ROUTE_DIRECT, ROUTE_SPEC = 1, 2
 
 _c = ctypes
 _vp, _i32, _i64, _f32 = _c.c_void_p, _c.c_int32, _c.c_int64, _c.c_float
@@ -41,6 +45,8 @@ SIGNATURES = {
     "modcr_build_packed_mask": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "modcr_linear_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _i32,
                                 _i32, _i32, _i32, _i32, _vp]),
+    "modcr_linear_route": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _i32,
+                                  _i32, _i32, _i32, _i32, _c.POINTER(_i32)]),
     "modcr_ffn_up_gelu_fwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "modcr_linear_residual_ln_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32,
                                             _i32, _vp, _i64, _i32, _vp]),
@@ -234,6 +240,32 @@ def linear(a, w, bias=None, act=ACT_NONE, residual=None, out_dtype=None, out=Non
                                   dt_of(res2) if res2 is not None else 0, _ptr(out), out.stride(0), m, n,
                                   k, act, dt, od, _stream()), "modcr_linear_fwd")
     return out.view(*a.shape[:-1], n) if (a.dim() != 2) else out
+
+
+LinearRoute = collections.namedtuple("LinearRoute", "kernel direct spec ngroup rev_walk")
+
+
+def linear_route(a, w, bias=None, residual=None, out_dtype=None, act=ACT_NONE, lda=None, ldw=None, ldc=None, ldr=None, out=None,
+                 dtype=None, res_dtype=None):
+    """The route modcr_linear_fwd takes for these arguments (modcr_linear_route; nothing is launched or read):
+    LinearRoute(kernel = a name of ROUTE_KERNELS, direct, spec = epilogue bits, ngroup = column tiles per group of the
+    persistent 256 x 256 walk, rev_walk).  a [M, K] and w [N, K] tensors, or (rows, cols) tuples for a shape-only query
+    (give `dtype`); a shape-only bias / residual / out is any non-tensor truthy value.  Non-tensors stand for 256-byte
+    aligned allocations.  Strides default to a's / w's / out's row stride, the dense row otherwise."""
+    def ptr_ld(t):
+        if isinstance(t, torch.Tensor):
+            return t.data_ptr(), t.stride(0) if t.dim() == 2 else t.shape[-1]
+        return (256 if t else None), None
+    m, k = (a.shape[0], a.shape[-1]) if isinstance(a, torch.Tensor) else a
+    n = w.shape[0] if isinstance(w, torch.Tensor) else w[0]
+    dt = dt_of(w) if isinstance(w, torch.Tensor) else (BF16 if dtype is None else dtype)
+    od = dt if out_dtype is None else out_dtype
+    (pa, sa), (pw, sw), (pb, _), (pr, sr), (pc, sc) = map(ptr_ld, (a, w, bias, residual, 1 if out is None else out))
+    rdt = dt_of(residual) if isinstance(residual, torch.Tensor) else (res_dtype or 0)
+    info = (_i32 * 4)()
+    _check(lib().modcr_linear_route(pa, lda or sa or k, pw, ldw or sw or k, pb, pr, ldr or sr or n, rdt, pc, ldc or sc or n,
+                                    m, n, k, act, dt, od, info), "modcr_linear_route")
+    return LinearRoute(ROUTE_KERNELS[info[0]], int(bool(info[1] & ROUTE_DIRECT)), int(bool(info[1] & ROUTE_SPEC)), info[2], info[3])
 
 
 def layernorm(x, gamma, beta, eps, residual=None, out_dtype=None, out=None, rows_per_group=0,

@@ -665,3 +665,26 @@ def test_backward_memory_auto_counts_every_group_of_trainable_layers(monkeypatch
         assert hip_layers.configure_backward_memory("auto", device="cuda:0", groups=[]) == "keep"
     finally:
         hip_layers.SAVE_QKV, hip_layers.KEEP_GELU_INPUT = keep0
+
+
+def test_gemm_route_table_on_the_host():
+    """The GPU route table of test_hip_gemm_routes (and its forced / offset-guard cases) asserts each case's route before it runs;
+    modcr_linear_route dereferences nothing, so the same table is checked here without a GPU: a dispatcher change that moves a
+    case off its kernel fails on the CPU box with the route's name.  Also: the query returns modcr_linear_fwd's errors."""
+    import modcr_hip as mh
+    import test_hip_gemm_routes as T
+
+    def query(c, lda=None):
+        pa, pw, pc, pr = c.pad
+        return mh.linear_route((c.m, c.k), (c.n, c.k), bias=True, residual=bool(c.res), res_dtype=T.RES[c.res][0],
+                               out_dtype=T.OUT[c.out][0], act=c.act, lda=lda or c.k + pa, ldw=c.k + pw, ldc=c.n + pc, ldr=c.n + pr)
+    for c in T.CASES + list(T.FORCE.values()):
+        assert query(c) == c.route, c.id
+    for gid, c, lda, route in T.GUARDS:
+        assert query(c, lda) == route, gid
+    assert mh.linear_route((100, 64), (3, 64), dtype=mh.F32).kernel == "f32_rowdot"
+    assert mh.linear_route((100, 64), (30, 64), dtype=mh.F32).kernel == "f32_tile"
+    with pytest.raises(mh.ModcrHipError, match="fp16 output"):
+        mh.linear_route((4096, 256), (256, 256), act=mh.ACT_GELU, out_dtype=mh.F16)
+    with pytest.raises(mh.ModcrHipError, match="multiple of 64"):
+        mh.linear_route((4096, 200), (256, 200))
