@@ -65,7 +65,11 @@ const char* modcr_last_error(void);
  *   probs    [N,A,S,P+S] fp32 softmax probabilities, or NULL (output_attentions, modeling_bert.py:74)
  *   align_map [N,T,R] fp32, or NULL: += sum over heads of probs[:, :, :T, P+T:P+T+R] (atomic; the
  *            caller zeroes it; consumed at v10:982).  T = align_t, R = S - T.
- *   H = A*64 (head size 64: BERT-base/large, Oscar-base/large).  P+S <= 256.
+ *   H = A*64 (head size 64: BERT-base/large, Oscar-base/large).  P+S <= 512.
+ *   256 < P+S <= 512 (eval mode): [hist ; x] is projected into the workspace (modcr_qkv_attn_workspace: N (P+S) 3H x 2
+ *            bytes in bf16) and a streaming core (64-key tiles, online softmax) runs over it; attention-probability
+ *            dropout (attn_p > 0), lse and qkv_dump are MODCR_ERR_UNSUPPORTED there (they exist for the backward, which
+ *            takes S <= 256), and so is P+S > 512.
  */
 int modcr_qkv_attn_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
                        const float* key_mask, const uint32_t* dense_mask_bits,
@@ -115,7 +119,7 @@ int modcr_qkv_attn_opt_fwd(const void* x, const void* hist, const void* wqkv, co
  * own duration, as rocprofv3 --kernel-trace reports it, without the two extra barrier packets of a hipEventRecord pair.
  * Consumed by that one launch; (NULL, NULL) clears it.  bench.py's `roofline` uses it. */
 int modcr_time_next_attn(void* start_event, void* stop_event);
-/* bytes of `workspace` modcr_qkv_attn_fwd needs (0 for the fused bf16 path) */
+/* bytes of `workspace` modcr_qkv_attn_fwd needs (0 for the fused bf16 path; the q | k | v rows above 256 keys) */
 int64_t modcr_qkv_attn_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype);
 
 /* Chunk-mean query on its own (v10:66-78): q [N,S,H] in place, chunk_id [N,T] as above. */

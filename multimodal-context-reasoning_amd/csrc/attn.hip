@@ -2182,6 +2182,7 @@ extern "C" int64_t modcr_qkv_attn_dump_bytes(int32_t N, int32_t S, int32_t A) {
 }
 
 extern "C" int64_t modcr_qkv_attn_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
+    if (dtype == MODCR_BF16 && P + S > 256) return (int64_t)N * (P + S) * 3 * H * 2;  // q | k | v rows for attn_long.hip
     if (dtype == MODCR_BF16) return P > 0 ? (int64_t)N * (P + S) * H * 2 : 0;      // [prefix ; x] rows for the tile kernels
     return (int64_t)N * (S + P) * 3 * H * (int64_t)sizeof(float);
 }
@@ -2233,6 +2234,64 @@ extern "C" int modcr_qkv_attn_lse_fwd(const void* x, const void* hist, const voi
                                   N, S, P, H, A, attn_p, seed, offset, 0, workspace, workspace_bytes, dtype, stream);
 }
 
+// 256 < P + S <= 512 (eval mode): project [hist ; x] once into the workspace (x rows [N*S][3H], then the prefix rows
+// [N*P][3H]), chunk-mean the query columns, then the streaming core of attn_long.hip.  No dropout, no row statistics,
+// no q|k|v dump: those exist for the backward, which stops at 256 keys.
+static int qkv_attn_long_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* key_mask,
+                             const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
+                             float* align_map, int32_t align_t, float* lse, void* qkv_dump, int32_t N, int32_t S, int32_t P, int32_t H,
+                             int32_t A, float attn_p, int32_t flags, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                             modcr_stream_t stream) {
+    const int L = P + S;
+    MODCR_REQUIRE((flags & ~MODCR_ATTN_SIDE_POST_DROPOUT) == 0, "qkv_attn_fwd: unknown flags 0x%x", flags);
+    if (L > 512) {
+        modcr_set_error("qkv_attn_fwd: P+S=%d exceeds the 512-key limit of the attention forward", L);
+        return MODCR_ERR_UNSUPPORTED;
+    }
+    if (attn_p > 0.f) {
+        modcr_set_error("qkv_attn_fwd: attention-probability dropout (p=%g) is not implemented above 256 keys (P+S=%d)", attn_p, L);
+        return MODCR_ERR_UNSUPPORTED;
+    }
+    if (lse || qkv_dump) {
+        modcr_set_error("qkv_attn_fwd: row statistics (lse) / q|k|v dump are not produced above 256 keys (P+S=%d): no backward there", L);
+        return MODCR_ERR_UNSUPPORTED;
+    }
+    MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "qkv_attn_fwd: unknown dtype %d", dtype);
+    MODCR_REQUIRE(N > 0 && S > 0 && P >= 0 && A > 0, "qkv_attn_fwd: bad shape");
+    MODCR_REQUIRE(H == A * 64, "qkv_attn_fwd: head size must be 64 (H=%d, A=%d)", H, A);
+    MODCR_REQUIRE(P == 0 || hist, "qkv_attn_fwd: P=%d but hist is null", P);
+    MODCR_REQUIRE(key_mask || dense_mask_bits, "qkv_attn_fwd: need key_mask or dense_mask_bits");
+    MODCR_REQUIRE(!chunk_id || (chunk_t > 0 && chunk_t <= S), "qkv_attn_fwd: chunk_t=%d out of range", chunk_t);
+    MODCR_REQUIRE(!align_map || (align_t > 0 && align_t < S), "qkv_attn_fwd: align_t=%d out of range", align_t);
+    MODCR_REQUIRE(N <= 65535 && A <= 65535, "qkv_attn_fwd: grid of N=%d sequences x A=%d heads too large", N, A);
+    const int64_t need = modcr_qkv_attn_workspace(N, S, P, H, dtype);
+    MODCR_REQUIRE(workspace && workspace_bytes >= need && modcr_aligned16(workspace), "qkv_attn_fwd: workspace %lld < %lld bytes (or unaligned)",
+                  (long long)workspace_bytes, (long long)need);
+    if (dtype == MODCR_BF16)
+        MODCR_REQUIRE(modcr_aligned16(x) && modcr_aligned16(wqkv) && modcr_aligned16(ctx) && (P == 0 || modcr_aligned16(hist)),
+                      "qkv_attn_fwd(bf16): 16-byte alignment");
+    const int64_t esz = dtype == MODCR_BF16 ? 2 : 4;
+    char* qx = (char*)workspace;
+    char* qh = qx + (int64_t)N * S * 3 * H * esz;
+    int rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, qx, 3 * H, N * S, 3 * H, H, MODCR_ACT_NONE, dtype, dtype, stream);
+    if (rc != MODCR_OK) return rc;
+    if (P > 0) {
+        rc = modcr_linear_fwd(hist, H, wqkv, H, bqkv, nullptr, 0, 0, qh, 3 * H, N * P, 3 * H, H, MODCR_ACT_NONE, dtype, dtype, stream);
+        if (rc != MODCR_OK) return rc;
+    }
+    if (chunk_id) {
+        rc = modcr_chunk_mean_q_fwd(qx, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, dtype, stream);
+        if (rc != MODCR_OK) return rc;
+    }
+    AttnLongArgs g;
+    g.qx = qx; g.qh = P > 0 ? qh : nullptr; g.key_mask = key_mask; g.bits = dense_mask_bits;
+    g.ctx = ctx; g.probs = probs; g.align_map = align_map;
+    g.N = N; g.S = S; g.P = P; g.H = H; g.A = A; g.align_t = align_t;
+    hipEvent_t ev0 = g_time_start, ev1 = g_time_stop;     // the measurement hook times the core, not the projection
+    g_time_start = g_time_stop = nullptr;
+    return modcr_launch_attn_long(g, dtype, (hipStream_t)stream, ev0, ev1);
+}
+
 // flags: MODCR_ATTN_SIDE_POST_DROPOUT = the probabilities / align map leave AFTER the dropout, P o m / (1 - p), as the reference's
 // modules return them (modeling_bert.py:69-74, v10:94-106); tile kernels only (bf16, 64 < P + S <= 256).  0 = the un-dropped ones.
 extern "C" int modcr_qkv_attn_opt_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
@@ -2242,6 +2301,9 @@ extern "C" int modcr_qkv_attn_opt_fwd(const void* x, const void* hist, const voi
                                       int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
                                       void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
     MODCR_REQUIRE(x && wqkv && bqkv && ctx, "qkv_attn_fwd: null pointer");
+    if (S > 0 && P >= 0 && P + S > 256)
+        return qkv_attn_long_fwd(x, hist, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, ctx, probs, align_map, align_t, lse, qkv_dump,
+                                 N, S, P, H, A, attn_p, flags, workspace, workspace_bytes, dtype, stream);
     MODCR_REQUIRE((flags & ~MODCR_ATTN_SIDE_POST_DROPOUT) == 0, "qkv_attn_fwd: unknown flags 0x%x", flags);
     MODCR_REQUIRE(!qkv_dump || (lse && P == 0 && S > 64 && S <= 192 && modcr_aligned16(qkv_dump)),
                   "qkv_attn_fwd: the q|k|v dump comes with lse, without prefix rows, for 64 < S <= 192 (S=%d P=%d)", S, P);

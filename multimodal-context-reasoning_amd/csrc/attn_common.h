@@ -124,3 +124,15 @@ struct AttnBwdArgs {
 
 // attn_bwd.hip: launches attn_bwd5_kernel on `b` (bf16 rows, 0 < S <= 192, lse and ctx given, no align-map gradient)
 __attribute__((visibility("hidden"))) int modcr_launch_attn_bwd5(const AttnBwdArgs& b, hipStream_t stream);
+
+// attn_long.hip: the attention core above 256 keys (256 < P + S <= 512, no dropout) over q | k | v rows the dispatcher
+// projected: qx [N*S][3H] (queries, chunk-mean applied), qh [N*P][3H] (prefix rows) -- bf16 or fp32 as `dtype`
+struct AttnLongArgs {
+    const void* qx; const void* qh;
+    const float* key_mask; const uint32_t* bits;
+    void* ctx; float* probs; float* align_map;
+    int N, S, P, H, A, align_t;
+};
+// ev0 / ev1 (or NULL): stamped at the start and the end of the kernel (modcr_time_next_attn)
+__attribute__((visibility("hidden"))) int modcr_launch_attn_long(const AttnLongArgs& p, int32_t dtype, hipStream_t stream, hipEvent_t ev0,
+                                                                 hipEvent_t ev1);

@@ -1,0 +1,346 @@
+// Attention core for 256 < P + S <= 512 keys, forward only, no attention-probability dropout (inference / eval mode).
+//
+// The tile kernels of attn.hip hold the whole key row of a head in LDS; above 256 keys it does not fit, so this core
+// streams the keys in tiles of 64 with an online softmax (flash-style).  Its inputs are the q | k | v rows the dispatcher
+// (modcr_qkv_attn_opt_fwd) projected into the workspace: qx [N*S][3H] (the x rows, chunk-mean queries already applied)
+// and qh [N*P][3H] (the prefix rows).  Keys / values of sequence n are [prefix ; x], queries the x rows.
+//
+// bf16 core: one workgroup of 2 waves per (64-query block, head, sequence); wave w owns queries 32 w .. 32 w + 31 as two
+// 16-query blocks whose Q fragments stay in registers.  Per 64-key tile (double-buffered in LDS, the next one in flight in
+// registers under the current one's arithmetic):
+//   S^T = K.Q^T  with v_mfma_f32_16x16x32_bf16 (A = K rows from LDS, B = the Q fragment): the QUERY lies on the lane
+//                (l & 15), a lane holds keys 16 kb + 4 g + i (g = lane >> 4), so a row's max / sum needs two xor shuffles;
+//   scores       acc x log2e / 8 + (masked ? -10000 log2e : 0), -inf beyond P + S; running row max and sum in fp32;
+//   O^T += V^T.P^T  with P as bf16 straight from the accumulators: the 32 keys of a step arrive in the order 4 g + e |
+//                16 + 4 g + e, and the V^T fragment (two ds_read_b64 of a [feature][key] image) uses that order.
+// Side outputs (probabilities, align map) come from a second sweep over the K tiles with the final row max and sum, so
+// they are exact and a call without them pays nothing.
+//
+// fp32 parity core: the same tiling with VALU products, 4 waves x 16 queries, key on the lane for the scores and
+// feature on the lane for the context.
+#include <hip/hip_ext.h>
+
+#include "common.h"
+#include "attn_common.h"
+
+namespace {
+
+constexpr int LG_KS = 72;                       // K image row stride (bf16): 144-byte rows, conflict-free ds_read_b128
+constexpr int LG_VS = 68;                       // V^T image row stride (bf16): 136-byte rows, conflict-free ds_read_b64
+constexpr int LG_KIMG = 64 * LG_KS;
+constexpr int LG_BUF = LG_KIMG + 64 * LG_VS;    // bf16 elements of one K | V^T buffer (17 920 bytes)
+
+template <typename T> __device__ __forceinline__ const T* lg_row(const AttnLongArgs& p, int n, int j) {
+    const int64_t h3 = 3 * (int64_t)p.H;
+    return j < p.P ? (const T*)p.qh + ((int64_t)n * p.P + j) * h3 : (const T*)p.qx + ((int64_t)n * p.S + (j - p.P)) * h3;
+}
+
+// additive mask of key j (< P + S) for query q (< S), log2 domain
+__device__ __forceinline__ float lg_mask(const AttnLongArgs& p, int n, int q, int j, int L) {
+    bool see;
+    if (p.bits) see = (p.bits[((int64_t)n * p.S + q) * ((L + 31) >> 5) + (j >> 5)] >> (j & 31)) & 1u;
+    else see = p.key_mask[(int64_t)n * L + j] != 0.f;
+    return see ? 0.f : MODCR_NEG * LOG2E;
+}
+
+__device__ __forceinline__ uint32_t lg_half(const uint4& v, int e) {
+    const uint32_t w = e < 2 ? v.x : e < 4 ? v.y : e < 6 ? v.z : v.w;
+    return (e & 1) ? (w >> 16) : (w & 0xffffu);
+}
+
+template <bool SIDE>
+__global__ __launch_bounds__(128) void attn_long_bf16_kernel(AttnLongArgs p) {
+    __shared__ __attribute__((aligned(16))) bf16 sm[2 * LG_BUF];
+    const int S = p.S, L = p.P + S, H = p.H;
+    const int n = blockIdx.z, a = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l15 = lane & 15, g = lane >> 4;
+    const int ntiles = (L + 63) >> 6;
+    const float sc = 0.125f * LOG2E;
+
+    // Q fragments (B operand of S^T): query q0 + 16 qs + l15, features 32 ds + 8 g .. + 7; rows past S read row S - 1
+    int qrow[2];
+    bf16x8 qf[2][2];
+#pragma unroll
+    for (int qs = 0; qs < 2; ++qs) {
+        qrow[qs] = blockIdx.x * 64 + wave * 32 + qs * 16 + l15;
+        const bf16* r = (const bf16*)p.qx + ((int64_t)n * S + (qrow[qs] < S ? qrow[qs] : S - 1)) * 3 * H + a * 64;
+#pragma unroll
+        for (int ds = 0; ds < 2; ++ds) qf[qs][ds] = *reinterpret_cast<const bf16x8*>(r + 32 * ds + 8 * g);
+    }
+
+    // staging: K piece r of thread t = row (t + 128 r) >> 3, 16-byte chunk t & 7; V: keys 4 (t >> 3) .. + 3, chunk t & 7
+    uint4 kreg[4], vreg[4];
+    auto load = [&](int t, bool with_v) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = t * 64 + ((tid + 128 * r) >> 3);
+            kreg[r] = j < L ? *reinterpret_cast<const uint4*>(lg_row<bf16>(p, n, j) + H + a * 64 + (tid & 7) * 8) : make_uint4(0, 0, 0, 0);
+        }
+        if (with_v) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = t * 64 + (tid >> 3) * 4 + r;
+                vreg[r] = j < L ? *reinterpret_cast<const uint4*>(lg_row<bf16>(p, n, j) + 2 * H + a * 64 + (tid & 7) * 8)
+                                : make_uint4(0, 0, 0, 0);
+            }
+        }
+    };
+    auto store = [&](int b, bool with_v) {
+        bf16* K = sm + b * LG_BUF;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) *reinterpret_cast<uint4*>(K + ((tid + 128 * r) >> 3) * LG_KS + (tid & 7) * 8) = kreg[r];
+        if (with_v) {
+            bf16* Vt = K + LG_KIMG;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {           // feature 8 (t & 7) + e, keys 4 (t >> 3) .. + 3: one 8-byte piece
+                uint2 w;
+                w.x = lg_half(vreg[0], e) | (lg_half(vreg[1], e) << 16);
+                w.y = lg_half(vreg[2], e) | (lg_half(vreg[3], e) << 16);
+                *reinterpret_cast<uint2*>(Vt + ((tid & 7) * 8 + e) * LG_VS + (tid >> 3) * 4) = w;
+            }
+        }
+    };
+    // S^T of tile t (buffer b) as log2-domain scores: s[qs][kb][i] = key t 64 + 16 kb + 4 g + i, query qrow[qs]
+    auto scores = [&](int t, int b, f32x4 (&s)[2][4]) {
+        const bf16* K = sm + b * LG_BUF;
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+            const bf16x8 k0 = *reinterpret_cast<const bf16x8*>(K + (kb * 16 + l15) * LG_KS + 8 * g);
+            const bf16x8 k1 = *reinterpret_cast<const bf16x8*>(K + (kb * 16 + l15) * LG_KS + 32 + 8 * g);
+#pragma unroll
+            for (int qs = 0; qs < 2; ++qs) {
+                f32x4 c = {0.f, 0.f, 0.f, 0.f};
+                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf[qs][0], c, 0, 0, 0);
+                s[qs][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf[qs][1], c, 0, 0, 0);
+            }
+        }
+        // dense mask: the two 32-key words of the tile per query; key mask: one value per key
+        uint32_t w[2][2] = {{~0u, ~0u}, {~0u, ~0u}};
+        if (p.bits) {
+            const int LW = (L + 31) >> 5;
+#pragma unroll
+            for (int qs = 0; qs < 2; ++qs) {
+                const uint32_t* row = p.bits + ((int64_t)n * S + (qrow[qs] < S ? qrow[qs] : S - 1)) * LW;
+                w[qs][0] = row[2 * t];
+                w[qs][1] = 2 * t + 1 < LW ? row[2 * t + 1] : 0u;
+            }
+        }
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int j = t * 64 + kb * 16 + 4 * g + i;
+                const bool in = j < L;
+                const bool km = p.bits || !in || p.key_mask[(int64_t)n * L + j] != 0.f;
+#pragma unroll
+                for (int qs = 0; qs < 2; ++qs) {
+                    const bool see = km && ((w[qs][kb >> 1] >> (j & 31)) & 1u);
+                    s[qs][kb][i] = in ? s[qs][kb][i] * sc + (see ? 0.f : MODCR_NEG * LOG2E) : -INFINITY;
+                }
+            }
+    };
+
+    float m[2] = {-INFINITY, -INFINITY}, lsum[2] = {0.f, 0.f};
+    f32x4 o[2][4];
+#pragma unroll
+    for (int qs = 0; qs < 2; ++qs)
+#pragma unroll
+        for (int db = 0; db < 4; ++db) o[qs][db] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    load(0, true);
+    store(0, true);
+    __syncthreads();
+    for (int t = 0; t < ntiles; ++t) {
+        const int b = t & 1;
+        if (t + 1 < ntiles) load(t + 1, true);
+        f32x4 s[2][4];
+        scores(t, b, s);
+        bf16x8 pb[2][2];                            // P^T fragments: step ks = keys 32 ks + (4 g + e | 16 + 4 g + e)
+#pragma unroll
+        for (int qs = 0; qs < 2; ++qs) {
+            float mx = -INFINITY;
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[qs][kb][i]);
+            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float mn = fmaxf(m[qs], mx);
+            const float alpha = __builtin_amdgcn_exp2f(m[qs] - mn);
+            m[qs] = mn;
+            float sum = 0.f;
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float e = __builtin_amdgcn_exp2f(s[qs][kb][i] - mn);
+                    sum += e;
+                    pb[qs][kb >> 1][(kb & 1) * 4 + i] = (bf16)e;
+                }
+            lsum[qs] = lsum[qs] * alpha + sum;
+#pragma unroll
+            for (int db = 0; db < 4; ++db) o[qs][db] *= alpha;
+        }
+        const bf16* Vt = sm + b * LG_BUF + LG_KIMG;
+#pragma unroll
+        for (int db = 0; db < 4; ++db)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const bf16* v = Vt + (db * 16 + l15) * LG_VS + ks * 32 + 4 * g;
+                const bf16x4 lo = *reinterpret_cast<const bf16x4*>(v);
+                const bf16x4 hi = *reinterpret_cast<const bf16x4*>(v + 16);
+                const bf16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+                for (int qs = 0; qs < 2; ++qs) o[qs][db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[qs][ks], o[qs][db], 0, 0, 0);
+            }
+        if (t + 1 < ntiles) store(b ^ 1, true);
+        __syncthreads();
+    }
+
+    float inv[2];
+#pragma unroll
+    for (int qs = 0; qs < 2; ++qs) {
+        float l = lsum[qs];
+        l += __shfl_xor(l, 16, 64);
+        l += __shfl_xor(l, 32, 64);
+        inv[qs] = 1.0f / l;
+        if (qrow[qs] < S) {
+            bf16* c = (bf16*)p.ctx + ((int64_t)n * S + qrow[qs]) * H + a * 64 + 4 * g;
+#pragma unroll
+            for (int db = 0; db < 4; ++db) {
+                const bf16x4 w = {(bf16)(o[qs][db][0] * inv[qs]), (bf16)(o[qs][db][1] * inv[qs]), (bf16)(o[qs][db][2] * inv[qs]),
+                                  (bf16)(o[qs][db][3] * inv[qs])};
+                *reinterpret_cast<bf16x4*>(c + db * 16) = w;
+            }
+        }
+    }
+
+    if constexpr (SIDE) {
+        // second sweep: exact probabilities from the final row max and sum (K tiles only, one buffer)
+        const int R = S - p.align_t, key0 = p.P + p.align_t;
+        for (int t = 0; t < ntiles; ++t) {
+            load(t, false);
+            store(0, false);
+            __syncthreads();
+            f32x4 s[2][4];
+            scores(t, 0, s);
+#pragma unroll
+            for (int qs = 0; qs < 2; ++qs) {
+                const int q = qrow[qs];
+                if (q >= S) continue;
+#pragma unroll
+                for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int j = t * 64 + kb * 16 + 4 * g + i;
+                        if (j >= L) continue;
+                        const float pr = __builtin_amdgcn_exp2f(s[qs][kb][i] - m[qs]) * inv[qs];
+                        if (p.probs) p.probs[(((int64_t)n * p.A + a) * S + q) * L + j] = pr;
+                        if (p.align_map && q < p.align_t && j >= key0)
+                            atomicAdd(p.align_map + ((int64_t)n * p.align_t + q) * R + (j - key0), pr);
+                    }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// fp32 parity core: 4 waves x 16 queries per (64-query block, head, sequence); K and V tiles of 64 keys in LDS
+__global__ __launch_bounds__(256) void attn_long_f32_kernel(AttnLongArgs p) {
+    __shared__ float sK[64 * 65], sV[64 * 65], sQ[4 * 16 * 64], sP[4 * 64];
+    const int S = p.S, L = p.P + S, H = p.H;
+    const int n = blockIdx.z, a = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ntiles = (L + 63) >> 6;
+    const float sc = 0.125f * LOG2E;
+    const int q0 = blockIdx.x * 64 + wave * 16;
+    float* q_img = sQ + wave * 16 * 64;
+    float* p_img = sP + wave * 64;
+#pragma unroll
+    for (int qi = 0; qi < 16; ++qi) {
+        const int q = q0 + qi < S ? q0 + qi : S - 1;
+        q_img[qi * 64 + lane] = ((const float*)p.qx)[((int64_t)n * S + q) * 3 * H + a * 64 + lane];
+    }
+    float m[16], lsum[16], o[16];
+#pragma unroll
+    for (int qi = 0; qi < 16; ++qi) { m[qi] = -INFINITY; lsum[qi] = 0.f; o[qi] = 0.f; }
+
+    auto load = [&](int t, bool with_v) {
+        __syncthreads();
+        for (int idx = tid; idx < 64 * 64; idx += 256) {
+            const int r = idx >> 6, d = idx & 63, j = t * 64 + r;
+            const float* row = j < L ? lg_row<float>(p, n, j) : nullptr;
+            sK[r * 65 + d] = row ? row[H + a * 64 + d] : 0.f;
+            if (with_v) sV[r * 65 + d] = row ? row[2 * H + a * 64 + d] : 0.f;
+        }
+        __syncthreads();
+    };
+    // log2-domain score of key t 64 + lane for query q0 + qi
+    auto score = [&](int t, int qi) {
+        const int j = t * 64 + lane;
+        float s = 0.f;
+#pragma unroll 8
+        for (int d = 0; d < 64; ++d) s = fmaf(q_img[qi * 64 + d], sK[lane * 65 + d], s);
+        const int q = q0 + qi < S ? q0 + qi : S - 1;
+        return j < L ? s * sc + lg_mask(p, n, q, j, L) : -INFINITY;
+    };
+
+    for (int t = 0; t < ntiles; ++t) {
+        load(t, true);
+#pragma unroll
+        for (int qi = 0; qi < 16; ++qi) {
+            const float s = score(t, qi);
+            const float mn = fmaxf(m[qi], wave_max(s));
+            const float alpha = exp2f(m[qi] - mn);
+            const float e = exp2f(s - mn);
+            lsum[qi] = lsum[qi] * alpha + wave_sum(e);
+            m[qi] = mn;
+            p_img[lane] = e;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            float acc = 0.f;
+#pragma unroll 8
+            for (int j = 0; j < 64; ++j) acc = fmaf(p_img[j], sV[j * 65 + lane], acc);
+            o[qi] = o[qi] * alpha + acc;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        }
+    }
+#pragma unroll
+    for (int qi = 0; qi < 16; ++qi)
+        if (q0 + qi < S) ((float*)p.ctx)[((int64_t)n * S + q0 + qi) * H + a * 64 + lane] = o[qi] / lsum[qi];
+
+    if (p.probs || p.align_map) {
+        const int R = S - p.align_t, key0 = p.P + p.align_t;
+        for (int t = 0; t < ntiles; ++t) {
+            load(t, false);
+#pragma unroll
+            for (int qi = 0; qi < 16; ++qi) {
+                const float s = score(t, qi);
+                const int q = q0 + qi, j = t * 64 + lane;
+                if (q >= S || j >= L) continue;
+                const float pr = exp2f(s - m[qi]) / lsum[qi];
+                if (p.probs) p.probs[(((int64_t)n * p.A + a) * S + q) * L + j] = pr;
+                if (p.align_map && q < p.align_t && j >= key0) atomicAdd(p.align_map + ((int64_t)n * p.align_t + q) * R + (j - key0), pr);
+            }
+        }
+    }
+}
+
+template <typename K>
+void lg_launch(K kernel, dim3 grid, dim3 block, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, const AttnLongArgs& p) {
+    if (ev0 && ev1) hipExtLaunchKernelGGL(kernel, grid, block, 0, st, ev0, ev1, 0, p);
+    else hipLaunchKernelGGL(kernel, grid, block, 0, st, p);
+}
+
+}  // namespace
+
+int modcr_launch_attn_long(const AttnLongArgs& p, int32_t dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+    const dim3 grid((p.S + 63) / 64, p.A, p.N);
+    if (dtype == MODCR_BF16) {
+        if (p.probs || p.align_map) lg_launch(attn_long_bf16_kernel<true>, grid, dim3(128), st, ev0, ev1, p);
+        else lg_launch(attn_long_bf16_kernel<false>, grid, dim3(128), st, ev0, ev1, p);
+    } else {
+        lg_launch(attn_long_f32_kernel, grid, dim3(256), st, ev0, ev1, p);
+    }
+    return modcr_check_launch("attn_long");
+}

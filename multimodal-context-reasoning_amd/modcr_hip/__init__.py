@@ -371,6 +371,10 @@ def build_phase_mask(input_mask, chunk_mask, phase):
 
 
 ATTN_SIDE_POST_DROPOUT = 1      # include/modcr_hip.h: MODCR_ATTN_SIDE_POST_DROPOUT
+# keys (P + S) the attention forward takes: the tile kernels up to 256, the streaming core of csrc/attn_long.hip above (eval
+# mode only: no attention-probability dropout, no row statistics, no backward)
+ATTN_TILE_KEYS = 256
+ATTN_MAX_KEYS = 512
 
 
 def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=None, want_probs=False,
@@ -387,6 +391,8 @@ def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=N
     n, s, h = x.shape
     a = num_heads
     p = 0 if hist is None else hist.shape[1]
+    if p + s > ATTN_MAX_KEYS:
+        raise ValueError("qkv_attn: P + S = %d keys exceeds the %d-key limit of the attention forward" % (p + s, ATTN_MAX_KEYS))
     if (dt == BF16 and attn_dropout is not None and attn_dropout[0] > 0.0 and side_post_dropout and (want_probs or align_map is not None)
             and not side_outputs_on_tiles(s, p, h, a)):
         # post-dropout side outputs are served by the bf16 TILE kernels only (modcr_qkv_attn_opt_fwd returns MODCR_ERR_UNSUPPORTED on

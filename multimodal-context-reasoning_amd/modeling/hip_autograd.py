@@ -352,6 +352,12 @@ class BertLayerFn(_NotedFn):
     @staticmethod
     def forward(ctx, x, key_mask, mask_bits, chunk_id, num_heads, eps, p, attn_p, packed, *params):
         from . import hip_layers
+        s = x.shape[1]
+        if s > mh.ATTN_TILE_KEYS and _caller_grad_mode()[-1] and (x.requires_grad or any(
+                isinstance(p_, torch.Tensor) and p_.requires_grad for p_ in params)):
+            # the attention forward serves up to 512 keys, its backward (modcr_qkv_attn_bwd) 256: refuse before any launch
+            raise NotImplementedError("a trainable layer at S = %d exceeds the %d keys the attention backward takes; run it under "
+                                      "torch.no_grad() (eval) up to %d keys" % (s, mh.ATTN_TILE_KEYS, mh.ATTN_MAX_KEYS))
         align = packed.get("_align") if isinstance(packed, dict) else None       # (map buffer, T, gradient holder) of AlignMapFn
         amap, at = (align[0], align[1]) if align is not None else (None, 0)
         y, saved = hip_layers.layer_forward_train(packed, x.detach(), num_heads, eps, key_mask=key_mask,
