@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- ModCR hot path on MI355X: PMR training examples/s (4-choice, S = 180).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (child processes, one per GPU, started BEFORE
@@ -17,11 +17,18 @@ says so; --with-roberta includes it.
 
 Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json +
   roofline      fused QKV+attention forward kernel, HIP-event timed inside the timed region (the shape the step runs:
-                512 sequences) and, as `config2`, at BASELINE configs[1] (N = 256 sequences, fwd only, eval and train variants)
+                512 sequences)
+
+A plain run does only that: set up, warm up, time the steps, write --dump-outputs, print the line.  --full adds everything
+that takes runs of its own (about three minutes more):
+  roofline.config2 / .prefix_rows  the same kernel by itself at BASELINE configs[1] (N = 256 sequences, fwd only, eval and
+                train variants) and the call with prefix rows
   cpu_baseline  the CPU oracle (kind "port") on bounded samples of the same workload: full step (B = 2), and SURVEY 8(d)'s
                 cases (i) fused-attention fwd and (ii) one layer fwd+bwd
   parity_vs_oracle  answer-agreement RATE of the HIP path against the oracle over synthetic "val" examples, margin-aware
   config3_full_fwd_bwd  the same step with both encoders trained (every layer's backward on the HIP kernels)
+  with_roberta, last_layer_rows, c5  the secondary workloads, each with its own model, steps and in-step attention figure
+  rccl_ranks_seen, config.collective  (N > 1) the communicator's own view and one extra step with every bucket timed
 
 --dump-outputs DIR (rank 0) writes what the headline's LAST timed step handed its caller, as float32 .npy files (see dump_outputs):
 the inputs, weights and dropout streams are seeded, so two builds run with the same arguments can be compared output for output.
@@ -64,21 +71,25 @@ def parse_args():
                     help="pmr = the headline PMR workload (BASELINE configs[1..3]); c5 = the VCR / Oscar-large shape class of configs[4]; "
                          "toy = small dims for the many-rank rehearsal of the N > 1 plumbing (not a measurement)")
     ap.add_argument("--batch", type=int, default=None, help="examples per GPU per step (default: 128 for pmr, 32 for c5 = VCR's 8 x 4 accumulation)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip cpu_baseline and parity_vs_oracle (CPU work)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything that takes runs of its own: roofline.config2 / prefix_rows, "
+                         "cpu_baseline, parity_vs_oracle, config3_full_fwd_bwd, the secondary workloads and (N > 1) the communicator checks; "
+                         "the --no-* options below leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline and parity_vs_oracle (CPU work)")
     ap.add_argument("--parity-examples", type=int, default=256,
-                    help="synthetic 'val' examples for the answer-agreement rate against the CPU oracle (time-boxed)")
-    ap.add_argument("--parity-seconds", type=float, default=120.0, help="time box of the oracle side of the agreement check")
+                    help="--full: synthetic 'val' examples for the answer-agreement rate against the CPU oracle (time-boxed)")
+    ap.add_argument("--parity-seconds", type=float, default=120.0, help="--full: time box of the oracle side of the agreement check")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="REHEARSAL of the N > 1 path on a one-GPU box: every rank uses device 0 and the collectives run over gloo "
                          "(RCCL refuses two ranks on one device).  Exercises spawn, weight broadcast, the bucketed all-reduce hooks "
                          "and the max-over-ranks timing; the printed value is NOT a measurement (config.rehearsal says so)")
-    ap.add_argument("--no-config3", action="store_true", help="skip the second measurement (both encoders trained)")
+    ap.add_argument("--no-config3", action="store_true", help="--full: skip the second measurement (both encoders trained)")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the secondary workloads of the default line (with_roberta = the reference's real step with the prefix "
+                    help="--full: skip the secondary workloads (with_roberta = the reference's real step with the prefix "
                          "RoBERTa-large body trained; c5 = the VCR / Oscar-large shape class)")
     ap.add_argument("--real-step-seconds", type=float, default=40.0,
-                    help="time box of the CPU-oracle evidence of the with_roberta leg (its own cpu_baseline + agreement check)")
-    ap.add_argument("--leg-seconds", type=float, default=60.0, help="time box of each secondary workload (model build excluded)")
+                    help="--full: time box of the CPU-oracle evidence of the with_roberta leg (its own cpu_baseline + agreement check)")
+    ap.add_argument("--leg-seconds", type=float, default=60.0, help="--full: time box of each secondary workload (model build excluded)")
     ap.add_argument("--dropout", type=float, default=0.3,
                     help="hidden_dropout_prob (the reference trains with --drop_out 0.3, live inside the frozen encoders too: "
                          "run_PMR_ModCR.py:171,585); 0 = the eval-mode arithmetic")
@@ -92,13 +103,13 @@ def parse_args():
     ap.add_argument("--last-layer-rows", action="store_true",
                     help="opt-in config.modcr_last_layer_rows for the MAIN measurement: the frozen encoders' last layers skip the token-wise blocks of rows "
                          "ModCR never reads (same loss, logits and gradients).  Off by default: the headline computes every row the reference computes; "
-                         "the default line reports the opt-in step as the secondary field `last_layer_rows`")
+                         "--full reports the opt-in step as the secondary field `last_layer_rows`")
     ap.add_argument("--with-roberta", action="store_true",
                     help="include the 24-layer prefix RoBERTa-large body, forward and backward (SURVEY 8f-1); "
                          "not the default workload (BASELINE north_star names the Oscar/ChunkAlign path)")
     ap.add_argument("--train-encoders", action="store_true",
                     help="run global_enc and seq_enc WITH gradients as the headline (SURVEY 8f-4, the ChunkAlign_CLS_enc4_align "
-                         "variant); by default this is measured second and reported as config3_full_fwd_bwd")
+                         "variant); --full measures it second and reports it as config3_full_fwd_bwd")
     ap.add_argument("--optimizer", choices=("hf", "torch"), default="hf",
                     help="hf = transformers.AdamW arithmetic, what the reference trains with (default); torch = torch.optim.AdamW form (A/B)")
     ap.add_argument("--grad-comm", choices=("fp32", "bf16"), default="fp32",
@@ -599,7 +610,7 @@ def main():
         dump_outputs(args.dump_outputs, loss, run_timed.logits, opt)
     flat_buckets, launched_in_bwd = [list(b) for b in flat.buckets], flat.launched_in_backward
     per_rank_s = run_timed.per_rank_s
-    if world > 1:
+    if world > 1 and args.full:
         # what the communicator itself saw (not the environment): an all-reduce of ones over the RCCL group, its version, and one
         # extra untimed step with every bucket's launch -> completion stamped on the compute stream
         ones = torch.ones(1, device=dev)
@@ -741,27 +752,27 @@ def main():
                 out["roofline"]["traffic"] = pmc_traffic(pmc512)
                 out["roofline"]["traffic_source"] = ("NOT measured in this run: 2*FETCH_SIZE + WRITE_SIZE of the committed rocprofv3 --pmc pass "
                                                      "profiles/%s (same kernel and size, N=512)" % pmc512)
-            # BASELINE configs[1]: N = 256 sequences, fused attention fwd only
             if args.config != "pmr":
                 out["roofline"]["traffic"] = out["roofline"]["traffic_source"] = None
+        if achieved and args.full and args.config == "pmr":
+            # BASELINE configs[1]: N = 256 sequences, fused attention fwd only
             c2 = {"shape": "N=256 S=%d H=%d A=%d (BASELINE configs[1]: batch=64, fused prefix-attention fwd only)" % (s_len, H_OSCAR, A_OSCAR),
                   "algorithmic_gflop_per_launch": round(attn_flops(256) / 1e9, 2), "where": "20 back-to-back launches after the timed region",
                   "traffic": traffic256, "traffic_source": "profiles/%s (committed PMC pass, not live)" % pmc_file if traffic256 else None}
             for nm, tm in (("eval", False), ("train", True)):
-                if (tm and not attn_drop) or args.config != "pmr":
+                if tm and not attn_drop:
                     continue
                 t = kernel_seconds(256, tm)
                 c2[nm] = {"kernel": "qkv_attn4_kernel<1, 192, %d, 2, 0>" % (1 if tm else 0), "avg_launch_us": round(t * 1e6, 2),
                           "achieved": round(attn_flops(256) / t / 1e12, 2), "frac": round(attn_flops(256) / t / PEAK_BF16, 4)}
-            if args.config == "pmr":
-                out["roofline"]["config2"] = c2
-                tp, flp, sq, pfx = prefix_call_seconds()
-                out["roofline"]["prefix_rows"] = {
-                    "shape": "N=256, prefix P=%d + S=%d query rows (keys %d), H=%d A=%d, eval mode" % (pfx, sq, s_len, H_OSCAR, A_OSCAR),
-                    "avg_call_us": round(tp * 1e6, 2), "algorithmic_gflop_per_call": round(flp / 1e9, 2),
-                    "achieved": round(flp / tp / 1e12, 2), "frac": round(flp / tp / PEAK_BF16, 4),
-                    "where": "20 back-to-back modcr_qkv_attn_fwd calls with history_state after the timed region; the call = one row-concatenation "
-                             "launch into the workspace + qkv_attn4_kernel<1,192,0> over the 180-row tile (torch events around the loop)"}
+            out["roofline"]["config2"] = c2
+            tp, flp, sq, pfx = prefix_call_seconds()
+            out["roofline"]["prefix_rows"] = {
+                "shape": "N=256, prefix P=%d + S=%d query rows (keys %d), H=%d A=%d, eval mode" % (pfx, sq, s_len, H_OSCAR, A_OSCAR),
+                "avg_call_us": round(tp * 1e6, 2), "algorithmic_gflop_per_call": round(flp / 1e9, 2),
+                "achieved": round(flp / tp / 1e12, 2), "frac": round(flp / tp / PEAK_BF16, 4),
+                "where": "20 back-to-back modcr_qkv_attn_fwd calls with history_state after the timed region; the call = one row-concatenation "
+                         "launch into the workspace + qkv_attn4_kernel<1,192,0> over the 180-row tile (torch events around the loop)"}
 
     # ---- secondary workloads of the same line, each with its own model / optimizer / batches, ms per step and the in-step fused
     # attention fraction of ITS main attention shape (kernel-exact events, as `roofline`):
@@ -828,8 +839,8 @@ def main():
         torch.cuda.empty_cache()
         return res
 
-    plain = not args.train_encoders and not args.with_roberta and args.h2d == "none" and args.config == "pmr"
-    if plain and not args.no_config3:
+    default_workload = not args.train_encoders and not args.with_roberta and args.h2d == "none" and args.config == "pmr"
+    if args.full and default_workload and not args.no_config3:
         del opt, flat
         r3 = leg(True, False, "pmr", 10,
                  "the same step with global_enc (full pass) and seq_enc TRAINED: 24 encoder layers forward + backward on the HIP kernels "
@@ -837,7 +848,7 @@ def main():
                  "heads, clip + AdamW over all parameters")
         if rank == 0:
             out["config3_full_fwd_bwd"] = r3
-    if plain and not args.no_extra_legs and world == 1:
+    if args.full and default_workload and not args.no_extra_legs and world == 1:
         out["with_roberta"] = leg(False, True, "pmr", 5,
                                   "the reference's real training step (SURVEY 8f-1): frozen Oscar encoders + heads as the headline, PLUS the 24-layer "
                                   "prefix RoBERTa-large body (H=1024, 16 heads, S=106) forward and backward on the same kernels, trainable, its own "
@@ -853,6 +864,11 @@ def main():
                         "BASELINE configs[4] shape class (run_vcr_ModCR.py, Oscar-large): T=194 + R=36 = S 230, H=1024, 16 heads, 24 layers, frozen "
                         "encoders + heads, 32 examples = the reference's 8 x 4 accumulation; the 256-token tile kernels")
     if world > 1 and rank == 0:
+        out["config"]["gradient_buckets"] = {"bytes": [int((e - s_) * 4) for s_, e, _ in flat_buckets], "count": len(flat_buckets),
+                                             "launched_during_backward_last_step": launched_in_bwd, "comm_dtype": args.grad_comm,
+                                             "note": "flat fp32 gradient buffer in reverse registration order, one asynchronous RCCL all-reduce per "
+                                                     "bucket launched from post-accumulate-grad hooks while backward is still running"}
+    if world > 1 and rank == 0 and args.full:
         out["rccl_ranks_seen"] = ranks_seen
         out["config"]["collective"] = {"backend": "gloo (one-GPU rehearsal)" if args.rehearse_on_one_gpu else "nccl (= RCCL on ROCm) %s" % rccl_version,
                                        "ranks_seen_by_all_reduce": ranks_seen,
@@ -861,13 +877,9 @@ def main():
                                                         "and behind the stream-side wait for its all-reduce in finish(); later buckets include the wait "
                                                         "for earlier ones",
                                        "expected_all_reduce_ms": "DESIGN.md section 6: 242 MB of fp32 gradients here (1.66 GB with the RoBERTa body) over 7 xGMI links"}
-        out["config"]["gradient_buckets"] = {"bytes": [int((e - s_) * 4) for s_, e, _ in flat_buckets], "count": len(flat_buckets),
-                                             "launched_during_backward_last_step": launched_in_bwd, "comm_dtype": args.grad_comm,
-                                             "note": "flat fp32 gradient buffer in reverse registration order, one asynchronous RCCL all-reduce per "
-                                                     "bucket launched from post-accumulate-grad hooks while backward is still running"}
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not args.with_roberta and not args.train_encoders and args.config == "pmr":
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.with_roberta and not args.train_encoders and args.config == "pmr":
             mask_cores, ncpu = usable_cpus()
             nthreads = max(1, min(32, ncpu))
             out["cpu_baseline"] = cpu_baseline(model, 4321, nthreads, host_cores=ncpu, affinity_cores=mask_cores)
