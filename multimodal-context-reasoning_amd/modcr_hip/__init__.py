@@ -889,13 +889,35 @@ def dropout(x, p, seed, offset, out=None):
     return out
 
 
-def dropout_residual_ln(x, residual, gamma, beta, eps, p, seed, offset, out_dtype):
-    """LN(dropout(x) + residual): x [M,H] fp32, or fp16 (the bf16 path's sublayer output)"""
+def dropout_residual_ln(x, residual, gamma, beta, eps, p, seed, offset, out_dtype, pre_out=None):
+    """LN(dropout(x) + residual): x [M,H] fp32, or fp16 (the bf16 path's sublayer output).  pre_out: contiguous fp32 or fp16 [M,H]
+    tensor that receives the pre-LayerNorm rows dropout(x) + residual"""
     x = _contig(x) if x.dtype == torch.float16 else _contig(x, torch.float32)
     m, h = x.shape
     r2 = _contig(residual.reshape(m, h)) if residual is not None else None
     out = torch.empty((m, h), dtype=torch_dtype(out_dtype), device=x.device)
+    if pre_out is not None and (pre_out.dtype not in (torch.float32, torch.float16) or pre_out.numel() != m * h or not pre_out.is_contiguous()):
+        raise ValueError("dropout_residual_ln: pre_out must be a contiguous fp32 or fp16 [M,H] tensor")
     _check(lib().modcr_dropout_residual_ln_fwd(_ptr(x), dt_of(x), _ptr(r2), dt_of(r2) if r2 is not None else 0, _ptr(gamma), _ptr(beta),
-                                               float(eps), _ptr(out), out_dtype, None, F32, m, h, float(p), seed, offset, _stream()),
+                                               float(eps), _ptr(out), out_dtype, _ptr(pre_out), dt_of(pre_out) if pre_out is not None else F32,
+                                               m, h, float(p), seed, offset, _stream()),
            "modcr_dropout_residual_ln_fwd")
     return out
+
+
+def layernorm_dropout_bwd(dy, pre, gamma, eps, dgamma, dbeta, want_d_pre=True, want_d_sub=True, dropout=None):
+    """LayerNorm backward of the encoder layer's output blocks from the saved pre-LN rows (modcr_layernorm_dropout_bwd): dy [M,H]
+    fp32 or bf16, pre [M,H] fp32 or fp16, H in {256, 512, 768, 1024}.  Returns (d_pre fp32 [M,H] or None, d_sub bf16 [M,H] or None):
+    d_sub is d_pre under the forward's dropout mask (dropout = (p, seed, offset); None: a plain bf16 copy).  dgamma / dbeta (fp32 [H]
+    or None) are accumulated into."""
+    dy, pre = _contig(dy), _contig(pre)
+    m, h = pre.shape
+    if tuple(dy.shape) != (m, h):
+        raise ValueError("layernorm_dropout_bwd: dy %s against pre %s" % (tuple(dy.shape), tuple(pre.shape)))
+    d_pre = torch.empty((m, h), dtype=torch.float32, device=pre.device) if want_d_pre else None
+    d_sub = torch.empty((m, h), dtype=torch.bfloat16, device=pre.device) if want_d_sub else None
+    p, seed, off = dropout if dropout is not None else (0.0, 0, 0)
+    _check(lib().modcr_layernorm_dropout_bwd(_ptr(dy), dt_of(dy), _ptr(pre), dt_of(pre), _ptr(gamma), float(eps), _ptr(d_pre), _ptr(d_sub),
+                                             _ptr(dgamma), _ptr(dbeta), m, h, float(p), seed, off, _stream()),
+           "modcr_layernorm_dropout_bwd")
+    return d_pre, d_sub

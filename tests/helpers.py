@@ -223,3 +223,28 @@ def attn_drop_keep_torch(seq_ids, heads, s, p, seed, offset, device="cpu", keys=
     f = (w >> ((key_ & 1) * 16)) & 0xffff
     f = torch.where(f >= 32768, f - 65536, f)
     return (f >= thr).to(torch.float32)
+
+
+# ---- hidden-dropout mask: host restatement of csrc/common.h (drop_words / drop_field / drop_threshold) ------------------------
+def hidden_drop_keep(seed, offset, n, p):
+    """keep[i] (numpy bool, length n) of counter ctr = offset + i under modcr_dropout and every row pass that applies the hidden
+    mask: the decision is 15-bit field ctr & 3 of the two hash words of the GROUP ctr >> 2 (fields 0 / 1 = bits 0-14 / 16-30 of
+    x, fields 2 / 3 the same of y), kept iff field >= round(p * 2^15).  uint32 arithmetic except the 64-bit counter; p is the
+    fp32 number the C entry receives."""
+    m32 = np.uint64(0xffffffff)
+    seed, offset = int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+    ctr = np.uint64(offset) + np.arange(n, dtype=np.uint64)                 # wraps mod 2^64 like the device's uint64_t
+    grp = ctr >> np.uint64(2)
+
+    def mul(a, c):                                                          # uint32 product held in uint64
+        return (a * np.uint64(c)) & m32
+
+    x = mul(grp & m32, 0x9E3779B1) ^ mul(grp >> np.uint64(32), 0x85EBCA77) ^ np.uint64(seed & 0xffffffff)
+    x ^= x >> np.uint64(16); x = mul(x, 0x85EBCA6B); x ^= x >> np.uint64(13); x = mul(x, 0xC2B2AE35); x ^= x >> np.uint64(16)
+    y = (mul(x, 0x2C1B3C6D) + np.uint64(seed >> 32)) & m32
+    y ^= y >> np.uint64(15)
+    f = ctr & np.uint64(3)
+    w = np.where((f & np.uint64(2)) != 0, y, x)
+    u = (w >> ((f & np.uint64(1)) * np.uint64(16))) & np.uint64(0x7fff)
+    thr = int(float(np.float32(p)) * 32768.0 + 0.5)
+    return u >= np.uint64(thr)

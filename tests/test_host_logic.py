@@ -688,3 +688,64 @@ def test_gemm_route_table_on_the_host():
         mh.linear_route((4096, 256), (256, 256), act=mh.ACT_GELU, out_dtype=mh.F16)
     with pytest.raises(mh.ModcrHipError, match="multiple of 64"):
         mh.linear_route((4096, 200), (256, 200))
+
+
+def test_hidden_dropout_mask_restatement_properties():
+    """helpers.hidden_drop_keep, the host statement of csrc/common.h's drop_words / drop_field / drop_threshold that the GPU tests of
+    tests/test_hip_rowops.py hold every consumer of the hidden mask to: properties that need no device."""
+    n = 1 << 20
+    for seed, off in ((1234, 77), (4242, 2 ** 33), (2 ** 63 + 5, 2 ** 40 + 3)):
+        assert H.hidden_drop_keep(seed, off, 4099, 0.0).all()                               # p = 0 keeps everything
+        for p in (0.1, 0.3, 0.5):
+            keep = H.hidden_drop_keep(seed, off, n, p)
+            assert keep.dtype == np.bool_ and keep.shape == (n,)
+            assert abs(keep.mean() - (1 - p)) < 4e-3, (seed, off, p, keep.mean())           # the bound of the GPU statistics test
+            # shift equivariance (also across the unaligned start): counter off + 5 + i is counter off + (i + 5)
+            assert np.array_equal(H.hidden_drop_keep(seed, off + 5, 1000, p), H.hidden_drop_keep(seed, off, 1005, p)[5:])
+            # no dependence on n
+            assert np.array_equal(H.hidden_drop_keep(seed, off, 37, p), keep[:37])
+    base = H.hidden_drop_keep(1234, 77, 4096, 0.3)
+    assert not np.array_equal(base, H.hidden_drop_keep(1234 + 2 ** 32, 77, 4096, 0.3))      # high word of the seed
+    assert not np.array_equal(base, H.hidden_drop_keep(1234, 77 + 2 ** 34, 4096, 0.3))      # high word of the group (ctr >> 2 >> 32)
+    assert not np.array_equal(base, H.hidden_drop_keep(1235, 77, 4096, 0.3))
+    # field order: counters 4g .. 4g + 3 read bits 0-14 / 16-30 of x, then of y; threshold round(p * 2^15)
+    x = 5 * 0x9E3779B1 & 0xffffffff                 # group 5, seed 0
+    x ^= x >> 16; x = x * 0x85EBCA6B & 0xffffffff; x ^= x >> 13; x = x * 0xC2B2AE35 & 0xffffffff; x ^= x >> 16
+    y = x * 0x2C1B3C6D & 0xffffffff
+    y ^= y >> 15
+    fields = [x & 0x7fff, (x >> 16) & 0x7fff, y & 0x7fff, (y >> 16) & 0x7fff]
+    for p in (0.1, 0.3, 0.77):
+        thr = int(p * 32768 + 0.5)
+        assert list(H.hidden_drop_keep(0, 20, 4, p)) == [f >= thr for f in fields]
+    for f in fields:                                 # kept iff field >= threshold: the field itself is kept, the field + 1 is not
+        if 0 < f < 32767:
+            k = fields.index(f)
+            assert H.hidden_drop_keep(0, 20, 4, (f - 0.25) / 32768.0)[k] and not H.hidden_drop_keep(0, 20, 4, (f + 0.75) / 32768.0)[k]
+
+
+def test_rowops_case_tables_cover_every_route():
+    """tests/test_hip_rowops.py states in each case's id the kernel and rows-per-wave count its shape lands on (the dispatcher's
+    rule, restated there); the tables must keep reaching every kernel x rpw class and every dtype route."""
+    import test_hip_rowops as T
+    got = {(k, T.rpw_class(r)) for k, r in (T.ln_bwd_route(m, h) for m, h in T.LN_BWD_CASES)}
+    assert got == {(k, c) for k in ("rows4", "rows12", "rows16", "generic") for c in ("1", "2-15", "16")}, got
+    assert T.ln_bwd_route(4097, 256) == ("rows4", 1) and T.ln_bwd_route(8197, 257) == ("rows12", 2) and T.ln_bwd_route(27136, 769) == ("rows16", 6)
+    assert T.ln_bwd_route(46080, 1024) == ("rows16", 11) and T.ln_bwd_route(70001, 1025) == ("generic", 16)
+    for m, rem in ((8197, 8), (27136, 24), (70001, 64)):            # ragged last wave: M is no multiple of 4 rpw
+        assert m % rem != 0 and m % (4 * T.rows_per_wave(m)) != 0
+    for kernel, hs in T.LN_BWD_H.items():                           # every listed H at every small M, one H per kernel at the large ones
+        for h in hs:
+            assert {m for m, hh in T.LN_BWD_CASES if hh == h} >= set(T.LN_BWD_SMALL_M)
+        assert {m for m, hh in T.LN_BWD_CASES if hh in hs} >= set(T.LN_BWD_LARGE_M)
+    vec = {T.vec_route(*c)[:3] for c in T.VEC_CASES}
+    assert vec == {(nv, dy, pre) for nv in (1, 2, 3, 4) for dy in ("f32", "bf16") for pre in ("f32", "f16")}, vec
+    assert {(T.vec_route(*c)[0], T.rpw_class(T.vec_route(*c)[3])) for c in T.VEC_CASES} >= {(nv, c) for nv in (1, 2, 3, 4) for c in ("1", "2-15")}
+    assert {dt for c in T.VEC_CASES if c[0] >= 8192 for dt in [c[2:]]} == set(T.VEC_DT)
+    ids = [T.ln_bwd_id(c) for c in T.LN_BWD_CASES] + [T.vec_id(c) for c in T.VEC_CASES]
+    assert len(set(ids)) == len(ids)
+    assert set(T.LN_FWD_ROUTES) == {(i, r, o) for i in ("bf16", "f32") for r in ("bf16", "f32") for o in ("bf16", "f32")} | \
+        {("f16", None, "bf16"), ("f16", "bf16", "bf16")} and len(T.LN_FWD_ROUTES) == 10
+    assert set(T.LN_FWD_H) >= {4, 132, 260, 1020, 1024} and set(T.LN_FWD_M) >= {1, 5, 37, 4099}
+    assert set(T.FUSED_ROUTES) == {("f32", r, o) for r in (None, "bf16", "f32") for o in ("bf16", "f32")} | \
+        {("f16", None, "bf16"), ("f16", "bf16", "bf16")}
+    assert set(T.FUSED_H) >= {256, 772, 1024}
