@@ -114,10 +114,36 @@ int modcr_qkv_attn_opt_fwd(const void* x, const void* hist, const void* wqkv, co
                            int32_t chunk_t, void* ctx, float* probs, float* align_map, int32_t align_t, float* lse, void* qkv_dump, int32_t N,
                            int32_t S, int32_t P, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
                            void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
+/* Attention forward with an ADDITIVE mask / bias and a head mask: softmax(q.k / 8 + bias), dropout, x head_mask, . V -- the
+ * arithmetic of the reference's modeling_bert.py:55-68 for whatever float mask it is handed (soft biases, -5000, -inf, finfo.min),
+ * where the entries above take one bit per key.  P + S <= 512, bf16 and fp32.
+ *   bias      fp32, element (n, head a, query q, key j) at bias[n stride_n + a stride_a + q stride_q + j]: strides in ELEMENTS,
+ *             0 = broadcast over that dimension, key stride 1 -- [N,1,1,L], [N,1,S,L], [1,A,S,L], [N,A,S,L] and expand()ed views
+ *             are passed as they are.  NULL = no bias.  -inf entries are legal; a query row whose EVERY key is -inf leaves
+ *             with context 0 and probabilities 0 (the reference's softmax gives NaN there: the one deliberate difference).  A
+ *             row of -10000 everywhere is the uniform softmax, as with the binary masks.
+ *   head_mask fp32, element (n, a) at head_mask[n head_mask_stride_n + a] (stride 0 = one [A] vector for every sequence):
+ *             multiplies the head's probabilities after softmax and dropout -- its 64 context columns, probs and align_map.
+ *             NULL = 1.  bias and head_mask may not both be NULL (that call is modcr_qkv_attn_opt_fwd).
+ *   attn_p > 0 (P + S <= 256 only, MODCR_ERR_UNSUPPORTED above): the keep decisions every other route makes for the same
+ *             (seed, offset); the context uses P o m / (1 - p), the side outputs the un-dropped probabilities, or with
+ *             MODCR_ATTN_SIDE_POST_DROPOUT the post-dropout ones.
+ *   chunk_id / ctx / probs / align_map / align_t: as modcr_qkv_attn_fwd.  No lse, no qkv_dump, no backward.
+ *   workspace: modcr_qkv_attn_bias_workspace = N (P+S) 3H elements of the storage dtype at EVERY key count: [hist ; x] is
+ *             projected into it (modcr_linear_fwd), the chunk-mean applied, then the streaming core of csrc/attn_long.hip runs.
+ * Every argument is validated before the first launch.  modcr_time_next_attn times this core too. */
+int64_t modcr_qkv_attn_bias_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype);
+int modcr_qkv_attn_bias_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                            const float* bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                            const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
+                            void* ctx, float* probs, float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P,
+                            int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
+                            void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
 /* Measurement hook: the NEXT bf16 modcr_qkv_attn_fwd / _dropout_fwd launch issued by the calling thread stamps the two
  * hipEvent_t (caller-created, timing enabled) at the start and the end of its kernel (hipExtLaunchKernel) -- the kernel's
  * own duration, as rocprofv3 --kernel-trace reports it, without the two extra barrier packets of a hipEventRecord pair.
- * Consumed by that one launch; (NULL, NULL) clears it.  bench.py's `roofline` uses it. */
+ * Consumed by that one launch; (NULL, NULL) clears it.  bench.py's `roofline` uses it.  The streaming core behind
+ * modcr_qkv_attn_opt_fwd above 256 keys and behind modcr_qkv_attn_bias_fwd is timed the same way (the core, not the projection). */
 int modcr_time_next_attn(void* start_event, void* stop_event);
 /* bytes of `workspace` modcr_qkv_attn_fwd needs (0 for the fused bf16 path; the q | k | v rows above 256 keys) */
 int64_t modcr_qkv_attn_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype);

@@ -2234,6 +2234,30 @@ extern "C" int modcr_qkv_attn_lse_fwd(const void* x, const void* hist, const voi
                                   N, S, P, H, A, attn_p, seed, offset, 0, workspace, workspace_bytes, dtype, stream);
 }
 
+// Shared by the two entries that run the streaming core of attn_long.hip: project [hist ; x] once into the workspace (x rows
+// [N*S][3H], then the prefix rows [N*P][3H]), chunk-mean the query columns, launch the core on `g` (arguments already validated).
+static int attn_long_project_and_launch(const void* x, const void* hist, const void* wqkv, const float* bqkv, const int32_t* chunk_id,
+                                        int32_t chunk_t, AttnLongArgs& g, void* workspace, int32_t dtype, modcr_stream_t stream) {
+    const int N = g.N, S = g.S, P = g.P, H = g.H;
+    const int64_t esz = dtype == MODCR_BF16 ? 2 : 4;
+    char* qx = (char*)workspace;
+    char* qh = qx + (int64_t)N * S * 3 * H * esz;
+    int rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, qx, 3 * H, N * S, 3 * H, H, MODCR_ACT_NONE, dtype, dtype, stream);
+    if (rc != MODCR_OK) return rc;
+    if (P > 0) {
+        rc = modcr_linear_fwd(hist, H, wqkv, H, bqkv, nullptr, 0, 0, qh, 3 * H, N * P, 3 * H, H, MODCR_ACT_NONE, dtype, dtype, stream);
+        if (rc != MODCR_OK) return rc;
+    }
+    if (chunk_id) {
+        rc = modcr_chunk_mean_q_fwd(qx, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, dtype, stream);
+        if (rc != MODCR_OK) return rc;
+    }
+    g.qx = qx; g.qh = P > 0 ? qh : nullptr;
+    hipEvent_t ev0 = g_time_start, ev1 = g_time_stop;     // the measurement hook times the core, not the projection
+    g_time_start = g_time_stop = nullptr;
+    return modcr_launch_attn_long(g, dtype, (hipStream_t)stream, ev0, ev1);
+}
+
 // 256 < P + S <= 512 (eval mode): project [hist ; x] once into the workspace (x rows [N*S][3H], then the prefix rows
 // [N*P][3H]), chunk-mean the query columns, then the streaming core of attn_long.hip.  No dropout, no row statistics,
 // no q|k|v dump: those exist for the backward, which stops at 256 keys.
@@ -2270,26 +2294,66 @@ static int qkv_attn_long_fwd(const void* x, const void* hist, const void* wqkv, 
     if (dtype == MODCR_BF16)
         MODCR_REQUIRE(modcr_aligned16(x) && modcr_aligned16(wqkv) && modcr_aligned16(ctx) && (P == 0 || modcr_aligned16(hist)),
                       "qkv_attn_fwd(bf16): 16-byte alignment");
-    const int64_t esz = dtype == MODCR_BF16 ? 2 : 4;
-    char* qx = (char*)workspace;
-    char* qh = qx + (int64_t)N * S * 3 * H * esz;
-    int rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, qx, 3 * H, N * S, 3 * H, H, MODCR_ACT_NONE, dtype, dtype, stream);
-    if (rc != MODCR_OK) return rc;
-    if (P > 0) {
-        rc = modcr_linear_fwd(hist, H, wqkv, H, bqkv, nullptr, 0, 0, qh, 3 * H, N * P, 3 * H, H, MODCR_ACT_NONE, dtype, dtype, stream);
-        if (rc != MODCR_OK) return rc;
-    }
-    if (chunk_id) {
-        rc = modcr_chunk_mean_q_fwd(qx, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, dtype, stream);
-        if (rc != MODCR_OK) return rc;
-    }
-    AttnLongArgs g;
-    g.qx = qx; g.qh = P > 0 ? qh : nullptr; g.key_mask = key_mask; g.bits = dense_mask_bits;
+    AttnLongArgs g = {};
+    g.key_mask = key_mask; g.bits = dense_mask_bits;
     g.ctx = ctx; g.probs = probs; g.align_map = align_map;
     g.N = N; g.S = S; g.P = P; g.H = H; g.A = A; g.align_t = align_t;
-    hipEvent_t ev0 = g_time_start, ev1 = g_time_stop;     // the measurement hook times the core, not the projection
-    g_time_start = g_time_stop = nullptr;
-    return modcr_launch_attn_long(g, dtype, (hipStream_t)stream, ev0, ev1);
+    return attn_long_project_and_launch(x, hist, wqkv, bqkv, chunk_id, chunk_t, g, workspace, dtype, stream);
+}
+
+extern "C" int64_t modcr_qkv_attn_bias_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
+    return (int64_t)N * (P + S) * 3 * H * (dtype == MODCR_BF16 ? 2 : 4);     // q | k | v rows of [x ; hist] at every key count
+}
+
+// Attention forward with an additive fp32 bias (any float mask, broadcastable over sequence / head / query) and / or a per-head
+// multiplier, P + S <= 512: the projection sequence of qkv_attn_long_fwd, then the bias variant of the streaming core.
+extern "C" int modcr_qkv_attn_bias_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                                       const float* bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                                       const float* head_mask, int64_t head_mask_stride_n,
+                                       const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
+                                       float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P,
+                                       int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
+                                       void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
+    MODCR_REQUIRE(x && wqkv && bqkv && ctx, "qkv_attn_bias_fwd: null pointer");
+    MODCR_REQUIRE(bias || head_mask, "qkv_attn_bias_fwd: neither bias nor head_mask (that call belongs to modcr_qkv_attn_opt_fwd)");
+    MODCR_REQUIRE((flags & ~MODCR_ATTN_SIDE_POST_DROPOUT) == 0, "qkv_attn_bias_fwd: unknown flags 0x%x", flags);
+    MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "qkv_attn_bias_fwd: unknown dtype %d", dtype);
+    MODCR_REQUIRE(N > 0 && S > 0 && P >= 0 && A > 0, "qkv_attn_bias_fwd: bad shape");
+    MODCR_REQUIRE(H == A * 64, "qkv_attn_bias_fwd: head size must be 64 (H=%d, A=%d)", H, A);
+    const int L = P + S;
+    if (L > 512) {
+        modcr_set_error("qkv_attn_bias_fwd: P+S=%d exceeds the 512-key limit of the attention forward", L);
+        return MODCR_ERR_UNSUPPORTED;
+    }
+    MODCR_REQUIRE(attn_p >= 0.f && attn_p < 1.f, "qkv_attn_bias_fwd: attention dropout p=%g out of [0, 1)", attn_p);
+    if (attn_p > 0.f && L > 256) {
+        modcr_set_error("qkv_attn_bias_fwd: attention-probability dropout (p=%g) is not implemented above 256 keys (P+S=%d)", attn_p, L);
+        return MODCR_ERR_UNSUPPORTED;
+    }
+    MODCR_REQUIRE(P == 0 || hist, "qkv_attn_bias_fwd: P=%d but hist is null", P);
+    MODCR_REQUIRE(bias_stride_n >= 0 && bias_stride_a >= 0 && bias_stride_q >= 0 && head_mask_stride_n >= 0,
+                  "qkv_attn_bias_fwd: negative stride");
+    MODCR_REQUIRE(!chunk_id || (chunk_t > 0 && chunk_t <= S), "qkv_attn_bias_fwd: chunk_t=%d out of range", chunk_t);
+    MODCR_REQUIRE(!align_map || (align_t > 0 && align_t < S), "qkv_attn_bias_fwd: align_t=%d out of range", align_t);
+    MODCR_REQUIRE(N <= 65535 && A <= 65535, "qkv_attn_bias_fwd: grid of N=%d sequences x A=%d heads too large", N, A);
+    const int64_t need = modcr_qkv_attn_bias_workspace(N, S, P, H, dtype);
+    MODCR_REQUIRE(workspace && workspace_bytes >= need && modcr_aligned16(workspace),
+                  "qkv_attn_bias_fwd: workspace %lld < %lld bytes (or unaligned)", (long long)workspace_bytes, (long long)need);
+    MODCR_REQUIRE(((uintptr_t)bias & 3) == 0 && ((uintptr_t)head_mask & 3) == 0, "qkv_attn_bias_fwd: bias / head_mask not 4-byte aligned");
+    if (dtype == MODCR_BF16)
+        MODCR_REQUIRE(modcr_aligned16(x) && modcr_aligned16(wqkv) && modcr_aligned16(ctx) && (P == 0 || modcr_aligned16(hist)),
+                      "qkv_attn_bias_fwd(bf16): 16-byte alignment");
+    AttnLongArgs g = {};
+    g.ctx = ctx; g.probs = probs; g.align_map = align_map;
+    g.N = N; g.S = S; g.P = P; g.H = H; g.A = A; g.align_t = align_t;
+    g.bias = bias; g.bias_sn = bias_stride_n; g.bias_sa = bias_stride_a; g.bias_sq = bias_stride_q;
+    g.head_mask = head_mask; g.head_mask_sn = head_mask_stride_n;
+    g.drop_keep = 1.f;
+    if (attn_p > 0.f) {                                     // the mask of every other route for the same (seed, offset)
+        g.drop_thr16 = attn_thr16(attn_p); g.drop_key = seed + offset * 0x9E3779B97F4A7C15ull;
+        g.drop_keep = 1.0f / (1.0f - attn_p); g.side_post_drop = (flags & MODCR_ATTN_SIDE_POST_DROPOUT) ? 1 : 0;
+    }
+    return attn_long_project_and_launch(x, hist, wqkv, bqkv, chunk_id, chunk_t, g, workspace, dtype, stream);
 }
 
 // flags: MODCR_ATTN_SIDE_POST_DROPOUT = the probabilities / align map leave AFTER the dropout, P o m / (1 - p), as the reference's

@@ -125,13 +125,22 @@ struct AttnBwdArgs {
 // attn_bwd.hip: launches attn_bwd5_kernel on `b` (bf16 rows, 0 < S <= 192, lse and ctx given, no align-map gradient)
 __attribute__((visibility("hidden"))) int modcr_launch_attn_bwd5(const AttnBwdArgs& b, hipStream_t stream);
 
-// attn_long.hip: the attention core above 256 keys (256 < P + S <= 512, no dropout) over q | k | v rows the dispatcher
-// projected: qx [N*S][3H] (queries, chunk-mean applied), qh [N*P][3H] (prefix rows) -- bf16 or fp32 as `dtype`
+// attn_long.hip: the streaming attention core (P + S <= 512) over q | k | v rows the dispatcher projected: qx [N*S][3H] (queries,
+// chunk-mean applied), qh [N*P][3H] (prefix rows) -- bf16 or fp32 as `dtype`.  Binary masks (key_mask / bits: above 256 keys, no
+// dropout), or -- bias and / or head_mask set -- the additive-bias variant of modcr_qkv_attn_bias_fwd at any P + S <= 512.
 struct AttnLongArgs {
     const void* qx; const void* qh;
     const float* key_mask; const uint32_t* bits;
     void* ctx; float* probs; float* align_map;
     int N, S, P, H, A, align_t;
+    // bias variant: bias[n sn + a sa + q sq + j] fp32 (strides in elements, 0 = broadcast; NULL = no bias), head_mask[n hsn + a]
+    // (NULL = 1); dropout of the probabilities (P + S <= 256): 0 = off, else thr16 = round(p * 2^16), the 64-bit key, 1 / (1 - p)
+    const float* bias; int64_t bias_sn, bias_sa, bias_sq;
+    const float* head_mask; int64_t head_mask_sn;
+    uint32_t drop_thr16;
+    uint64_t drop_key;
+    float drop_keep;
+    int side_post_drop;
 };
 // ev0 / ev1 (or NULL): stamped at the start and the end of the kernel (modcr_time_next_attn)
 __attribute__((visibility("hidden"))) int modcr_launch_attn_long(const AttnLongArgs& p, int32_t dtype, hipStream_t stream, hipEvent_t ev0,

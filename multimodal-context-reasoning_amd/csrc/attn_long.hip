@@ -1,4 +1,8 @@
-// Attention core for 256 < P + S <= 512 keys, forward only, no attention-probability dropout (inference / eval mode).
+// Streaming attention core, forward only.  Two uses:
+//   * 256 < P + S <= 512 keys with a binary mask (key mask / dense mask bits), no attention-probability dropout (inference /
+//     eval mode): modcr_qkv_attn_opt_fwd above the tile kernels' 256 keys;
+//   * any P + S <= 512 with an ADDITIVE fp32 bias per (sequence, head, query, key) and / or a per-head multiplier
+//     (modcr_qkv_attn_bias_fwd): the BIAS instantiations below, see "Bias variant" further down.
 //
 // The tile kernels of attn.hip hold the whole key row of a head in LDS; above 256 keys it does not fit, so this core
 // streams the keys in tiles of 64 with an online softmax (flash-style).  Its inputs are the q | k | v rows the dispatcher
@@ -18,6 +22,21 @@
 //
 // fp32 parity core: the same tiling with VALU products, 4 waves x 16 queries, key on the lane for the scores and
 // feature on the lane for the context.
+//
+// Bias variant (MODE 1, MODE 2 = with attention-probability dropout): the score of (n, head a, query q, key j) is
+//   q.k / 8 x log2e + bias[n sn + a sa + q sq + j] x log2e      (strides in elements, 0 = broadcast, key stride 1)
+// A lane's keys of one 16-key block are four consecutive floats: one 16-byte load when the address is 16-byte aligned and the four
+// keys are inside the row, four scalar loads otherwise (L % 4 != 0 with sq = L breaks the alignment on odd rows).  The bias of tile
+// t + 1 is requested together with its K / V rows and waits in registers under tile t's arithmetic; with sq = 0 it is loaded once per
+// tile for both query sub-blocks.  -inf entries are legal: while a row's running max is -inf the exponentials are taken against 0
+// (the tile contributes 0, the rescale of the empty accumulators is harmless), and a row whose every key is -inf leaves with context
+// 0 and probabilities 0 -- the one deliberate difference from the reference, whose softmax gives NaN there.  A row of -10000
+// everywhere is the uniform softmax, as on the binary routes.  head_mask[n hsn + a] (NULL = 1) multiplies the head's probabilities
+// after softmax and dropout: the 64 context columns in the epilogue and the side outputs in the second sweep.
+// Dropout (P + S <= 256 only, MODE 2): the keep decisions of attn_common.h for row counter (n A + head) x 256 + query, keys over
+// [prefix ; x]; the lane's g is the layout's l4, so attn_drop8_rt clears the dropped bf16 pairs of the P^T fragments as in the tile
+// kernels.  The context is P o m / (1 - p); the side outputs are the un-dropped probabilities, or with side_post_drop the
+// post-dropout ones (the second sweep regenerates the keep bits).
 #include <hip/hip_ext.h>
 
 #include "common.h"
@@ -48,8 +67,11 @@ __device__ __forceinline__ uint32_t lg_half(const uint4& v, int e) {
     return (e & 1) ? (w >> 16) : (w & 0xffffu);
 }
 
-template <bool SIDE>
-__global__ __launch_bounds__(128) void attn_long_bf16_kernel(AttnLongArgs p) {
+// MODE 0 = binary masks (key_mask / bits), 1 = bias / head mask, 2 = the same with dropout.  LDS admits four workgroups per CU = two
+// waves per SIMD; the bias instantiations are asked to stay inside that register budget (left alone they take 208-230 VGPRs beside 32
+// AGPRs and the ones with side outputs drop to one wave per SIMD; asked, 224-236 unified, no spill).  MODE 0 compiles as before.
+template <bool SIDE, int MODE>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MODE != 0 ? 2 : 1))) void attn_long_bf16_kernel(AttnLongArgs p) {
     __shared__ __attribute__((aligned(16))) bf16 sm[2 * LG_BUF];
     const int S = p.S, L = p.P + S, H = p.H;
     const int n = blockIdx.z, a = blockIdx.y;
@@ -101,8 +123,40 @@ __global__ __launch_bounds__(128) void attn_long_bf16_kernel(AttnLongArgs p) {
             }
         }
     };
+    // bias variant: the lane's 4 x 4 bias values of a tile per query sub-block (natural-log domain, as given)
+    [[maybe_unused]] const float* brow[2] = {nullptr, nullptr};
+    [[maybe_unused]] bool bvec[2] = {false, false};
+    if constexpr (MODE != 0) {
+        if (p.bias) {
+#pragma unroll
+            for (int qs = 0; qs < 2; ++qs) {
+                brow[qs] = p.bias + n * p.bias_sn + a * p.bias_sa + (qrow[qs] < S ? qrow[qs] : S - 1) * p.bias_sq;
+                bvec[qs] = (reinterpret_cast<uintptr_t>(brow[qs]) & 15) == 0;
+            }
+        }
+    }
+    [[maybe_unused]] auto load_bias = [&](int t, f32x4 (&bb)[2][4]) {
+        const int nq = p.bias_sq == 0 ? 1 : 2;      // one bias row for every query: loaded once per tile
+#pragma unroll
+        for (int qs = 0; qs < 2; ++qs) {
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) {
+                const int j = t * 64 + kb * 16 + 4 * g;
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (qs < nq && brow[qs]) {
+                    if (bvec[qs] && j + 3 < L) v = *reinterpret_cast<const f32x4*>(brow[qs] + j);
+                    else {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (j + i < L) v[i] = brow[qs][j + i];
+                    }
+                }
+                bb[qs][kb] = qs < nq ? v : bb[0][kb];
+            }
+        }
+    };
     // S^T of tile t (buffer b) as log2-domain scores: s[qs][kb][i] = key t 64 + 16 kb + 4 g + i, query qrow[qs]
-    auto scores = [&](int t, int b, f32x4 (&s)[2][4]) {
+    auto scores = [&](int t, int b, f32x4 (&s)[2][4], [[maybe_unused]] const f32x4 (&bb)[2][4]) {
         const bf16* K = sm + b * LG_BUF;
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
@@ -114,6 +168,17 @@ __global__ __launch_bounds__(128) void attn_long_bf16_kernel(AttnLongArgs p) {
                 c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf[qs][0], c, 0, 0, 0);
                 s[qs][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf[qs][1], c, 0, 0, 0);
             }
+        }
+        if constexpr (MODE != 0) {
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const bool in = t * 64 + kb * 16 + 4 * g + i < L;
+#pragma unroll
+                    for (int qs = 0; qs < 2; ++qs) s[qs][kb][i] = in ? fmaf(s[qs][kb][i], sc, bb[qs][kb][i] * LOG2E) : -INFINITY;
+                }
+            return;
         }
         // dense mask: the two 32-key words of the tile per query; key mask: one value per key
         uint32_t w[2][2] = {{~0u, ~0u}, {~0u, ~0u}};
@@ -148,14 +213,34 @@ __global__ __launch_bounds__(128) void attn_long_bf16_kernel(AttnLongArgs p) {
 #pragma unroll
         for (int db = 0; db < 4; ++db) o[qs][db] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+    // dropout (MODE 2): the lane's hash base per query sub-block (its g is the layout's l4), the packed threshold
+    [[maybe_unused]] uint32_t dbase[2] = {0u, 0u};
+    [[maybe_unused]] uint32_t dthr2 = 0u;
+    if constexpr (MODE == 2) {
+        dthr2 = attn_thrm1_2(p.drop_thr16);
+#pragma unroll
+        for (int qs = 0; qs < 2; ++qs) dbase[qs] = attn_drop_base((uint32_t)((n * p.A + a) * 256 + qrow[qs]), (uint32_t)g, p.drop_key);
+    }
+
+    f32x4 bcur[2][4], bnext[2][4];
     load(0, true);
+    if constexpr (MODE != 0) load_bias(0, bnext);
     store(0, true);
     __syncthreads();
     for (int t = 0; t < ntiles; ++t) {
         const int b = t & 1;
-        if (t + 1 < ntiles) load(t + 1, true);
+        if constexpr (MODE != 0) {
+#pragma unroll
+            for (int qs = 0; qs < 2; ++qs)
+#pragma unroll
+                for (int kb = 0; kb < 4; ++kb) bcur[qs][kb] = bnext[qs][kb];
+        }
+        if (t + 1 < ntiles) {
+            load(t + 1, true);
+            if constexpr (MODE != 0) load_bias(t + 1, bnext);
+        }
         f32x4 s[2][4];
-        scores(t, b, s);
+        scores(t, b, s, bcur);
         bf16x8 pb[2][2];                            // P^T fragments: step ks = keys 32 ks + (4 g + e | 16 + 4 g + e)
 #pragma unroll
         for (int qs = 0; qs < 2; ++qs) {
@@ -167,17 +252,23 @@ __global__ __launch_bounds__(128) void attn_long_bf16_kernel(AttnLongArgs p) {
             mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
             const float mn = fmaxf(m[qs], mx);
-            const float alpha = __builtin_amdgcn_exp2f(m[qs] - mn);
+            // bias variant: every key so far at -inf -> exponentials against 0, the tile contributes 0 (no exp2(-inf + inf))
+            const float ms = (MODE != 0 && mn == -INFINITY) ? 0.f : mn;
+            const float alpha = __builtin_amdgcn_exp2f(m[qs] - ms);
             m[qs] = mn;
             float sum = 0.f;
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float e = __builtin_amdgcn_exp2f(s[qs][kb][i] - mn);
+                    const float e = __builtin_amdgcn_exp2f(s[qs][kb][i] - ms);
                     sum += e;
                     pb[qs][kb >> 1][(kb & 1) * 4 + i] = (bf16)e;
                 }
+            if constexpr (MODE == 2) {                  // the row sum keeps the un-dropped weights; the context takes P o m
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) pb[qs][ks] = attn_drop8_rt(pb[qs][ks], dbase[qs], 2 * t + ks, p.drop_key, dthr2);
+            }
             lsum[qs] = lsum[qs] * alpha + sum;
 #pragma unroll
             for (int db = 0; db < 4; ++db) o[qs][db] *= alpha;
@@ -198,19 +289,24 @@ __global__ __launch_bounds__(128) void attn_long_bf16_kernel(AttnLongArgs p) {
         __syncthreads();
     }
 
+    // bias variant: the head's multiplier (after softmax and dropout), 1 / (1 - p) of the dropout
+    [[maybe_unused]] float hm = 1.f;
+    if constexpr (MODE != 0) hm = p.head_mask ? p.head_mask[n * p.head_mask_sn + a] : 1.f;
     float inv[2];
 #pragma unroll
     for (int qs = 0; qs < 2; ++qs) {
         float l = lsum[qs];
         l += __shfl_xor(l, 16, 64);
         l += __shfl_xor(l, 32, 64);
-        inv[qs] = 1.0f / l;
+        if constexpr (MODE != 0) inv[qs] = l > 0.f ? hm / l : 0.f;     // a row of -inf everywhere: context 0, probabilities 0
+        else inv[qs] = 1.0f / l;
+        const float oi = MODE == 2 ? inv[qs] * p.drop_keep : inv[qs];
         if (qrow[qs] < S) {
             bf16* c = (bf16*)p.ctx + ((int64_t)n * S + qrow[qs]) * H + a * 64 + 4 * g;
 #pragma unroll
             for (int db = 0; db < 4; ++db) {
-                const bf16x4 w = {(bf16)(o[qs][db][0] * inv[qs]), (bf16)(o[qs][db][1] * inv[qs]), (bf16)(o[qs][db][2] * inv[qs]),
-                                  (bf16)(o[qs][db][3] * inv[qs])};
+                const bf16x4 w = {(bf16)(o[qs][db][0] * oi), (bf16)(o[qs][db][1] * oi), (bf16)(o[qs][db][2] * oi),
+                                  (bf16)(o[qs][db][3] * oi)};
                 *reinterpret_cast<bf16x4*>(c + db * 16) = w;
             }
         }
@@ -223,23 +319,36 @@ __global__ __launch_bounds__(128) void attn_long_bf16_kernel(AttnLongArgs p) {
             load(t, false);
             store(0, false);
             __syncthreads();
+            if constexpr (MODE != 0) load_bias(t, bcur);
             f32x4 s[2][4];
-            scores(t, 0, s);
+            scores(t, 0, s, bcur);
 #pragma unroll
             for (int qs = 0; qs < 2; ++qs) {
                 const int q = qrow[qs];
                 if (q >= S) continue;
+                const float mf = (MODE != 0 && m[qs] == -INFINITY) ? 0.f : m[qs];
 #pragma unroll
-                for (int kb = 0; kb < 4; ++kb)
+                for (int kb = 0; kb < 4; ++kb) {
+                    [[maybe_unused]] uint32_t wx = 0u, wy = 0u;     // the keep words of the lane's four keys of this block
+                    if constexpr (MODE == 2) {
+                        if (p.side_post_drop) {
+                            wx = attn_drop_word(dbase[qs], 2 * (4 * t + kb), p.drop_key);
+                            wy = attn_drop_word(dbase[qs], 2 * (4 * t + kb) + 1, p.drop_key);
+                        }
+                    }
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int j = t * 64 + kb * 16 + 4 * g + i;
                         if (j >= L) continue;
-                        const float pr = __builtin_amdgcn_exp2f(s[qs][kb][i] - m[qs]) * inv[qs];
+                        float pr = __builtin_amdgcn_exp2f(s[qs][kb][i] - mf) * inv[qs];
+                        if constexpr (MODE == 2) {
+                            if (p.side_post_drop) pr = attn_keep_field(wx, wy, i, p.drop_thr16) ? pr * p.drop_keep : 0.f;
+                        }
                         if (p.probs) p.probs[(((int64_t)n * p.A + a) * S + q) * L + j] = pr;
                         if (p.align_map && q < p.align_t && j >= key0)
                             atomicAdd(p.align_map + ((int64_t)n * p.align_t + q) * R + (j - key0), pr);
                     }
+                }
             }
             __syncthreads();
         }
@@ -247,6 +356,7 @@ __global__ __launch_bounds__(128) void attn_long_bf16_kernel(AttnLongArgs p) {
 }
 
 // fp32 parity core: 4 waves x 16 queries per (64-query block, head, sequence); K and V tiles of 64 keys in LDS
+template <bool BIAS>
 __global__ __launch_bounds__(256) void attn_long_f32_kernel(AttnLongArgs p) {
     __shared__ float sK[64 * 65], sV[64 * 65], sQ[4 * 16 * 64], sP[4 * 64];
     const int S = p.S, L = p.P + S, H = p.H;
@@ -283,7 +393,19 @@ __global__ __launch_bounds__(256) void attn_long_f32_kernel(AttnLongArgs p) {
 #pragma unroll 8
         for (int d = 0; d < 64; ++d) s = fmaf(q_img[qi * 64 + d], sK[lane * 65 + d], s);
         const int q = q0 + qi < S ? q0 + qi : S - 1;
-        return j < L ? s * sc + lg_mask(p, n, q, j, L) : -INFINITY;
+        if constexpr (BIAS) {
+            if (j >= L) return -INFINITY;
+            return p.bias ? fmaf(s, sc, p.bias[n * p.bias_sn + a * p.bias_sa + q * p.bias_sq + j] * LOG2E) : s * sc;
+        } else {
+            return j < L ? s * sc + lg_mask(p, n, q, j, L) : -INFINITY;
+        }
+    };
+    // bias variant: keep factor (1 / (1 - p) or 0) of key t 64 + lane for query q0 + qi under the dropout of attn_common.h
+    [[maybe_unused]] auto keep = [&](int t, int qi) {
+        const int j = t * 64 + lane;
+        uint32_t hx, hy;
+        attn_drop_words((uint32_t)((n * p.A + a) * 256 + q0 + qi), j >> 2, p.drop_key, hx, hy);
+        return attn_keep_field(hx, hy, j & 3, p.drop_thr16) ? p.drop_keep : 0.f;
     };
 
     for (int t = 0; t < ntiles; ++t) {
@@ -292,11 +414,13 @@ __global__ __launch_bounds__(256) void attn_long_f32_kernel(AttnLongArgs p) {
         for (int qi = 0; qi < 16; ++qi) {
             const float s = score(t, qi);
             const float mn = fmaxf(m[qi], wave_max(s));
-            const float alpha = exp2f(m[qi] - mn);
-            const float e = exp2f(s - mn);
+            const float ms = (BIAS && mn == -INFINITY) ? 0.f : mn;     // every key so far at -inf: the tile contributes 0
+            const float alpha = exp2f(m[qi] - ms);
+            const float e = exp2f(s - ms);
             lsum[qi] = lsum[qi] * alpha + wave_sum(e);
             m[qi] = mn;
-            p_img[lane] = e;
+            if constexpr (BIAS) p_img[lane] = p.drop_thr16 ? e * keep(t, qi) : e;
+            else p_img[lane] = e;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             float acc = 0.f;
 #pragma unroll 8
@@ -305,9 +429,15 @@ __global__ __launch_bounds__(256) void attn_long_f32_kernel(AttnLongArgs p) {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         }
     }
+    [[maybe_unused]] float hm = 1.f;
+    if constexpr (BIAS) hm = p.head_mask ? p.head_mask[n * p.head_mask_sn + a] : 1.f;
 #pragma unroll
     for (int qi = 0; qi < 16; ++qi)
-        if (q0 + qi < S) ((float*)p.ctx)[((int64_t)n * S + q0 + qi) * H + a * 64 + lane] = o[qi] / lsum[qi];
+        if (q0 + qi < S) {
+            float* c = (float*)p.ctx + ((int64_t)n * S + q0 + qi) * H + a * 64 + lane;
+            if constexpr (BIAS) *c = lsum[qi] > 0.f ? o[qi] * hm / lsum[qi] : 0.f;     // a row of -inf everywhere: 0
+            else *c = o[qi] / lsum[qi];
+        }
 
     if (p.probs || p.align_map) {
         const int R = S - p.align_t, key0 = p.P + p.align_t;
@@ -318,7 +448,13 @@ __global__ __launch_bounds__(256) void attn_long_f32_kernel(AttnLongArgs p) {
                 const float s = score(t, qi);
                 const int q = q0 + qi, j = t * 64 + lane;
                 if (q >= S || j >= L) continue;
-                const float pr = exp2f(s - m[qi]) / lsum[qi];
+                float pr;
+                if constexpr (BIAS) {
+                    pr = lsum[qi] > 0.f ? exp2f(s - m[qi]) * hm / lsum[qi] : 0.f;
+                    if (p.drop_thr16 && p.side_post_drop) pr *= keep(t, qi);
+                } else {
+                    pr = exp2f(s - m[qi]) / lsum[qi];
+                }
                 if (p.probs) p.probs[(((int64_t)n * p.A + a) * S + q) * L + j] = pr;
                 if (p.align_map && q < p.align_t && j >= key0) atomicAdd(p.align_map + ((int64_t)n * p.align_t + q) * R + (j - key0), pr);
             }
@@ -336,11 +472,23 @@ void lg_launch(K kernel, dim3 grid, dim3 block, hipStream_t st, hipEvent_t ev0, 
 
 int modcr_launch_attn_long(const AttnLongArgs& p, int32_t dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     const dim3 grid((p.S + 63) / 64, p.A, p.N);
+    const bool side = p.probs || p.align_map;
+    const int mode = !(p.bias || p.head_mask) ? 0 : p.drop_thr16 ? 2 : 1;
     if (dtype == MODCR_BF16) {
-        if (p.probs || p.align_map) lg_launch(attn_long_bf16_kernel<true>, grid, dim3(128), st, ev0, ev1, p);
-        else lg_launch(attn_long_bf16_kernel<false>, grid, dim3(128), st, ev0, ev1, p);
+        if (mode == 0) {
+            if (side) lg_launch(attn_long_bf16_kernel<true, 0>, grid, dim3(128), st, ev0, ev1, p);
+            else lg_launch(attn_long_bf16_kernel<false, 0>, grid, dim3(128), st, ev0, ev1, p);
+        } else if (mode == 1) {
+            if (side) lg_launch(attn_long_bf16_kernel<true, 1>, grid, dim3(128), st, ev0, ev1, p);
+            else lg_launch(attn_long_bf16_kernel<false, 1>, grid, dim3(128), st, ev0, ev1, p);
+        } else {
+            if (side) lg_launch(attn_long_bf16_kernel<true, 2>, grid, dim3(128), st, ev0, ev1, p);
+            else lg_launch(attn_long_bf16_kernel<false, 2>, grid, dim3(128), st, ev0, ev1, p);
+        }
+    } else if (mode == 0) {
+        lg_launch(attn_long_f32_kernel<false>, grid, dim3(256), st, ev0, ev1, p);
     } else {
-        lg_launch(attn_long_f32_kernel, grid, dim3(256), st, ev0, ev1, p);
+        lg_launch(attn_long_f32_kernel<true>, grid, dim3(256), st, ev0, ev1, p);
     }
-    return modcr_check_launch("attn_long");
+    return modcr_check_launch(mode ? "attn_bias" : "attn_long");
 }

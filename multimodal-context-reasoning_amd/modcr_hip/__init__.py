@@ -35,6 +35,9 @@ SIGNATURES = {
                                       _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
     "modcr_qkv_attn_opt_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32,
                                       _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _i32, _vp, _i64, _i32, _vp]),
+    "modcr_qkv_attn_bias_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_bias_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i32,
+                                       _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _i32, _vp, _i64, _i32, _vp]),
     "modcr_linear_splitk_workspace": (_i64, [_i32, _i32, _i32]),
     "modcr_linear_splitk_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "modcr_qkv_attn_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
@@ -379,8 +382,12 @@ ATTN_MAX_KEYS = 512
 
 def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=None, want_probs=False,
              align_map=None, align_t=0, num_heads=None, workspace=None, out=None, attn_dropout=None, lse=None, dump=None,
-             side_post_dropout=False):
+             side_post_dropout=False, attn_bias=None, head_mask=None):
     """Fused QKV projection + attention.  x [N,S,H]; returns (ctx [N,S,H], probs or None).
+    attn_bias: any float tensor broadcastable to [N, A, S, P+S], ADDED to the scores before the softmax (the reference's additive
+    attention_mask, soft biases, -inf entries); head_mask: [A], [1,A,1,1], [N,A] or [N,A,1,1], multiplies the probabilities of a
+    head after softmax and dropout.  Either one sends the call to modcr_qkv_attn_bias_fwd (the streaming core with a float bias,
+    P + S <= 512, dropout up to 256 keys); they replace key_mask / mask_bits and do not combine with lse / dump.
     attn_dropout = (p, seed, offset): training-mode dropout of the attention probabilities.
     side_post_dropout: probs / align_map are the probabilities AFTER that dropout, P o m / (1 - p), as the reference's modules
     return them (modeling_bert.py:69-74); default: the un-dropped ones (and no probs output under dropout).
@@ -393,6 +400,13 @@ def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=N
     p = 0 if hist is None else hist.shape[1]
     if p + s > ATTN_MAX_KEYS:
         raise ValueError("qkv_attn: P + S = %d keys exceeds the %d-key limit of the attention forward" % (p + s, ATTN_MAX_KEYS))
+    if attn_bias is not None or head_mask is not None:
+        if key_mask is not None or mask_bits is not None:
+            raise ValueError("qkv_attn: attn_bias / head_mask replace key_mask / mask_bits (fold a binary mask into the bias as 0 / -10000)")
+        if lse is not None or dump is not None:
+            raise ValueError("qkv_attn: no row statistics (lse) / q|k|v dump on the attn_bias / head_mask route (forward only)")
+        return _qkv_attn_bias(x, wqkv, bqkv, attn_bias, head_mask, hist, chunk_id, want_probs, align_map, align_t, a, workspace, out,
+                              attn_dropout, side_post_dropout)
     if (dt == BF16 and attn_dropout is not None and attn_dropout[0] > 0.0 and side_post_dropout and (want_probs or align_map is not None)
             and not side_outputs_on_tiles(s, p, h, a)):
         # post-dropout side outputs are served by the bf16 TILE kernels only (modcr_qkv_attn_opt_fwd returns MODCR_ERR_UNSUPPORTED on
@@ -426,6 +440,73 @@ def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=N
                                         _ptr(workspace) if need else None, need, dt, _stream()),
            "modcr_qkv_attn_fwd")
     return ctx, probs
+
+
+def _bias_strides(attn_bias, n, a, s, l):
+    """attn_bias -> (fp32 tensor with unit key stride, element strides over sequence / head / query; 0 = broadcast).  Strides are
+    taken from the tensor as it is (an expand()ed view stays a view); only a non-unit key stride or another dtype makes a copy."""
+    b = attn_bias
+    if not b.is_floating_point():
+        raise ValueError("qkv_attn: attn_bias must be a float tensor, got %s" % b.dtype)
+    if b.dim() > 4:
+        raise ValueError("qkv_attn: attn_bias has %d dimensions, want at most 4 ([N, A, S, L])" % b.dim())
+    b = b.reshape((1,) * (4 - b.dim()) + tuple(b.shape)) if b.dim() < 4 else b
+    for d, full in enumerate((n, a, s)):
+        if b.shape[d] not in (1, full):
+            raise ValueError("qkv_attn: attn_bias %s does not broadcast to [N=%d, A=%d, S=%d, L=%d]" % (tuple(attn_bias.shape), n, a, s, l))
+    if b.shape[3] != l:
+        raise ValueError("qkv_attn: attn_bias %s: the key dimension must be P + S = %d" % (tuple(attn_bias.shape), l))
+    if b.dtype != torch.float32:
+        b = b.to(torch.float32)
+    if l > 1 and b.stride(3) != 1:
+        b = b.contiguous()
+    return b, [0 if b.shape[d] == 1 else b.stride(d) for d in range(3)]
+
+
+def _head_mask_2d(head_mask, n, a):
+    """head_mask [A], [1,A,1,1], [N,A] or [N,A,1,1] -> (contiguous fp32 [1 or N, A], sequence stride in elements)"""
+    hm = head_mask
+    if hm.dim() == 4 and hm.shape[2] == 1 and hm.shape[3] == 1:
+        hm = hm.reshape(hm.shape[0], hm.shape[1])
+    elif hm.dim() == 1:
+        hm = hm.reshape(1, -1)
+    if hm.dim() != 2 or hm.shape[1] != a or hm.shape[0] not in (1, n):
+        raise ValueError("qkv_attn: head_mask %s is not [A], [1,A,1,1], [N,A] or [N,A,1,1] (N=%d, A=%d)" % (tuple(head_mask.shape), n, a))
+    hm = _contig(hm, torch.float32)
+    return hm, (0 if hm.shape[0] == 1 else a)
+
+
+def _qkv_attn_bias(x, wqkv, bqkv, attn_bias, head_mask, hist, chunk_id, want_probs, align_map, align_t, a, workspace, out, attn_dropout,
+                   side_post_dropout):
+    """qkv_attn with attn_bias / head_mask: modcr_qkv_attn_bias_fwd"""
+    dt = dt_of(x)
+    n, s, h = x.shape
+    p = 0 if hist is None else hist.shape[1]
+    l = p + s
+    ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
+    if ap > 0.0 and l > ATTN_TILE_KEYS:
+        raise ValueError("qkv_attn: attention-probability dropout with attn_bias / head_mask stops at %d keys (P + S = %d)" % (ATTN_TILE_KEYS, l))
+    bias, (bsn, bsa, bsq) = (None, (0, 0, 0)) if attn_bias is None else _bias_strides(attn_bias, n, a, s, l)
+    hm, hsn = (None, 0) if head_mask is None else _head_mask_2d(head_mask, n, a)
+    hist = _contig(hist)
+    ctx = torch.empty_like(x) if out is None else out
+    probs = torch.empty((n, a, s, l), dtype=torch.float32, device=x.device) if want_probs else None
+    need = lib().modcr_qkv_attn_bias_workspace(n, s, p, h, dt)
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=x.device)
+    chunk_t = 0 if chunk_id is None else chunk_id.shape[1]
+    _check(lib().modcr_qkv_attn_bias_fwd(_ptr(x), _ptr(hist), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq, _ptr(hm), hsn,
+                                         _ptr(chunk_id), chunk_t, _ptr(ctx), _ptr(probs), _ptr(align_map), align_t, n, s, p, h, a,
+                                         float(ap), seed, off, ATTN_SIDE_POST_DROPOUT if side_post_dropout else 0,
+                                         _ptr(workspace), need, dt, _stream()),
+           "modcr_qkv_attn_bias_fwd")
+    return ctx, probs
+
+
+def additive_mask_is_binary(mask):
+    """True iff every element of the additive mask is 0 or -10000 -- what the binary routes (key mask / dense mask bits) compute
+    exactly.  One reduction and one host read; CPU tensors work too."""
+    return bool(((mask == 0) | (mask == -10000.0)).all().item())
 
 
 def side_outputs_on_tiles(s, p, h, a):

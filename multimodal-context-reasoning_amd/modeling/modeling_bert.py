@@ -8,13 +8,19 @@ import modcr_hip as mh
 from .bert_primitives import BertSelfAttention, BertSelfOutput, additive_to_binary
 
 
-def split_additive_mask(attention_mask, n, s, l):
-    """additive [N,1,1,L] -> key mask [N,L]; additive [N,1,S,L] -> packed bits [N,S,LW]."""
-    if attention_mask.dim() != 4 or attention_mask.shape[1] != 1:
-        raise ValueError("attention_mask must be [N,1,1,L] or [N,1,S,L], got %s" % (tuple(attention_mask.shape),))
-    if attention_mask.shape[2] == 1:
-        return additive_to_binary(attention_mask.reshape(n, l)), None
-    return None, mh.pack_mask_bits(additive_to_binary(attention_mask.reshape(n, s, l)))
+def split_additive_mask(attention_mask, n, s, l, head_mask=None):
+    """The reference's additive attention_mask -> the arguments of hip_forward, as a dict.
+    A 0 / -10000 mask without head_mask takes the binary routes: [N,1,1,L] -> key_mask [N,L], [N,1,S,L] -> mask_bits [N,S,LW].
+    Anything else -- a soft bias, -5000, -inf, a per-head mask [.,A,.,L], a head_mask -- is added as it is (attn_bias) on the
+    general route (modcr_qkv_attn_bias_fwd); the head mask goes with it.  The check costs one reduction and one host read, and is
+    paid only by the reference-signature forward()s: the encoders' hip_forward hot path takes 0/1 masks and never comes here."""
+    if attention_mask.dim() != 4:
+        raise ValueError("attention_mask must be 4-D, broadcastable to [N,A,S,L], got %s" % (tuple(attention_mask.shape),))
+    if head_mask is None and attention_mask.shape[1] == 1 and mh.additive_mask_is_binary(attention_mask):
+        if attention_mask.shape[2] == 1:
+            return dict(key_mask=additive_to_binary(attention_mask.reshape(n, l)))
+        return dict(mask_bits=mh.pack_mask_bits(additive_to_binary(attention_mask.reshape(n, s, l))))
+    return dict(attn_bias=attention_mask, head_mask=head_mask)
 
 
 class CaptionBertSelfAttention(BertSelfAttention):
@@ -26,7 +32,9 @@ class CaptionBertSelfAttention(BertSelfAttention):
         self.side_post_dropout = bool(getattr(config, "modcr_align_map_post_dropout", True))
 
     def hip_forward(self, x, key_mask=None, mask_bits=None, hist=None, chunk_id=None, want_probs=False,
-                    align_map=None, align_t=0, workspace=None, out=None):
+                    align_map=None, align_t=0, workspace=None, out=None, attn_bias=None, head_mask=None):
+        """attn_bias / head_mask (instead of key_mask / mask_bits): an additive float mask broadcastable to [N,A,S,L] and a
+        per-head multiplier of the probabilities, mh.qkv_attn's general route."""
         w, b = self.packed_qkv(x.dtype)
         drop = None
         if self.training and self.dropout.p > 0.0:      # nn.Dropout on the probabilities (modeling_bert.py:69), training mode
@@ -46,16 +54,14 @@ class CaptionBertSelfAttention(BertSelfAttention):
         return mh.qkv_attn(x, w, b, key_mask=key_mask, mask_bits=mask_bits, hist=hist, chunk_id=chunk_id,
                            want_probs=want_probs, align_map=align_map, align_t=align_t,
                            num_heads=self.num_attention_heads, workspace=workspace, out=out, attn_dropout=drop,
-                           side_post_dropout=self.side_post_dropout and drop is not None and (want_probs or align_map is not None))
+                           side_post_dropout=self.side_post_dropout and drop is not None and (want_probs or align_map is not None),
+                           attn_bias=attn_bias, head_mask=head_mask)
 
     def forward(self, hidden_states, attention_mask, head_mask=None, history_state=None):
-        if head_mask is not None:
-            raise NotImplementedError("head_mask is always None on the ModCR path (modeling_transfomres.py:657)")
         n, s, _ = hidden_states.shape
         l = s + (0 if history_state is None else history_state.shape[1])
-        km, bits = split_additive_mask(attention_mask, n, s, l)
-        ctx, probs = self.hip_forward(hidden_states, km, bits, hist=history_state,
-                                      want_probs=self.output_attentions)
+        ctx, probs = self.hip_forward(hidden_states, hist=history_state, want_probs=self.output_attentions,
+                                      **split_additive_mask(attention_mask, n, s, l, head_mask))
         return (ctx, probs) if self.output_attentions else (ctx,)
 
 

@@ -24,16 +24,20 @@ class CaptionBertLayer(nn.Module):
         self.output = BertOutput(config)
 
     def hip_forward(self, x, key_mask=None, mask_bits=None, hist=None, chunk_id=None, want_probs=False,
-                    align_map=None, align_t=0, ws=None, out_rows=None, seq_len=None):
-        """out_rows = k (opt-in, the LAST layer of a frozen pass whose caller consumes only the first k rows of every sequence:
+                    align_map=None, align_t=0, ws=None, out_rows=None, seq_len=None, attn_bias=None, head_mask=None):
+        """attn_bias / head_mask: CaptionBertSelfAttention.hip_forward's general route (instead of key_mask / mask_bits).
+        out_rows = k (opt-in, the LAST layer of a frozen pass whose caller consumes only the first k rows of every sequence:
         config.modcr_last_layer_rows): attention runs over all rows (keys and values of every row are needed), the token-wise
         blocks behind it -- BertSelfOutput, BertIntermediate, BertOutput -- only over rows 0..k-1; returns [N,k,H].  seq_len: the
         sequence length when x is a packed view of several short sequences per row block."""
         ws = ws or Workspace()
         n, s, h = x.shape
-        need = mh.lib().modcr_qkv_attn_workspace(n, s, 0 if hist is None else hist.shape[1], h, mh.dt_of(x))
+        general = attn_bias is not None or head_mask is not None
+        need = (mh.lib().modcr_qkv_attn_bias_workspace if general else mh.lib().modcr_qkv_attn_workspace)(
+            n, s, 0 if hist is None else hist.shape[1], h, mh.dt_of(x))
         ctx, probs = self.attention.self.hip_forward(x, key_mask, mask_bits, hist, chunk_id, want_probs, align_map,
-                                                     align_t, ws.get("attn", need, x.device) if need else None)
+                                                     align_t, ws.get("attn", need, x.device) if need else None,
+                                                     attn_bias=attn_bias, head_mask=head_mask)
         if out_rows is not None:
             sl = seq_len or s
             if out_rows < sl:
@@ -62,9 +66,9 @@ class CaptionBertLayer(nn.Module):
     def forward(self, hidden_states, attention_mask, head_mask=None, history_state=None):
         n, s, _ = hidden_states.shape
         l = s + (0 if history_state is None else history_state.shape[1])
-        km, bits = split_additive_mask(attention_mask, n, s, l)
         want = self.attention.self.output_attentions
-        y, probs = self.hip_forward(hidden_states, km, bits, hist=history_state, want_probs=want)
+        y, probs = self.hip_forward(hidden_states, hist=history_state, want_probs=want,
+                                    **split_additive_mask(attention_mask, n, s, l, head_mask))
         return (y, probs) if want else (y,)
 
     def attention_cal(self, hidden_states, attention_mask, head_mask=None, history_state=None):
@@ -171,10 +175,35 @@ class CaptionBertEncoder(nn.Module):
     def forward(self, hidden_states, attention_mask, head_mask=None, encoder_history_states=None):
         n, s, _ = hidden_states.shape
         p = 0 if not encoder_history_states else encoder_history_states[0].shape[1]
-        km, bits = split_additive_mask(attention_mask, n, s, s + p)
-        if bits is not None:
-            raise NotImplementedError("global_enc always uses the broadcast padding mask (modeling_transfomres.py:628-641)")
-        return self.hip_forward(hidden_states, km, encoder_history_states)
+        if head_mask is not None and not (torch.is_tensor(head_mask) or len(head_mask) == len(self.layer)):
+            raise ValueError("head_mask: one entry per layer (%d), got %d" % (len(self.layer), len(head_mask)))
+        if head_mask is None or all(hm is None for hm in head_mask):
+            m = split_additive_mask(attention_mask, n, s, s + p)
+            if "key_mask" in m:                                 # the binary key mask: today's route, all its packing included
+                return self.hip_forward(hidden_states, m["key_mask"], encoder_history_states)
+            if "mask_bits" in m:
+                raise NotImplementedError("global_enc always uses the broadcast padding mask (modeling_transfomres.py:628-641)")
+            head_mask = [None] * len(self.layer)
+        # a non-binary additive mask and / or a head mask per layer (head_mask[i], as the reference indexes it): layer by layer on
+        # the general route, outputs laid out as hip_forward's
+        want = self.output_attentions and self.materialize
+        ws = Workspace()
+        x, all_hidden, all_att = hidden_states, (), ()
+        for i, layer in enumerate(self.layer):
+            if self.output_hidden_states:
+                all_hidden = all_hidden + (x,)
+            hist = None if encoder_history_states is None else encoder_history_states[i]
+            x, probs = layer.hip_forward(x, hist=hist, want_probs=want, ws=ws, attn_bias=attention_mask, head_mask=head_mask[i])
+            if self.output_attentions:
+                all_att = all_att + (probs,)
+        if self.output_hidden_states:
+            all_hidden = all_hidden + (x,)
+        outputs = (x,)
+        if self.output_hidden_states:
+            outputs = outputs + (all_hidden,)
+        if self.output_attentions:
+            outputs = outputs + (all_att,)
+        return outputs
 
 
 class ImgEmbedMixin(object):

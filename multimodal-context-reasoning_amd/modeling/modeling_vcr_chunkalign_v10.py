@@ -47,17 +47,14 @@ class CaptionBertSelfAttention(_GlobalSelfAttention):
 
     def forward(self, hidden_states, attention_mask, head_mask=None, history_state=None, do_chunk_cross=False,
                 offsets=None, gather_index=None):
-        if head_mask is not None:
-            raise NotImplementedError("head_mask is always None on the ModCR path")
         n, s, _ = hidden_states.shape
         l = s + (0 if history_state is None else history_state.shape[1])
-        km, bits = split_additive_mask(attention_mask, n, s, l)
         cid = None
         if do_chunk_cross:
             t = 1 + max(g.numel() for g in gather_index) + 1
             cid = pack_chunk_ids(gather_index, min(t, s), hidden_states.device)
-        ctx, probs = self.hip_forward(hidden_states, km, bits, hist=history_state, chunk_id=cid,
-                                      want_probs=self.output_attentions)
+        ctx, probs = self.hip_forward(hidden_states, hist=history_state, chunk_id=cid, want_probs=self.output_attentions,
+                                      **split_additive_mask(attention_mask, n, s, l, head_mask))
         return (ctx, probs) if self.output_attentions else (ctx,)
 
 
