@@ -139,6 +139,22 @@ int modcr_qkv_attn_bias_fwd(const void* x, const void* hist, const void* wqkv, c
                             void* ctx, float* probs, float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P,
                             int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
                             void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
+/* The route a forward call takes for the same scalars (no stream), decided by the same host functions: every modcr_qkv_attn_*_fwd
+ * entry above, or -- with MODCR_ATTN_HAS_BIAS -- modcr_qkv_attn_bias_fwd.  `present` says which optional arguments the call gives
+ * (MODCR_ATTN_HAS_*; key_mask is taken as given where dense_mask_bits is not), workspace_bytes / workspace_aligned16 describe its
+ * workspace (0 bytes = none).  Dereferences nothing and launches nothing; what depends on a pointer's value alone (alignment, bias
+ * strides) is taken as met.  Returns MODCR_OK or the error the call would return, with its message, and fills
+ * info[0] = kernel family (MODCR_ATTN_ROUTE_*), info[1..5] = what picks the instantiation -- TILE: NW, HPW, OCC, BKA, NSLOT of
+ * qkv_attn_bf16_kernel; TILE4: MODE, LP, NH of qkv_attn4_kernel; LONG_BF16 / LONG_F32: the streaming core's mode (0 = binary masks,
+ * 1 = bias / head mask, 2 = the same with dropout); 0 otherwise -- and info[6] = 1 when concat_prefix_kernel first copies
+ * [hist ; x] into the workspace.  The tuning build reports the route its MODCR_ATTN_* knobs select. */
+enum { MODCR_ATTN_HAS_BIAS = 1, MODCR_ATTN_HAS_DENSE_MASK = 2, MODCR_ATTN_HAS_CHUNK_ID = 4, MODCR_ATTN_HAS_PROBS = 8,
+       MODCR_ATTN_HAS_ALIGN_MAP = 16, MODCR_ATTN_HAS_LSE = 32, MODCR_ATTN_HAS_QKV_DUMP = 64 };
+enum { MODCR_ATTN_ROUTE_TILE = 1 /* the older tile kernel */, MODCR_ATTN_ROUTE_TILE4 = 2, MODCR_ATTN_ROUTE_LONG_BF16 = 3,
+       MODCR_ATTN_ROUTE_F32 = 4 /* exact core, P + S <= 256 */, MODCR_ATTN_ROUTE_LONG_F32 = 5 };
+int modcr_qkv_attn_route(int32_t present, int32_t chunk_t, int32_t align_t, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A,
+                         float attn_p, int32_t flags, int64_t workspace_bytes, int32_t workspace_aligned16, int32_t dtype,
+                         int32_t* info);
 /* Measurement hook: the NEXT bf16 modcr_qkv_attn_fwd / _dropout_fwd launch issued by the calling thread stamps the two
  * hipEvent_t (caller-created, timing enabled) at the start and the end of its kernel (hipExtLaunchKernel) -- the kernel's
  * own duration, as rocprofv3 --kernel-trace reports it, without the two extra barrier packets of a hipEventRecord pair.

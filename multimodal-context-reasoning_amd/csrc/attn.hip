@@ -74,6 +74,17 @@ struct AttnArgs {
 #endif
 };
 
+// attention-probability dropout as the host hands it to a kernel: the 64-bit key of (seed, offset), thr16 = round(p * 2^16) (0 = off)
+// and 1 / (1 - p); thr2 = the packed threshold of the bf16 tile kernels
+struct AttnDrop {
+    uint64_t key; uint32_t thr16; float keep;
+    uint32_t thr2() const { return thr16 ? attn_thrm1_2(thr16) : 0; }
+};
+inline AttnDrop attn_drop(float attn_p, uint64_t seed, uint64_t offset) {
+    if (!(attn_p > 0.f)) return {0, 0, 1.f};
+    return {seed + offset * 0x9E3779B97F4A7C15ull, attn_thr16(attn_p), 1.0f / (1.0f - attn_p)};
+}
+
 constexpr int VT_PAD = 8;  // bytes of padding per V^T row: stride/4 = 2*odd -> conflict-free b64 reads
 
 // HPW = heads per workgroup.  A 6-wave workgroup (S <= 192) lands 2,2,1,1 on the four SIMDs and a
@@ -1582,10 +1593,8 @@ extern "C" int modcr_tuning_qkv_attn_fold_fwd(const void* pre, const void* wfold
     p.x = (const bf16*)pre; p.hist = nullptr; p.wqkv = (const bf16*)wfold; p.bqkv = d; p.key_mask = key_mask; p.bits = nullptr; p.chunk_id = nullptr;
     p.ctx = (bf16*)ctx; p.probs = nullptr; p.align_map = nullptr; p.lse = nullptr; p.dump = nullptr;
     p.N = N; p.S = S; p.P = 0; p.H = H; p.A = A; p.chunk_t = 0; p.align_t = 0; p.hconc = 3; p.debug = modcr_knob_int("MODCR_ATTN_DEBUG", 0);
-    p.drop_thr2 = 0; p.drop_on = 0; p.drop_key = 0; p.drop_keep = 1.f; p.side_post_drop = 0;
-    if (attn_p > 0.f) {
-        p.drop_key = seed + offset * 0x9E3779B97F4A7C15ull; p.drop_thr2 = attn_thrm1_2(attn_thr16(attn_p)); p.drop_on = 1; p.drop_keep = 1.0f / (1.0f - attn_p);
-    }
+    const AttnDrop dr = attn_drop(attn_p, seed, offset);
+    p.drop_thr2 = dr.thr2(); p.drop_on = dr.thr16 != 0; p.drop_key = dr.key; p.drop_keep = dr.keep; p.side_post_drop = 0;
     p.row_stats = row_stats; p.cfold = c;
     return attn_p > 0.f ? launch_attn4d<1, 192, 1, 2, 0, 1>(p, (hipStream_t)stream) : launch_attn4d<1, 192, 0, 2, 0, 1>(p, (hipStream_t)stream);
 }
@@ -2187,353 +2196,357 @@ extern "C" int64_t modcr_qkv_attn_workspace(int32_t N, int32_t S, int32_t P, int
     return (int64_t)N * (S + P) * 3 * H * (int64_t)sizeof(float);
 }
 
-extern "C" int modcr_qkv_attn_lse_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
-                                      const float* key_mask, const uint32_t* dense_mask_bits,
-                                      const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
-                                      float* align_map, int32_t align_t, float* lse, void* qkv_dump, int32_t N, int32_t S, int32_t P,
-                                      int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset,
-                                      void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
-
-extern "C" int modcr_qkv_attn_opt_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
-                                      const float* key_mask, const uint32_t* dense_mask_bits,
-                                      const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
-                                      float* align_map, int32_t align_t, float* lse, void* qkv_dump, int32_t N, int32_t S, int32_t P,
-                                      int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
-                                      void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
-
-extern "C" int modcr_qkv_attn_dropout_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
-                                          const float* key_mask, const uint32_t* dense_mask_bits,
-                                          const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
-                                          float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P,
-                                          int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset,
-                                          void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
-    return modcr_qkv_attn_lse_fwd(x, hist, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, ctx, probs, align_map, align_t, nullptr, nullptr,
-                                  N, S, P, H, A, attn_p, seed, offset, workspace, workspace_bytes, dtype, stream);
-}
-
-extern "C" int modcr_qkv_attn_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
-                                  const float* key_mask, const uint32_t* dense_mask_bits,
-                                  const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
-                                  float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P,
-                                  int32_t H, int32_t A, void* workspace, int64_t workspace_bytes,
-                                  int32_t dtype, modcr_stream_t stream) {
-    return modcr_qkv_attn_dropout_fwd(x, hist, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, ctx, probs, align_map,
-                                      align_t, N, S, P, H, A, 0.f, 0, 0, workspace, workspace_bytes, dtype, stream);
-}
-
-// lse (or NULL): [N, A, S] fp32, log2 of every query row's sum of exp2(log2e x score) -- the row statistics the five-product
-// backward (modcr_qkv_attn_lse_bwd) rebuilds the probabilities from.  Written by the tile kernels only (bf16, 64 < S <= 256
-// on their shapes): any other route returns MODCR_ERR_UNSUPPORTED when lse is given.
-extern "C" int modcr_qkv_attn_lse_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
-                                      const float* key_mask, const uint32_t* dense_mask_bits,
-                                      const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
-                                      float* align_map, int32_t align_t, float* lse, void* qkv_dump, int32_t N, int32_t S, int32_t P,
-                                      int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset,
-                                      void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
-    return modcr_qkv_attn_opt_fwd(x, hist, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, ctx, probs, align_map, align_t, lse, qkv_dump,
-                                  N, S, P, H, A, attn_p, seed, offset, 0, workspace, workspace_bytes, dtype, stream);
-}
-
-// Shared by the two entries that run the streaming core of attn_long.hip: project [hist ; x] once into the workspace (x rows
-// [N*S][3H], then the prefix rows [N*P][3H]), chunk-mean the query columns, launch the core on `g` (arguments already validated).
-static int attn_long_project_and_launch(const void* x, const void* hist, const void* wqkv, const float* bqkv, const int32_t* chunk_id,
-                                        int32_t chunk_t, AttnLongArgs& g, void* workspace, int32_t dtype, modcr_stream_t stream) {
-    const int N = g.N, S = g.S, P = g.P, H = g.H;
-    const int64_t esz = dtype == MODCR_BF16 ? 2 : 4;
-    char* qx = (char*)workspace;
-    char* qh = qx + (int64_t)N * S * 3 * H * esz;
-    int rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, qx, 3 * H, N * S, 3 * H, H, MODCR_ACT_NONE, dtype, dtype, stream);
-    if (rc != MODCR_OK) return rc;
-    if (P > 0) {
-        rc = modcr_linear_fwd(hist, H, wqkv, H, bqkv, nullptr, 0, 0, qh, 3 * H, N * P, 3 * H, H, MODCR_ACT_NONE, dtype, dtype, stream);
-        if (rc != MODCR_OK) return rc;
-    }
-    if (chunk_id) {
-        rc = modcr_chunk_mean_q_fwd(qx, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, dtype, stream);
-        if (rc != MODCR_OK) return rc;
-    }
-    g.qx = qx; g.qh = P > 0 ? qh : nullptr;
-    hipEvent_t ev0 = g_time_start, ev1 = g_time_stop;     // the measurement hook times the core, not the projection
-    g_time_start = g_time_stop = nullptr;
-    return modcr_launch_attn_long(g, dtype, (hipStream_t)stream, ev0, ev1);
-}
-
-// 256 < P + S <= 512 (eval mode): project [hist ; x] once into the workspace (x rows [N*S][3H], then the prefix rows
-// [N*P][3H]), chunk-mean the query columns, then the streaming core of attn_long.hip.  No dropout, no row statistics,
-// no q|k|v dump: those exist for the backward, which stops at 256 keys.
-static int qkv_attn_long_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* key_mask,
-                             const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
-                             float* align_map, int32_t align_t, float* lse, void* qkv_dump, int32_t N, int32_t S, int32_t P, int32_t H,
-                             int32_t A, float attn_p, int32_t flags, void* workspace, int64_t workspace_bytes, int32_t dtype,
-                             modcr_stream_t stream) {
-    const int L = P + S;
-    MODCR_REQUIRE((flags & ~MODCR_ATTN_SIDE_POST_DROPOUT) == 0, "qkv_attn_fwd: unknown flags 0x%x", flags);
-    if (L > 512) {
-        modcr_set_error("qkv_attn_fwd: P+S=%d exceeds the 512-key limit of the attention forward", L);
-        return MODCR_ERR_UNSUPPORTED;
-    }
-    if (attn_p > 0.f) {
-        modcr_set_error("qkv_attn_fwd: attention-probability dropout (p=%g) is not implemented above 256 keys (P+S=%d)", attn_p, L);
-        return MODCR_ERR_UNSUPPORTED;
-    }
-    if (lse || qkv_dump) {
-        modcr_set_error("qkv_attn_fwd: row statistics (lse) / q|k|v dump are not produced above 256 keys (P+S=%d): no backward there", L);
-        return MODCR_ERR_UNSUPPORTED;
-    }
-    MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "qkv_attn_fwd: unknown dtype %d", dtype);
-    MODCR_REQUIRE(N > 0 && S > 0 && P >= 0 && A > 0, "qkv_attn_fwd: bad shape");
-    MODCR_REQUIRE(H == A * 64, "qkv_attn_fwd: head size must be 64 (H=%d, A=%d)", H, A);
-    MODCR_REQUIRE(P == 0 || hist, "qkv_attn_fwd: P=%d but hist is null", P);
-    MODCR_REQUIRE(key_mask || dense_mask_bits, "qkv_attn_fwd: need key_mask or dense_mask_bits");
-    MODCR_REQUIRE(!chunk_id || (chunk_t > 0 && chunk_t <= S), "qkv_attn_fwd: chunk_t=%d out of range", chunk_t);
-    MODCR_REQUIRE(!align_map || (align_t > 0 && align_t < S), "qkv_attn_fwd: align_t=%d out of range", align_t);
-    MODCR_REQUIRE(N <= 65535 && A <= 65535, "qkv_attn_fwd: grid of N=%d sequences x A=%d heads too large", N, A);
-    const int64_t need = modcr_qkv_attn_workspace(N, S, P, H, dtype);
-    MODCR_REQUIRE(workspace && workspace_bytes >= need && modcr_aligned16(workspace), "qkv_attn_fwd: workspace %lld < %lld bytes (or unaligned)",
-                  (long long)workspace_bytes, (long long)need);
-    if (dtype == MODCR_BF16)
-        MODCR_REQUIRE(modcr_aligned16(x) && modcr_aligned16(wqkv) && modcr_aligned16(ctx) && (P == 0 || modcr_aligned16(hist)),
-                      "qkv_attn_fwd(bf16): 16-byte alignment");
-    AttnLongArgs g = {};
-    g.key_mask = key_mask; g.bits = dense_mask_bits;
-    g.ctx = ctx; g.probs = probs; g.align_map = align_map;
-    g.N = N; g.S = S; g.P = P; g.H = H; g.A = A; g.align_t = align_t;
-    return attn_long_project_and_launch(x, hist, wqkv, bqkv, chunk_id, chunk_t, g, workspace, dtype, stream);
-}
-
 extern "C" int64_t modcr_qkv_attn_bias_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
     return (int64_t)N * (P + S) * 3 * H * (dtype == MODCR_BF16 ? 2 : 4);     // q | k | v rows of [x ; hist] at every key count
 }
 
-// Attention forward with an additive fp32 bias (any float mask, broadcastable over sequence / head / query) and / or a per-head
-// multiplier, P + S <= 512: the projection sequence of qkv_attn_long_fwd, then the bias variant of the streaming core.
-extern "C" int modcr_qkv_attn_bias_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
-                                       const float* bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
-                                       const float* head_mask, int64_t head_mask_stride_n,
-                                       const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
-                                       float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P,
-                                       int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
-                                       void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
-    MODCR_REQUIRE(x && wqkv && bqkv && ctx, "qkv_attn_bias_fwd: null pointer");
-    MODCR_REQUIRE(bias || head_mask, "qkv_attn_bias_fwd: neither bias nor head_mask (that call belongs to modcr_qkv_attn_opt_fwd)");
-    MODCR_REQUIRE((flags & ~MODCR_ATTN_SIDE_POST_DROPOUT) == 0, "qkv_attn_bias_fwd: unknown flags 0x%x", flags);
-    MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "qkv_attn_bias_fwd: unknown dtype %d", dtype);
-    MODCR_REQUIRE(N > 0 && S > 0 && P >= 0 && A > 0, "qkv_attn_bias_fwd: bad shape");
-    MODCR_REQUIRE(H == A * 64, "qkv_attn_bias_fwd: head size must be 64 (H=%d, A=%d)", H, A);
-    const int L = P + S;
-    if (L > 512) {
-        modcr_set_error("qkv_attn_bias_fwd: P+S=%d exceeds the 512-key limit of the attention forward", L);
-        return MODCR_ERR_UNSUPPORTED;
-    }
-    MODCR_REQUIRE(attn_p >= 0.f && attn_p < 1.f, "qkv_attn_bias_fwd: attention dropout p=%g out of [0, 1)", attn_p);
-    if (attn_p > 0.f && L > 256) {
-        modcr_set_error("qkv_attn_bias_fwd: attention-probability dropout (p=%g) is not implemented above 256 keys (P+S=%d)", attn_p, L);
-        return MODCR_ERR_UNSUPPORTED;
-    }
-    MODCR_REQUIRE(P == 0 || hist, "qkv_attn_bias_fwd: P=%d but hist is null", P);
-    MODCR_REQUIRE(bias_stride_n >= 0 && bias_stride_a >= 0 && bias_stride_q >= 0 && head_mask_stride_n >= 0,
-                  "qkv_attn_bias_fwd: negative stride");
-    MODCR_REQUIRE(!chunk_id || (chunk_t > 0 && chunk_t <= S), "qkv_attn_bias_fwd: chunk_t=%d out of range", chunk_t);
-    MODCR_REQUIRE(!align_map || (align_t > 0 && align_t < S), "qkv_attn_bias_fwd: align_t=%d out of range", align_t);
-    MODCR_REQUIRE(N <= 65535 && A <= 65535, "qkv_attn_bias_fwd: grid of N=%d sequences x A=%d heads too large", N, A);
-    const int64_t need = modcr_qkv_attn_bias_workspace(N, S, P, H, dtype);
-    MODCR_REQUIRE(workspace && workspace_bytes >= need && modcr_aligned16(workspace),
-                  "qkv_attn_bias_fwd: workspace %lld < %lld bytes (or unaligned)", (long long)workspace_bytes, (long long)need);
-    MODCR_REQUIRE(((uintptr_t)bias & 3) == 0 && ((uintptr_t)head_mask & 3) == 0, "qkv_attn_bias_fwd: bias / head_mask not 4-byte aligned");
-    if (dtype == MODCR_BF16)
-        MODCR_REQUIRE(modcr_aligned16(x) && modcr_aligned16(wqkv) && modcr_aligned16(ctx) && (P == 0 || modcr_aligned16(hist)),
-                      "qkv_attn_bias_fwd(bf16): 16-byte alignment");
-    AttnLongArgs g = {};
-    g.ctx = ctx; g.probs = probs; g.align_map = align_map;
-    g.N = N; g.S = S; g.P = P; g.H = H; g.A = A; g.align_t = align_t;
-    g.bias = bias; g.bias_sn = bias_stride_n; g.bias_sa = bias_stride_a; g.bias_sq = bias_stride_q;
-    g.head_mask = head_mask; g.head_mask_sn = head_mask_stride_n;
-    g.drop_keep = 1.f;
-    if (attn_p > 0.f) {                                     // the mask of every other route for the same (seed, offset)
-        g.drop_thr16 = attn_thr16(attn_p); g.drop_key = seed + offset * 0x9E3779B97F4A7C15ull;
-        g.drop_keep = 1.0f / (1.0f - attn_p); g.side_post_drop = (flags & MODCR_ATTN_SIDE_POST_DROPOUT) ? 1 : 0;
-    }
-    return attn_long_project_and_launch(x, hist, wqkv, bqkv, chunk_id, chunk_t, g, workspace, dtype, stream);
+namespace {
+
+// What validation and routing look at: the scalars of a forward call and which optional arguments it gives (MODCR_ATTN_HAS_*).
+// who = the entry's name in the messages; ws_bytes = 0 without a workspace.
+struct AttnCall {
+    const char* who;
+    int32_t present, chunk_t, align_t, N, S, P, H, A; float attn_p; int32_t flags; int64_t ws_bytes; bool ws_aligned16; int32_t dtype;
+};
+
+int attn_present(const void* dense_mask_bits, const void* chunk_id, const void* probs, const void* align_map, const void* lse, const void* qkv_dump) {
+    return (dense_mask_bits ? MODCR_ATTN_HAS_DENSE_MASK : 0) | (chunk_id ? MODCR_ATTN_HAS_CHUNK_ID : 0) | (probs ? MODCR_ATTN_HAS_PROBS : 0) |
+           (align_map ? MODCR_ATTN_HAS_ALIGN_MAP : 0) | (lse ? MODCR_ATTN_HAS_LSE : 0) | (qkv_dump ? MODCR_ATTN_HAS_QKV_DUMP : 0);
 }
 
-// flags: MODCR_ATTN_SIDE_POST_DROPOUT = the probabilities / align map leave AFTER the dropout, P o m / (1 - p), as the reference's
-// modules return them (modeling_bert.py:69-74, v10:94-106); tile kernels only (bf16, 64 < P + S <= 256).  0 = the un-dropped ones.
-extern "C" int modcr_qkv_attn_opt_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
-                                      const float* key_mask, const uint32_t* dense_mask_bits,
-                                      const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
-                                      float* align_map, int32_t align_t, float* lse, void* qkv_dump, int32_t N, int32_t S, int32_t P,
-                                      int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
-                                      void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
-    MODCR_REQUIRE(x && wqkv && bqkv && ctx, "qkv_attn_fwd: null pointer");
-    if (S > 0 && P >= 0 && P + S > 256)
-        return qkv_attn_long_fwd(x, hist, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, ctx, probs, align_map, align_t, lse, qkv_dump,
-                                 N, S, P, H, A, attn_p, flags, workspace, workspace_bytes, dtype, stream);
-    MODCR_REQUIRE((flags & ~MODCR_ATTN_SIDE_POST_DROPOUT) == 0, "qkv_attn_fwd: unknown flags 0x%x", flags);
-    MODCR_REQUIRE(!qkv_dump || (lse && P == 0 && S > 64 && S <= 192 && modcr_aligned16(qkv_dump)),
-                  "qkv_attn_fwd: the q|k|v dump comes with lse, without prefix rows, for 64 < S <= 192 (S=%d P=%d)", S, P);
-    MODCR_REQUIRE(attn_p >= 0.f && attn_p < 1.f, "qkv_attn_fwd: attention dropout p=%g out of [0, 1)", attn_p);
-    MODCR_REQUIRE(N > 0 && S > 0 && P >= 0 && A > 0, "qkv_attn_fwd: bad shape");
-    MODCR_REQUIRE(H == A * 64, "qkv_attn_fwd: head size must be 64 (H=%d, A=%d)", H, A);
-    MODCR_REQUIRE(P + S <= 256, "qkv_attn_fwd: P+S=%d exceeds 256 keys", P + S);
-    MODCR_REQUIRE(P == 0 || hist, "qkv_attn_fwd: P=%d but hist is null", P);
-    MODCR_REQUIRE(key_mask || dense_mask_bits, "qkv_attn_fwd: need key_mask or dense_mask_bits");
-    MODCR_REQUIRE(!chunk_id || (chunk_t > 0 && chunk_t <= S), "qkv_attn_fwd: chunk_t=%d out of range", chunk_t);
-    MODCR_REQUIRE(!align_map || (align_t > 0 && align_t < S), "qkv_attn_fwd: align_t=%d out of range", align_t);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MODCR_BF16) {
-        MODCR_REQUIRE(modcr_aligned16(x) && modcr_aligned16(wqkv) && modcr_aligned16(ctx) &&
-                          (P == 0 || modcr_aligned16(hist)),
-                      "qkv_attn_fwd(bf16): 16-byte alignment");
-        AttnArgs p;
-        p.x = (const bf16*)x; p.hist = (const bf16*)hist; p.wqkv = (const bf16*)wqkv; p.bqkv = bqkv;
-        p.key_mask = key_mask; p.bits = dense_mask_bits; p.chunk_id = chunk_id;
-        p.ctx = (bf16*)ctx; p.probs = probs; p.align_map = align_map; p.lse = lse; p.dump = (bf16*)qkv_dump;
-        p.N = N; p.S = S; p.P = P; p.H = H; p.A = A; p.chunk_t = chunk_t; p.align_t = align_t;
-        p.drop_thr2 = 0; p.drop_on = 0; p.drop_key = 0; p.drop_keep = 1.f;
-        p.side_post_drop = (attn_p > 0.f && (flags & MODCR_ATTN_SIDE_POST_DROPOUT)) ? 1 : 0;
-        if (attn_p > 0.f) {
-            // the reference returns the probabilities AFTER the dropout (modeling_bert.py:74): a probabilities output comes with
-            // MODCR_ATTN_SIDE_POST_DROPOUT (the generic tile variant applies the mask to it); the un-dropped ones are not offered
-            if (probs && !p.side_post_drop) {
-                modcr_set_error("qkv_attn_fwd: a probabilities output under attention-probability dropout needs MODCR_ATTN_SIDE_POST_DROPOUT");
-                return MODCR_ERR_UNSUPPORTED;
-            }
-            p.drop_key = seed + offset * 0x9E3779B97F4A7C15ull;
-            p.drop_thr2 = attn_thrm1_2(attn_thr16(attn_p)); p.drop_on = 1;
-            p.drop_keep = 1.0f / (1.0f - attn_p);
-        }
-        // knobs below: tuning build only (common.h); the product library takes the defaults
-        p.debug = modcr_knob_int("MODCR_ATTN_DEBUG", 0);
-#ifdef MODCR_TUNING
-        if (getenv("MODCR_ATTN_TRACE_PTR")) p.trace = reinterpret_cast<unsigned long long*>(strtoull(getenv("MODCR_ATTN_TRACE_PTR"), nullptr, 0));
-#endif
-        p.hconc = modcr_knob_int("MODCR_ATTN_HCONC", 3);     // tile kernels: 3 head pairs at a time per XCD (measured 166 vs 168 us; FETCH_SIZE: profiles/)
-        const int L = P + S;
-        const int one_head = modcr_knob_set("MODCR_ATTN_HPW1");
-        [[maybe_unused]] const int ring64 = modcr_knob_set("MODCR_ATTN_RING64");          // 64-wide K-tiles, 2 slots
-        const bool pair = (A % 2 == 0) && !one_head;
-        // prefix rows (history_state) on the tile kernels: K and V over [prefix ; x] (modeling_bert.py:36-44), queries from x
-        // only.  The caller's workspace receives the concatenated rows (one copy pass); key-mask / dense-mask calls without
-        // side outputs take this route, everything else the older kernel.
-        bool prefix_tiles = false;
-        if (P > 0 && L > 64 && L <= 256 && (pair || L > 192) && !probs && !align_map && !chunk_id && (H % 128) == 0 && H >= 256 &&
-            workspace && workspace_bytes >= modcr_qkv_attn_workspace(N, S, P, H, dtype) && modcr_aligned16(workspace) &&
-            (int64_t)3 * H * H * 2 < (1ll << 31) && !modcr_knob_set("MODCR_ATTN_NO_PREFIX_TILES") &&
-            !modcr_knob_set("MODCR_ATTN_NO_V4") && !modcr_knob_set("MODCR_ATTN_NO_V4S")) {
-            const int64_t pieces = (int64_t)N * L * (H >> 3);
-            const int grid = (int)((pieces + 255) / 256 < 16384 ? (pieces + 255) / 256 : 16384);
-            hipLaunchKernelGGL(concat_prefix_kernel, dim3(grid), dim3(256), 0, st, p.hist, p.x, (bf16*)workspace, N, P, S, H);
-            int rc = modcr_check_launch("concat_prefix");
-            if (rc != MODCR_OK) return rc;
-            p.x = (const bf16*)workspace;
-            prefix_tiles = true;
-        }
-        // (row statistics come from the tile kernels only)
-#define MODCR_NO_LSE_HERE() do { if (lse) { modcr_set_error("qkv_attn_fwd: no row statistics (lse) on this route (S=%d P=%d A=%d H=%d)", S, P, A, H); return MODCR_ERR_UNSUPPORTED; } \
-                                 if (p.side_post_drop && (probs || align_map)) { modcr_set_error("qkv_attn_fwd: post-dropout side outputs on the tile kernels only (S=%d P=%d A=%d H=%d)", S, P, A, H); return MODCR_ERR_UNSUPPORTED; } } while (0)
-        if (L <= 64) MODCR_NO_LSE_HERE();
-        if (L <= 64) return pair ? launch_attn<2, 2, 2, 64, 2>(p, st) : launch_attn<2, 1, 2, 64, 2>(p, st);
-        if (L <= 128 && L > 64 && (A % 2 == 0) && !one_head && (P == 0 || prefix_tiles) && (H % 128) == 0 && H >= 256 && (int64_t)3 * H * H * 2 < (1ll << 31)) {
-            // 64 < S <= 128: the same kernel on a 128-token tile (A half = 64 rows = one LDS-DMA piece per wave)
-            const int no_v4s = modcr_knob_set("MODCR_ATTN_NO_V4S");
-            if (!no_v4s) {
-                if (!probs && align_map && chunk_id && dense_mask_bits) return launch_attn4<3, 128>(p, st);
-                if (probs || align_map || chunk_id) return launch_attn4<0, 128>(p, st);
-                return dense_mask_bits ? launch_attn4<2, 128>(p, st) : launch_attn4<1, 128>(p, st);
-            }
-        }
-        if (L <= 128) {
-            MODCR_NO_LSE_HERE();
-#ifdef MODCR_TUNING             // (A/B variants of the older kernel: instantiated in the tuning library only)
-            const int ring32 = modcr_knob_int("MODCR_ATTN_RING32", 0);
-            if (pair && ring32 == 1) return launch_attn<4, 2, 2, 32, 4>(p, st);
-            if (pair && ring32 == 2) return launch_attn<4, 2, 2, 32, 3>(p, st);
-#endif
-            return pair ? launch_attn<4, 2, 2, 64, 2>(p, st) : launch_attn<4, 1, 2, 64, 2>(p, st);
-        }
-        if (L <= 192) {
-            const int no_v4 = modcr_knob_set("MODCR_ATTN_NO_V4");
-            if (pair && !no_v4 && L > 128 && (P == 0 || prefix_tiles) && (H % 128) == 0 && H >= 256 && (int64_t)3 * H * H * 2 < (1ll << 31)) {
-                if (!probs && align_map && chunk_id && dense_mask_bits) return launch_attn4<3, 192>(p, st);
-                if (probs || align_map || chunk_id) return launch_attn4<0, 192>(p, st);
-                return dense_mask_bits ? launch_attn4<2, 192>(p, st) : launch_attn4<1, 192>(p, st);
-            }
-            MODCR_NO_LSE_HERE();
-            if (!pair) {
-#ifdef MODCR_TUNING
-                const int v = modcr_knob_int("MODCR_ATTN_HPW1", 0);
-                if (v == 2) return launch_attn<6, 1, 3, 32, 3>(p, st);   // 2 workgroups per CU
-                if (v == 3) return launch_attn<6, 1, 3, 32, 2>(p, st);
-#endif
-                return launch_attn<6, 1, 2, 64, 2>(p, st);
-            }
-#ifdef MODCR_TUNING
-            if (ring64) return launch_attn<6, 2, 3, 64, 2>(p, st);
-#endif
-            return launch_attn<6, 2, 3, 32, 4>(p, st);
-        }
-        // 192 < L <= 256 (the VCR / Oscar-large shape class S = 230): the 256-token tile, one head per workgroup; key-mask and
-        // dense-mask calls without side outputs, and the phase-3 call (dense mask + chunk-mean queries + align map) when its
-        // [T][R] fp32 tile fits the one V^T image (VCR: 194 x 36); everything else: the older kernel
-        if ((P == 0 || prefix_tiles) && !probs && (H % 128) == 0 && H >= 256 && (int64_t)3 * H * H * 2 < (1ll << 31) &&
-            !modcr_knob_set("MODCR_ATTN_NO_V4L")) {
-            if (!align_map && !chunk_id) return dense_mask_bits ? launch_attn4<2, 256, 1>(p, st) : launch_attn4<1, 256, 1>(p, st);
-            if (align_map && chunk_id && dense_mask_bits && P == 0 &&
-                (int64_t)align_t * (S - align_t) * 4 <= (int64_t)64 * A4T<256, 1>::VT_STRIDE)
-                return launch_attn4<3, 256, 1>(p, st);
-        }
-        // a probabilities output, or chunk-mean queries / an align map in any other combination (incl. a [T][R] tile larger than the
-        // V^T image): the generic variant of the same tile (exact pass; its align tile lies over K | V^T)
-        if (P == 0 && (H % 128) == 0 && H >= 256 && (int64_t)3 * H * H * 2 < (1ll << 31) && !modcr_knob_set("MODCR_ATTN_NO_V4L"))
-            return launch_attn4<0, 256, 1>(p, st);
-        MODCR_NO_LSE_HERE();
-        return launch_attn<8, 1, 2, 64, 2>(p, st);
+// The argument checks every forward entry shares.  given = x, wqkv, bqkv and ctx are there; aligned16 = x, wqkv, ctx and hist (P > 0)
+// lie on 16 bytes (looked at in bf16 only).
+int attn_fwd_setup(const AttnCall& c, bool given, bool has_hist, bool aligned16) {
+    const char* who = c.who;
+    const bool bias = c.present & MODCR_ATTN_HAS_BIAS, chunk = c.present & MODCR_ATTN_HAS_CHUNK_ID, align = c.present & MODCR_ATTN_HAS_ALIGN_MAP;
+    MODCR_REQUIRE(given, "%s: null pointer", who);
+    MODCR_REQUIRE((c.flags & ~MODCR_ATTN_SIDE_POST_DROPOUT) == 0, "%s: unknown flags 0x%x", who, c.flags);
+    MODCR_REQUIRE(c.dtype == MODCR_BF16 || c.dtype == MODCR_F32, "%s: unknown dtype %d", who, c.dtype);
+    MODCR_REQUIRE(c.N > 0 && c.S > 0 && c.P >= 0 && c.A > 0, "%s: bad shape", who);
+    MODCR_REQUIRE(c.H == c.A * 64, "%s: head size must be 64 (H=%d, A=%d)", who, c.H, c.A);
+    const int L = c.P + c.S;
+    if (L > 512 || (c.attn_p > 0.f && L > 256)) {
+        if (L > 512) modcr_set_error("%s: P+S=%d exceeds the 512-key limit of the attention forward", who, L);
+        else modcr_set_error("%s: attention-probability dropout (p=%g) is not implemented above 256 keys (P+S=%d)", who, c.attn_p, L);
+        return MODCR_ERR_UNSUPPORTED;
     }
-    MODCR_REQUIRE(!lse, "qkv_attn_fwd(f32): row statistics (lse) are written on the bf16 path only");
-    MODCR_REQUIRE(dtype == MODCR_F32, "qkv_attn_fwd: unknown dtype %d", dtype);
-    MODCR_REQUIRE(attn_p == 0.f || !probs || (flags & MODCR_ATTN_SIDE_POST_DROPOUT),
-                  "qkv_attn_fwd(f32): a probabilities output under attention-probability dropout needs MODCR_ATTN_SIDE_POST_DROPOUT");
-    const int64_t need = modcr_qkv_attn_workspace(N, S, P, H, dtype);
-    MODCR_REQUIRE(workspace && workspace_bytes >= need, "qkv_attn_fwd(f32): workspace %lld < %lld bytes",
-                  (long long)workspace_bytes, (long long)need);
-    float* qkv_x = (float*)workspace;
-    float* qkv_h = qkv_x + (int64_t)N * S * 3 * H;
-    int rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, qkv_x, 3 * H, N * S, 3 * H, H,
-                              MODCR_ACT_NONE, MODCR_F32, MODCR_F32, stream);
+    // (above 256 keys the binary-mask entries have only ever asked whether p > 0: anything else is "no dropout" there)
+    MODCR_REQUIRE((L > 256 && !bias) || (c.attn_p >= 0.f && c.attn_p < 1.f), "%s: attention dropout p=%g out of [0, 1)", who, c.attn_p);
+    MODCR_REQUIRE(c.P == 0 || has_hist, "%s: P=%d but hist is null", who, c.P);
+    MODCR_REQUIRE(!chunk || (c.chunk_t > 0 && c.chunk_t <= c.S), "%s: chunk_t=%d out of range", who, c.chunk_t);
+    MODCR_REQUIRE(!align || (c.align_t > 0 && c.align_t < c.S), "%s: align_t=%d out of range", who, c.align_t);
+    MODCR_REQUIRE(!(bias || L > 256) || (c.N <= 65535 && c.A <= 65535), "%s: grid of N=%d sequences x A=%d heads too large", who, c.N, c.A);   // (the streaming core's)
+    MODCR_REQUIRE(c.dtype != MODCR_BF16 || aligned16, "%s(bf16): 16-byte alignment", who);
+    return MODCR_OK;
+}
+
+// modcr_qkv_attn_opt_fwd's own checks, after the shared ones
+int attn_opt_checks(const AttnCall& c, bool has_mask, bool dump_aligned16) {
+    MODCR_REQUIRE(has_mask, "%s: need key_mask or dense_mask_bits", c.who);
+    MODCR_REQUIRE(!(c.present & MODCR_ATTN_HAS_QKV_DUMP) || c.P + c.S > 256 ||
+                      ((c.present & MODCR_ATTN_HAS_LSE) && c.P == 0 && c.S > 64 && c.S <= 192 && dump_aligned16),
+                  "%s: the q|k|v dump comes with lse, without prefix rows, for 64 < S <= 192 (S=%d P=%d)", c.who, c.S, c.P);
+    return MODCR_OK;
+}
+
+// modcr_qkv_attn_bias_fwd's own checks (b: its bias / head_mask arguments)
+int attn_bias_checks(const AttnLongArgs& b) {
+    MODCR_REQUIRE(b.bias || b.head_mask, "qkv_attn_bias_fwd: neither bias nor head_mask (that call belongs to modcr_qkv_attn_opt_fwd)");
+    MODCR_REQUIRE(b.bias_sn >= 0 && b.bias_sa >= 0 && b.bias_sq >= 0 && b.head_mask_sn >= 0, "qkv_attn_bias_fwd: negative stride");
+    MODCR_REQUIRE(((uintptr_t)b.bias & 3) == 0 && ((uintptr_t)b.head_mask & 3) == 0, "qkv_attn_bias_fwd: bias / head_mask not 4-byte aligned");
+    return MODCR_OK;
+}
+
+// The route of a validated forward call (every forward entry and modcr_qkv_attn_route).  The one place the choice is made:
+// family = MODCR_ATTN_ROUTE_*, v = what picks the instantiation (modcr_hip.h: info[1..5]), concat = concat_prefix_kernel runs first,
+// rc = MODCR_OK or why no route serves the call (the message is set).  DROP / DUMPV / SIDE of the launchers follow from the pointers
+// and stay with them.  The MODCR_ATTN_* knobs read here exist in the tuning build only (common.h).
+struct AttnRoute { int rc, family, v[5], concat; };
+AttnRoute attn_fwd_route(const AttnCall& c) {
+    AttnRoute r = {MODCR_OK, 0, {0, 0, 0, 0, 0}, 0};
+    const int N = c.N, S = c.S, P = c.P, H = c.H, A = c.A, L = P + S;
+    const bool bf = c.dtype == MODCR_BF16, bias = c.present & MODCR_ATTN_HAS_BIAS, dense = c.present & MODCR_ATTN_HAS_DENSE_MASK,
+               chunk = c.present & MODCR_ATTN_HAS_CHUNK_ID, probs = c.present & MODCR_ATTN_HAS_PROBS,
+               align = c.present & MODCR_ATTN_HAS_ALIGN_MAP, lse = c.present & MODCR_ATTN_HAS_LSE;
+    const bool side_post_drop = c.attn_p > 0.f && (c.flags & MODCR_ATTN_SIDE_POST_DROPOUT);
+    auto refuse = [&r](int rc, const char* fmt, auto... a) { modcr_set_error(fmt, a...); r.rc = rc; return r; };
+    auto tile = [&r](int nw, int hpw, int occ, int bka, int nslot) { r = {MODCR_OK, MODCR_ATTN_ROUTE_TILE, {nw, hpw, occ, bka, nslot}, 0}; };
+    // (prefix rows reach qkv_attn4_kernel through the concatenated copy only)
+    auto tile4 = [&r, P](int mode, int lp, int nh) { r = {MODCR_OK, MODCR_ATTN_ROUTE_TILE4, {mode, lp, nh, 0, 0}, P > 0}; };
+    // the streaming core of attn_long.hip over projected rows: above 256 keys (eval mode: no dropout, no row statistics, no q|k|v
+    // dump -- those exist for the backward, which stops at 256 keys), and every call of modcr_qkv_attn_bias_fwd
+    if (bias || L > 256) {
+        if (c.present & (MODCR_ATTN_HAS_LSE | MODCR_ATTN_HAS_QKV_DUMP))
+            return refuse(MODCR_ERR_UNSUPPORTED, "%s: row statistics (lse) / q|k|v dump are not produced above 256 keys (P+S=%d): no backward there", c.who, L);
+        const int64_t need = bias ? modcr_qkv_attn_bias_workspace(N, S, P, H, c.dtype) : modcr_qkv_attn_workspace(N, S, P, H, c.dtype);
+        if (c.ws_bytes < need || !c.ws_aligned16)
+            return refuse(MODCR_ERR_INVALID, "%s: workspace %lld < %lld bytes (or unaligned)", c.who, (long long)c.ws_bytes, (long long)need);
+        r.family = bf ? MODCR_ATTN_ROUTE_LONG_BF16 : MODCR_ATTN_ROUTE_LONG_F32;
+        // (reported only: modcr_launch_attn_long, attn_long.hip, derives the same mode from the arguments attn_fwd fills -- bias or
+        // head_mask set, drop_thr16 = attn_thr16(p) >= 1 exactly when p > 0; tools/attn_route_trace.py holds the two together)
+        r.v[0] = !bias ? 0 : c.attn_p > 0.f ? 2 : 1;
+        return r;
+    }
+    // the reference returns the probabilities AFTER the dropout (modeling_bert.py:74): a probabilities output comes with
+    // MODCR_ATTN_SIDE_POST_DROPOUT (the generic tile variant applies the mask to it); the un-dropped ones are not offered
+    if (c.attn_p > 0.f && probs && !side_post_drop)
+        return refuse(bf ? MODCR_ERR_UNSUPPORTED : MODCR_ERR_INVALID,
+                      "%s%s: a probabilities output under attention-probability dropout needs MODCR_ATTN_SIDE_POST_DROPOUT", c.who, bf ? "" : "(f32)");
+    if (!bf) {              // exact-parity core over projected rows
+        if (lse) return refuse(MODCR_ERR_INVALID, "%s(f32): row statistics (lse) are written on the bf16 path only", c.who);
+        const int64_t need = modcr_qkv_attn_workspace(N, S, P, H, c.dtype);
+        if (c.ws_bytes < need) return refuse(MODCR_ERR_INVALID, "%s(f32): workspace %lld < %lld bytes", c.who, (long long)c.ws_bytes, (long long)need);
+        r.family = MODCR_ATTN_ROUTE_F32;
+        return r;
+    }
+    const int hpw1 = modcr_knob_int("MODCR_ATTN_HPW1", 0);              // (set: one head per workgroup; 2, 3: A/B variants at 192 rows)
+    const bool pair = (A % 2 == 0) && !modcr_knob_set("MODCR_ATTN_HPW1");
+    const bool tile4_shape = (H % 128) == 0 && H >= 256 && (int64_t)3 * H * H * 2 < (1ll << 31);     // what qkv_attn4_kernel takes
+    // prefix rows (history_state) on the tile kernels: K and V over [prefix ; x] (modeling_bert.py:36-44), queries from x only.
+    // The caller's workspace receives the concatenated rows (one copy pass); key-mask / dense-mask calls without side outputs
+    // take this route, everything else the older kernel.
+    const bool prefix_tiles = P > 0 && L > 64 && (pair || L > 192) && !probs && !align && !chunk && tile4_shape &&
+                              c.ws_bytes >= modcr_qkv_attn_workspace(N, S, P, H, c.dtype) && c.ws_aligned16 &&
+                              !modcr_knob_set("MODCR_ATTN_NO_PREFIX_TILES") && !modcr_knob_set("MODCR_ATTN_NO_V4") &&
+                              !modcr_knob_set("MODCR_ATTN_NO_V4S");
+    const bool rows4 = tile4_shape && (P == 0 || prefix_tiles);
+    // MODE of qkv_attn4_kernel: 3 = the phase-3 call (dense mask + chunk-mean queries + align map), 0 = the generic variant (a
+    // probabilities output, chunk-mean queries / an align map in any other combination), 2 / 1 = dense mask / key mask alone
+    const int mode4 = (!probs && align && chunk && dense) ? 3 : (probs || align || chunk) ? 0 : dense ? 2 : 1;
+    if (L <= 64) {
+        tile(2, pair ? 2 : 1, 2, 64, 2);
+    } else if (L <= 128) {  // the 128-token tile (A half = 64 rows = one LDS-DMA piece per wave)
+        const int ring32 = modcr_knob_int("MODCR_ATTN_RING32", 0);
+        if (pair && rows4 && !modcr_knob_set("MODCR_ATTN_NO_V4S")) tile4(mode4, 128, 2);
+        else if (pair && (ring32 == 1 || ring32 == 2)) tile(4, 2, 2, 32, ring32 == 1 ? 4 : 3);
+        else tile(4, pair ? 2 : 1, 2, 64, 2);
+    } else if (L <= 192) {
+        if (pair && rows4 && !modcr_knob_set("MODCR_ATTN_NO_V4")) tile4(mode4, 192, 2);
+        else if (!pair && hpw1 == 2) tile(6, 1, 3, 32, 3);        // 2 workgroups per CU
+        else if (!pair && hpw1 == 3) tile(6, 1, 3, 32, 2);
+        else if (!pair) tile(6, 1, 2, 64, 2);
+        else if (modcr_knob_set("MODCR_ATTN_RING64")) tile(6, 2, 3, 64, 2);          // 64-wide K-tiles, 2 slots
+        else tile(6, 2, 3, 32, 4);
+    } else {
+        // 192 < L <= 256 (the VCR / Oscar-large shape class S = 230): the 256-token tile, one head per workgroup; key-mask and
+        // dense-mask calls without side outputs, and the phase-3 call when its [T][R] fp32 tile fits the one V^T image (VCR:
+        // 194 x 36); a probabilities output, or chunk-mean queries / an align map in any other combination (incl. a larger [T][R]
+        // tile): the generic variant of the same tile (exact pass; its align tile lies over K | V^T); prefix rows with any of
+        // those: the older kernel
+        const bool v4l = !modcr_knob_set("MODCR_ATTN_NO_V4L");
+        if (v4l && rows4 && (mode4 == 1 || mode4 == 2)) tile4(mode4, 256, 1);
+        else if (v4l && rows4 && P == 0 && mode4 == 3 && (int64_t)c.align_t * (S - c.align_t) * 4 <= (int64_t)64 * A4T<256, 1>::VT_STRIDE) tile4(3, 256, 1);
+        else if (v4l && rows4 && P == 0) tile4(0, 256, 1);
+        else tile(8, 1, 2, 64, 2);
+    }
+    // row statistics and post-dropout side outputs come from qkv_attn4_kernel only
+    if (r.family == MODCR_ATTN_ROUTE_TILE && lse)
+        return refuse(MODCR_ERR_UNSUPPORTED, "%s: no row statistics (lse) on this route (S=%d P=%d A=%d H=%d)", c.who, S, P, A, H);
+    if (r.family == MODCR_ATTN_ROUTE_TILE && side_post_drop && (probs || align))
+        return refuse(MODCR_ERR_UNSUPPORTED, "%s: post-dropout side outputs on the tile kernels only (S=%d P=%d A=%d H=%d)", c.who, S, P, A, H);
+    return r;
+}
+
+constexpr int tile_id(int nw, int hpw, int occ, int bka, int nslot) { return (((nw * 4 + hpw) * 4 + occ) * 128 + bka) * 8 + nslot; }
+int launch_route_tile(const AttnRoute& r, const AttnArgs& p, hipStream_t st) {
+    switch (tile_id(r.v[0], r.v[1], r.v[2], r.v[3], r.v[4])) {
+        case tile_id(2, 2, 2, 64, 2): return launch_attn<2, 2, 2, 64, 2>(p, st);
+        case tile_id(2, 1, 2, 64, 2): return launch_attn<2, 1, 2, 64, 2>(p, st);
+        case tile_id(4, 2, 2, 64, 2): return launch_attn<4, 2, 2, 64, 2>(p, st);
+        case tile_id(4, 1, 2, 64, 2): return launch_attn<4, 1, 2, 64, 2>(p, st);
+        case tile_id(6, 1, 2, 64, 2): return launch_attn<6, 1, 2, 64, 2>(p, st);
+        case tile_id(6, 2, 3, 32, 4): return launch_attn<6, 2, 3, 32, 4>(p, st);
+        case tile_id(8, 1, 2, 64, 2): return launch_attn<8, 1, 2, 64, 2>(p, st);
+#ifdef MODCR_TUNING             // (A/B variants of the older kernel: instantiated in the tuning library only)
+        case tile_id(4, 2, 2, 32, 4): return launch_attn<4, 2, 2, 32, 4>(p, st);
+        case tile_id(4, 2, 2, 32, 3): return launch_attn<4, 2, 2, 32, 3>(p, st);
+        case tile_id(6, 1, 3, 32, 3): return launch_attn<6, 1, 3, 32, 3>(p, st);
+        case tile_id(6, 1, 3, 32, 2): return launch_attn<6, 1, 3, 32, 2>(p, st);
+        case tile_id(6, 2, 3, 64, 2): return launch_attn<6, 2, 3, 64, 2>(p, st);
+#endif
+    }
+    modcr_set_error("qkv_attn_fwd: no instantiation NW=%d HPW=%d OCC=%d BKA=%d NSLOT=%d", r.v[0], r.v[1], r.v[2], r.v[3], r.v[4]);
+    return MODCR_ERR_UNSUPPORTED;
+}
+template <int LP, int NH> int launch_route_tile4(int mode, const AttnArgs& p, hipStream_t st) {
+    switch (mode) {
+        case 0: return launch_attn4<0, LP, NH>(p, st);
+        case 1: return launch_attn4<1, LP, NH>(p, st);
+        case 2: return launch_attn4<2, LP, NH>(p, st);
+    }
+    return launch_attn4<3, LP, NH>(p, st);
+}
+
+// x rows [N*S][3H], then the prefix rows [N*P][3H], projected into the workspace; chunk-mean over the query columns
+int attn_project(const void* x, const void* hist, const void* wqkv, const float* bqkv, const int32_t* chunk_id, int32_t chunk_t, int N, int S,
+                 int P, int H, void* workspace, int32_t dtype, modcr_stream_t stream, const void*& qx, const void*& qh) {
+    char* rx = (char*)workspace;
+    char* rh = rx + (int64_t)N * S * 3 * H * (dtype == MODCR_BF16 ? 2 : 4);
+    int rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, rx, 3 * H, N * S, 3 * H, H, MODCR_ACT_NONE, dtype, dtype, stream);
     if (rc != MODCR_OK) return rc;
     if (P > 0) {
-        rc = modcr_linear_fwd(hist, H, wqkv, H, bqkv, nullptr, 0, 0, qkv_h, 3 * H, N * P, 3 * H, H,
-                              MODCR_ACT_NONE, MODCR_F32, MODCR_F32, stream);
+        rc = modcr_linear_fwd(hist, H, wqkv, H, bqkv, nullptr, 0, 0, rh, 3 * H, N * P, 3 * H, H, MODCR_ACT_NONE, dtype, dtype, stream);
         if (rc != MODCR_OK) return rc;
     }
     if (chunk_id) {
-        rc = modcr_chunk_mean_q_fwd(qkv_x, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, MODCR_F32, stream);
+        rc = modcr_chunk_mean_q_fwd(rx, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, dtype, stream);
         if (rc != MODCR_OK) return rc;
     }
-    AttnF32Args f;
-    f.qkv_x = qkv_x; f.qkv_h = P > 0 ? qkv_h : nullptr; f.key_mask = key_mask; f.bits = dense_mask_bits;
-    f.ctx = (float*)ctx; f.probs = probs; f.align_map = align_map;
-    f.N = N; f.S = S; f.P = P; f.H = H; f.A = A; f.align_t = align_t;
-    f.drop_thr16 = 0; f.drop_key = 0; f.drop_keep = 1.f; f.side_post_drop = 0;
-    if (attn_p > 0.f) {                                     // exact-parity route: the mask of the bf16 kernels, so the two routes can be compared
-        f.drop_thr16 = attn_thr16(attn_p); f.drop_key = seed + offset * 0x9E3779B97F4A7C15ull;
-        f.drop_keep = 1.0f / (1.0f - attn_p); f.side_post_drop = (flags & MODCR_ATTN_SIDE_POST_DROPOUT) ? 1 : 0;
-    }
-    const int L = P + S;
+    qx = rx; qh = P > 0 ? rh : nullptr;
+    return MODCR_OK;
+}
+
+int launch_attn_f32(const AttnF32Args& f, hipStream_t st) {
+    const int L = f.P + f.S;
     const size_t smem = ((size_t)2 * L * 65 + 256 + 4 * (size_t)L) * sizeof(float);
     static bool configured_dev[MODCR_MAX_DEV] = {};
     bool& configured = configured_dev[modcr_device_index()];
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) {
             modcr_set_error("qkv_attn(f32): cannot reserve LDS: %s", hipGetErrorString(e));
             return MODCR_ERR_LAUNCH;
         }
         configured = true;
     }
-    hipLaunchKernelGGL(attn_f32_kernel, dim3(N * A), dim3(256), smem, st, f);
+    hipLaunchKernelGGL(attn_f32_kernel, dim3(f.N * f.A), dim3(256), smem, st, f);
     return modcr_check_launch("attn_f32");
+}
+
+// Every forward entry: setup, route, the route's arguments, launch.  bias = the bias / head_mask arguments of modcr_qkv_attn_bias_fwd.
+// lse (or NULL): [N, A, S] fp32, log2 of every query row's sum of exp2(log2e x score) -- the row statistics the five-product
+// backward rebuilds the probabilities from.  flags: modcr_hip.h (MODCR_ATTN_SIDE_POST_DROPOUT: modeling_bert.py:69-74, v10:94-106).
+int attn_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* key_mask, const uint32_t* dense_mask_bits,
+             const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs, float* align_map, int32_t align_t, float* lse, void* qkv_dump,
+             int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
+             void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream, const AttnLongArgs* bias = nullptr) {
+    const AttnCall c = {bias ? "qkv_attn_bias_fwd" : "qkv_attn_fwd",
+                        (bias ? MODCR_ATTN_HAS_BIAS : 0) | attn_present(dense_mask_bits, chunk_id, probs, align_map, lse, qkv_dump), chunk_t, align_t,
+                        N, S, P, H, A, attn_p, flags, workspace ? workspace_bytes : 0, modcr_aligned16(workspace), dtype};
+    int rc = attn_fwd_setup(c, x && wqkv && bqkv && ctx, hist != nullptr,
+                            modcr_aligned16(x) && modcr_aligned16(wqkv) && modcr_aligned16(ctx) && (P == 0 || modcr_aligned16(hist)));
+    if (rc == MODCR_OK) rc = bias ? attn_bias_checks(*bias) : attn_opt_checks(c, key_mask || dense_mask_bits, modcr_aligned16(qkv_dump));
+    if (rc != MODCR_OK) return rc;
+    const AttnRoute r = attn_fwd_route(c);
+    if (r.rc != MODCR_OK) return r.rc;
+    hipStream_t st = (hipStream_t)stream;
+    const AttnDrop d = attn_drop(attn_p, seed, offset);     // the same mask on every route, so that they can be compared
+    const int side_post_drop = (attn_p > 0.f && (flags & MODCR_ATTN_SIDE_POST_DROPOUT)) ? 1 : 0;
+    if (r.family == MODCR_ATTN_ROUTE_TILE || r.family == MODCR_ATTN_ROUTE_TILE4) {
+        AttnArgs p;
+        p.x = (const bf16*)x; p.hist = (const bf16*)hist; p.wqkv = (const bf16*)wqkv; p.bqkv = bqkv;
+        p.key_mask = key_mask; p.bits = dense_mask_bits; p.chunk_id = chunk_id;
+        p.ctx = (bf16*)ctx; p.probs = probs; p.align_map = align_map; p.lse = lse; p.dump = (bf16*)qkv_dump;
+        p.N = N; p.S = S; p.P = P; p.H = H; p.A = A; p.chunk_t = chunk_t; p.align_t = align_t;
+        p.drop_on = d.thr16 != 0; p.drop_thr2 = d.thr2(); p.drop_key = d.key; p.drop_keep = d.keep;
+        p.side_post_drop = side_post_drop;
+        // knobs below: tuning build only (common.h); the product library takes the defaults
+        p.debug = modcr_knob_int("MODCR_ATTN_DEBUG", 0);
+#ifdef MODCR_TUNING
+        if (getenv("MODCR_ATTN_TRACE_PTR")) p.trace = reinterpret_cast<unsigned long long*>(strtoull(getenv("MODCR_ATTN_TRACE_PTR"), nullptr, 0));
+#endif
+        p.hconc = modcr_knob_int("MODCR_ATTN_HCONC", 3);     // tile kernels: 3 head pairs at a time per XCD (measured 166 vs 168 us; FETCH_SIZE: profiles/)
+        if (r.concat) {
+            const int64_t pieces = (int64_t)N * (P + S) * (H >> 3);
+            const int grid = (int)((pieces + 255) / 256 < 16384 ? (pieces + 255) / 256 : 16384);
+            hipLaunchKernelGGL(concat_prefix_kernel, dim3(grid), dim3(256), 0, st, p.hist, p.x, (bf16*)workspace, N, P, S, H);
+            rc = modcr_check_launch("concat_prefix");
+            if (rc != MODCR_OK) return rc;
+            p.x = (const bf16*)workspace;
+        }
+        if (r.family == MODCR_ATTN_ROUTE_TILE) return launch_route_tile(r, p, st);
+        if (r.v[1] == 128) return launch_route_tile4<128, 2>(r.v[0], p, st);
+        return r.v[1] == 192 ? launch_route_tile4<192, 2>(r.v[0], p, st) : launch_route_tile4<256, 1>(r.v[0], p, st);
+    }
+    const void *qx, *qh;
+    rc = attn_project(x, hist, wqkv, bqkv, chunk_id, chunk_t, N, S, P, H, workspace, dtype, stream, qx, qh);
+    if (rc != MODCR_OK) return rc;
+    if (r.family == MODCR_ATTN_ROUTE_F32) {
+        AttnF32Args f;
+        f.qkv_x = (const float*)qx; f.qkv_h = (const float*)qh; f.key_mask = key_mask; f.bits = dense_mask_bits;
+        f.ctx = (float*)ctx; f.probs = probs; f.align_map = align_map;
+        f.N = N; f.S = S; f.P = P; f.H = H; f.A = A; f.align_t = align_t;
+        f.drop_thr16 = d.thr16; f.drop_key = d.key; f.drop_keep = d.keep; f.side_post_drop = side_post_drop;
+        return launch_attn_f32(f, st);
+    }
+    AttnLongArgs g = bias ? *bias : AttnLongArgs{};
+    g.qx = qx; g.qh = qh; g.key_mask = key_mask; g.bits = dense_mask_bits;
+    g.ctx = ctx; g.probs = probs; g.align_map = align_map;
+    g.N = N; g.S = S; g.P = P; g.H = H; g.A = A; g.align_t = align_t;
+    g.drop_thr16 = d.thr16; g.drop_key = d.key; g.drop_keep = d.keep; g.side_post_drop = side_post_drop;
+    hipEvent_t ev0 = g_time_start, ev1 = g_time_stop;       // the measurement hook times the core, not the projection
+    g_time_start = g_time_stop = nullptr;
+    return modcr_launch_attn_long(g, dtype, st, ev0, ev1);
+}
+
+}  // namespace
+
+extern "C" int modcr_qkv_attn_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* key_mask,
+                                  const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
+                                  float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, void* workspace,
+                                  int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
+    return attn_fwd(x, hist, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, ctx, probs, align_map, align_t, nullptr, nullptr,
+                    N, S, P, H, A, 0.f, 0, 0, 0, workspace, workspace_bytes, dtype, stream);
+}
+
+extern "C" int modcr_qkv_attn_dropout_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* key_mask,
+                                          const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
+                                          float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
+                                          uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                                          modcr_stream_t stream) {
+    return attn_fwd(x, hist, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, ctx, probs, align_map, align_t, nullptr, nullptr,
+                    N, S, P, H, A, attn_p, seed, offset, 0, workspace, workspace_bytes, dtype, stream);
+}
+
+extern "C" int modcr_qkv_attn_lse_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* key_mask,
+                                      const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
+                                      float* align_map, int32_t align_t, float* lse, void* qkv_dump, int32_t N, int32_t S, int32_t P, int32_t H,
+                                      int32_t A, float attn_p, uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes,
+                                      int32_t dtype, modcr_stream_t stream) {
+    return attn_fwd(x, hist, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, ctx, probs, align_map, align_t, lse, qkv_dump,
+                    N, S, P, H, A, attn_p, seed, offset, 0, workspace, workspace_bytes, dtype, stream);
+}
+
+extern "C" int modcr_qkv_attn_opt_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* key_mask,
+                                      const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
+                                      float* align_map, int32_t align_t, float* lse, void* qkv_dump, int32_t N, int32_t S, int32_t P, int32_t H,
+                                      int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags, void* workspace,
+                                      int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
+    return attn_fwd(x, hist, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, ctx, probs, align_map, align_t, lse, qkv_dump,
+                    N, S, P, H, A, attn_p, seed, offset, flags, workspace, workspace_bytes, dtype, stream);
+}
+
+// Attention forward with an additive fp32 bias (any float mask, broadcastable over sequence / head / query) and / or a per-head
+// multiplier, P + S <= 512: the bias variant of the streaming core (mode 1, or 2 with dropout) at every key count.
+extern "C" int modcr_qkv_attn_bias_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* bias, int64_t bias_stride_n,
+                                       int64_t bias_stride_a, int64_t bias_stride_q, const float* head_mask, int64_t head_mask_stride_n,
+                                       const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs, float* align_map, int32_t align_t,
+                                       int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset,
+                                       int32_t flags, void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
+    AttnLongArgs b = {};
+    b.bias = bias; b.bias_sn = bias_stride_n; b.bias_sa = bias_stride_a; b.bias_sq = bias_stride_q;
+    b.head_mask = head_mask; b.head_mask_sn = head_mask_stride_n;
+    return attn_fwd(x, hist, wqkv, bqkv, nullptr, nullptr, chunk_id, chunk_t, ctx, probs, align_map, align_t, nullptr, nullptr,
+                    N, S, P, H, A, attn_p, seed, offset, flags, workspace, workspace_bytes, dtype, stream, &b);
+}
+
+extern "C" int modcr_qkv_attn_route(int32_t present, int32_t chunk_t, int32_t align_t, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A,
+                                    float attn_p, int32_t flags, int64_t workspace_bytes, int32_t workspace_aligned16, int32_t dtype, int32_t* info) {
+    MODCR_REQUIRE(info, "qkv_attn_route: null info");
+    const bool bias = present & MODCR_ATTN_HAS_BIAS;
+    MODCR_REQUIRE(!bias || !(present & (MODCR_ATTN_HAS_DENSE_MASK | MODCR_ATTN_HAS_LSE | MODCR_ATTN_HAS_QKV_DUMP)),
+                  "qkv_attn_route: modcr_qkv_attn_bias_fwd takes no dense_mask_bits, lse or qkv_dump");
+    const AttnCall c = {bias ? "qkv_attn_bias_fwd" : "qkv_attn_fwd", present, chunk_t, align_t, N, S, P, H, A, attn_p, flags, workspace_bytes,
+                        workspace_aligned16 != 0, dtype};
+    int rc = attn_fwd_setup(c, true, true, true);
+    if (rc == MODCR_OK && !bias) rc = attn_opt_checks(c, true, true);
+    if (rc != MODCR_OK) return rc;
+    const AttnRoute r = attn_fwd_route(c);
+    if (r.rc != MODCR_OK) return r.rc;
+    info[0] = r.family;
+    for (int i = 0; i < 5; ++i) info[1 + i] = r.v[i];
+    info[6] = r.concat;
+    return MODCR_OK;
 }
 
 
@@ -2548,60 +2561,19 @@ extern "C" int64_t modcr_qkv_attn_bwd_workspace(int32_t N, int32_t S, int32_t H,
     return 2 * ((rows + 255) & ~(int64_t)255) + attn_bwd_sub_ws(N * S, H);
 }
 
-extern "C" int modcr_qkv_attn_lse_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv,
-                                      const float* key_mask, const uint32_t* dense_mask_bits, const int32_t* chunk_id,
-                                      int32_t chunk_t, const float* dx_residual, void* dx, float* dwqkv, float* dbqkv, int32_t accumulate, int32_t N,
-                                      int32_t S, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset,
-                                      const float* d_align, int32_t align_t, const void* ctx, const float* lse, const void* qkv_dump,
-                                      void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
+namespace {
 
-extern "C" int modcr_qkv_attn_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv,
-                                  const float* key_mask, const uint32_t* dense_mask_bits, const int32_t* chunk_id,
-                                  int32_t chunk_t, void* dx, float* dwqkv, float* dbqkv, int32_t accumulate, int32_t N,
-                                  int32_t S, int32_t H, int32_t A, void* workspace, int64_t workspace_bytes,
-                                  int32_t dtype, modcr_stream_t stream) {
-    return modcr_qkv_attn_lse_bwd(dctx, x, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, nullptr, dx, dwqkv, dbqkv, accumulate,
-                                  N, S, H, A, 0.f, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, workspace, workspace_bytes, dtype, stream);
-}
-
-extern "C" int modcr_qkv_attn_dropout_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv,
-                                          const float* key_mask, const uint32_t* dense_mask_bits, const int32_t* chunk_id,
-                                          int32_t chunk_t, const float* dx_residual, void* dx, float* dwqkv, float* dbqkv, int32_t accumulate, int32_t N,
-                                          int32_t S, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset,
-                                          const float* d_align, int32_t align_t,
-                                          void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
-    return modcr_qkv_attn_lse_bwd(dctx, x, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, dx_residual, dx, dwqkv, dbqkv, accumulate,
-                                  N, S, H, A, attn_p, seed, offset, d_align, align_t, nullptr, nullptr, nullptr, workspace, workspace_bytes, dtype, stream);
-}
-
+// Every backward entry (modcr_qkv_attn_bwd, _dropout_bwd, _lse_bwd, _opt_bwd).
 // ctx + lse (both or neither; bf16 path): the forward's context rows and the row statistics modcr_qkv_attn_lse_fwd wrote.  With
 // them the attention core runs as the five-product kernel of attn_bwd.hip (P rebuilt from lse, delta = rowsum(dO o O));
 // without them, or with an align-map gradient, the older core recomputes the statistics (eight products).
-extern "C" int modcr_qkv_attn_opt_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv,
-                                      const float* key_mask, const uint32_t* dense_mask_bits, const int32_t* chunk_id,
-                                      int32_t chunk_t, const float* dx_residual, void* dx, float* dwqkv, float* dbqkv, int32_t accumulate, int32_t N,
-                                      int32_t S, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset,
-                                      const float* d_align, int32_t align_t, const void* ctx, const float* lse, const void* qkv_dump, int32_t flags,
-                                      void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
-
-extern "C" int modcr_qkv_attn_lse_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv,
-                                      const float* key_mask, const uint32_t* dense_mask_bits, const int32_t* chunk_id,
-                                      int32_t chunk_t, const float* dx_residual, void* dx, float* dwqkv, float* dbqkv, int32_t accumulate, int32_t N,
-                                      int32_t S, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset,
-                                      const float* d_align, int32_t align_t, const void* ctx, const float* lse, const void* qkv_dump,
-                                      void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
-    return modcr_qkv_attn_opt_bwd(dctx, x, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, dx_residual, dx, dwqkv, dbqkv, accumulate,
-                                  N, S, H, A, attn_p, seed, offset, d_align, align_t, ctx, lse, qkv_dump, 0, workspace, workspace_bytes, dtype, stream);
-}
-
 // flags: MODCR_ATTN_SIDE_POST_DROPOUT = d_align is the gradient of an align map that summed the probabilities AFTER the dropout
 // (modcr_qkv_attn_opt_fwd with the same flag): it enters dP under the forward's mask, m / (1 - p) o d_align
-extern "C" int modcr_qkv_attn_opt_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv,
-                                      const float* key_mask, const uint32_t* dense_mask_bits, const int32_t* chunk_id,
-                                      int32_t chunk_t, const float* dx_residual, void* dx, float* dwqkv, float* dbqkv, int32_t accumulate, int32_t N,
-                                      int32_t S, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset,
-                                      const float* d_align, int32_t align_t, const void* ctx, const float* lse, const void* qkv_dump, int32_t flags,
-                                      void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
+int attn_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* key_mask, const uint32_t* dense_mask_bits,
+             const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx, float* dwqkv, float* dbqkv, int32_t accumulate,
+             int32_t N, int32_t S, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, const float* d_align, int32_t align_t,
+             const void* ctx, const float* lse, const void* qkv_dump, int32_t flags, void* workspace, int64_t workspace_bytes, int32_t dtype,
+             modcr_stream_t stream) {
     MODCR_REQUIRE(dctx && x && wqkv && bqkv && dx && dwqkv && dbqkv, "qkv_attn_bwd: null pointer");
     MODCR_REQUIRE((flags & ~MODCR_ATTN_SIDE_POST_DROPOUT) == 0, "qkv_attn_bwd: unknown flags 0x%x", flags);
     MODCR_REQUIRE(!d_align || (align_t > 0 && align_t < S), "qkv_attn_bwd: align_t=%d out of range", align_t);
@@ -2644,17 +2616,13 @@ extern "C" int modcr_qkv_attn_opt_bwd(const void* dctx, const void* x, const voi
     AttnBwdArgs b;
     b.qkv = qkv; b.qkvb = reinterpret_cast<const bf16*>(qkv); b.dctx = dctx; b.key_mask = key_mask; b.bits = dense_mask_bits; b.dqkv = dqkv;
     b.N = N; b.S = S; b.H = H; b.A = A; b.out_bf16 = 0;
-    b.drop_thr16 = 0; b.drop_key = 0; b.drop_keep = 1.f;
+    const AttnDrop d = attn_drop(attn_p, seed, offset);     // (as the forward)
+    b.drop_thr16 = d.thr16; b.drop_key = d.key; b.drop_keep = d.keep;
     b.side_post_drop = (attn_p > 0.f && (flags & MODCR_ATTN_SIDE_POST_DROPOUT)) ? 1 : 0;
     b.d_align = d_align; b.align_t = align_t;
     b.ctx = reinterpret_cast<const bf16*>(ctx); b.lse = lse; b.dump = reinterpret_cast<const bf16*>(qkv_dump);
     b.delta_align = qkv_dump ? qkv : nullptr;               // (with the dump the q|k|v area of the workspace is free: N A S floats of it)
     b.debug = modcr_knob_int("MODCR_ATTN_BWD_DEBUG", 0);                 // tuning build only
-    if (attn_p > 0.f) {
-        b.drop_key = seed + offset * 0x9E3779B97F4A7C15ull;
-        b.drop_thr16 = attn_thr16(attn_p);                  // (as the forward)
-        b.drop_keep = 1.0f / (1.0f - attn_p);
-    }
     const size_t smem = ((size_t)2 * S * 65 + 3 * (size_t)S + 4 * (128 + 2 * (size_t)S)) * sizeof(float);
     static bool configured_dev[MODCR_MAX_DEV] = {};
     bool& configured = configured_dev[modcr_device_index()];
@@ -2692,4 +2660,42 @@ extern "C" int modcr_qkv_attn_opt_bwd(const void* dctx, const void* x, const voi
     rc = modcr_linear_bwd_input_res(dqkv, 3 * H, gdt, wqkv, H, dx_residual, H, dx, H, M, 3 * H, H, dtype, dtype, sub, sub_bytes, stream);
     if (rc != MODCR_OK) return rc;
     return modcr_linear_bwd_weight(dqkv, 3 * H, gdt, x, H, dwqkv, dbqkv, M, 3 * H, H, accumulate, dtype, sub, sub_bytes, stream);
+}
+
+}  // namespace
+
+extern "C" int modcr_qkv_attn_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* key_mask,
+                                  const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, void* dx, float* dwqkv, float* dbqkv,
+                                  int32_t accumulate, int32_t N, int32_t S, int32_t H, int32_t A, void* workspace, int64_t workspace_bytes,
+                                  int32_t dtype, modcr_stream_t stream) {
+    return attn_bwd(dctx, x, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, nullptr, dx, dwqkv, dbqkv, accumulate,
+                    N, S, H, A, 0.f, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, workspace, workspace_bytes, dtype, stream);
+}
+
+extern "C" int modcr_qkv_attn_dropout_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* key_mask,
+                                          const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual,
+                                          void* dx, float* dwqkv, float* dbqkv, int32_t accumulate, int32_t N, int32_t S, int32_t H, int32_t A,
+                                          float attn_p, uint64_t seed, uint64_t offset, const float* d_align, int32_t align_t, void* workspace,
+                                          int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
+    return attn_bwd(dctx, x, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, dx_residual, dx, dwqkv, dbqkv, accumulate,
+                    N, S, H, A, attn_p, seed, offset, d_align, align_t, nullptr, nullptr, nullptr, 0, workspace, workspace_bytes, dtype, stream);
+}
+
+extern "C" int modcr_qkv_attn_lse_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* key_mask,
+                                      const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx,
+                                      float* dwqkv, float* dbqkv, int32_t accumulate, int32_t N, int32_t S, int32_t H, int32_t A, float attn_p,
+                                      uint64_t seed, uint64_t offset, const float* d_align, int32_t align_t, const void* ctx, const float* lse,
+                                      const void* qkv_dump, void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
+    return attn_bwd(dctx, x, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, dx_residual, dx, dwqkv, dbqkv, accumulate,
+                    N, S, H, A, attn_p, seed, offset, d_align, align_t, ctx, lse, qkv_dump, 0, workspace, workspace_bytes, dtype, stream);
+}
+
+extern "C" int modcr_qkv_attn_opt_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* key_mask,
+                                      const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx,
+                                      float* dwqkv, float* dbqkv, int32_t accumulate, int32_t N, int32_t S, int32_t H, int32_t A, float attn_p,
+                                      uint64_t seed, uint64_t offset, const float* d_align, int32_t align_t, const void* ctx, const float* lse,
+                                      const void* qkv_dump, int32_t flags, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                                      modcr_stream_t stream) {
+    return attn_bwd(dctx, x, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, dx_residual, dx, dwqkv, dbqkv, accumulate,
+                    N, S, H, A, attn_p, seed, offset, d_align, align_t, ctx, lse, qkv_dump, flags, workspace, workspace_bytes, dtype, stream);
 }

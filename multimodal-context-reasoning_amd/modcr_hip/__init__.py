@@ -38,6 +38,7 @@ SIGNATURES = {
     "modcr_qkv_attn_bias_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "modcr_qkv_attn_bias_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i32,
                                        _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _i32, _vp, _i64, _i32, _vp]),
+    "modcr_qkv_attn_route": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i64, _i32, _i32, _c.POINTER(_i32)]),
     "modcr_linear_splitk_workspace": (_i64, [_i32, _i32, _i32]),
     "modcr_linear_splitk_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "modcr_qkv_attn_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
@@ -509,10 +510,39 @@ def additive_mask_is_binary(mask):
     return bool(((mask == 0) | (mask == -10000.0)).all().item())
 
 
+# modcr_qkv_attn_route: kernel families (MODCR_ATTN_ROUTE_*) and the bits of `present` (MODCR_ATTN_HAS_*)
+ATTN_ROUTE_FAMILIES = {1: "tile", 2: "tile4", 3: "long_bf16", 4: "f32", 5: "long_f32"}
+ATTN_HAS_BIAS, ATTN_HAS_DENSE_MASK, ATTN_HAS_CHUNK_ID, ATTN_HAS_PROBS, ATTN_HAS_ALIGN_MAP, ATTN_HAS_LSE, ATTN_HAS_QKV_DUMP = 1, 2, 4, 8, 16, 32, 64
+AttnRoute = collections.namedtuple("AttnRoute", "rc family inst concat message")
+
+
+def qkv_attn_route(n, s, p, h, a, dtype=BF16, bias=False, dense=False, chunk_t=0, probs=False, align_t=0, lse=False, dump=False,
+                   attn_p=0.0, flags=0, workspace_bytes=None, workspace_aligned=True):
+    """The route the attention forward takes for these arguments (modcr_qkv_attn_route; nothing is launched or read):
+    AttnRoute(rc = the call's return code, family = a name of ATTN_ROUTE_FAMILIES, inst = the five numbers that pick the
+    instantiation, concat, message = the refusal's text).  bias: the call goes to modcr_qkv_attn_bias_fwd; chunk_t / align_t > 0:
+    chunk_id / align_map are given; workspace_bytes None: what qkv_attn supplies for the shape."""
+    present = ((ATTN_HAS_BIAS if bias else 0) | (ATTN_HAS_DENSE_MASK if dense else 0) | (ATTN_HAS_CHUNK_ID if chunk_t else 0) |
+               (ATTN_HAS_PROBS if probs else 0) | (ATTN_HAS_ALIGN_MAP if align_t else 0) | (ATTN_HAS_LSE if lse else 0) |
+               (ATTN_HAS_QKV_DUMP if dump else 0))
+    if workspace_bytes is None:
+        workspace_bytes = (lib().modcr_qkv_attn_bias_workspace if bias else lib().modcr_qkv_attn_workspace)(n, s, p, h, dtype)
+    info = (_i32 * 7)()
+    rc = lib().modcr_qkv_attn_route(present, chunk_t, align_t, n, s, p, h, a, float(attn_p), flags, workspace_bytes,
+                                    1 if workspace_aligned else 0, dtype, info)
+    if rc != 0:
+        return AttnRoute(rc, None, None, None, lib().modcr_last_error().decode())
+    return AttnRoute(0, ATTN_ROUTE_FAMILIES[info[0]], tuple(info[1:6]), info[6], "")
+
+
 def side_outputs_on_tiles(s, p, h, a):
-    """shapes on which the bf16 TILE kernels serve a probabilities output / an align map (the dispatcher of modcr_qkv_attn_opt_fwd,
-    csrc/attn.hip: 64 < S <= 256 without prefix rows, H a multiple of 128, head pairs up to 192 rows, one head per workgroup above)"""
-    return p == 0 and 64 < s <= 256 and h % 128 == 0 and 256 <= h <= 8192 and (a % 2 == 0 or s > 192)
+    """shapes on which the bf16 TILE kernels serve a post-dropout probabilities output / align map: what the dispatcher of
+    modcr_qkv_attn_opt_fwd answers for that call (64 < S <= 256 without prefix rows, H = 64 A a multiple of 128, head pairs up to
+    192 rows, one head per workgroup above).  Asked with a probabilities output; an align map alone gets the same answer, since
+    either one keeps prefix rows off the tile kernels and lands on the same generic tile variant.  Needs the built library, and a
+    False answer leaves the refusal's text in modcr_last_error."""
+    r = qkv_attn_route(1, s, p, h, a, probs=True, attn_p=0.5, flags=ATTN_SIDE_POST_DROPOUT)
+    return r.rc == 0 and r.family == "tile4"
 
 
 def qkv_dump_numel(n, s, a):

@@ -1448,6 +1448,23 @@ def test_side_outputs_on_tiles_predicate_is_the_dispatchers(mh, monkeypatch):
         assert ok == real(s, pfx, h, a), (s, pfx, h, a, ok)
 
 
+def test_attn_route_query_is_what_the_call_does(mh):
+    """modcr_qkv_attn_route against the entries themselves: every second row of the host test's route table (tests/
+    test_attn_route_host.py: every key-count class, both dtypes, prefix rows, the bias entry, the refusals) at N = 2 -- the call
+    succeeds or is refused exactly as the query's return code says, with the query's message, and writes finite context rows."""
+    import test_attn_route_host as R
+    rows = R.ROUTES[::2]
+    assert len(rows) >= 30 and sum(isinstance(w[0], int) for _, w, _ in rows) >= 5
+    for i, (kw, want, rule) in enumerate(rows):
+        r = R.route_of_call(mh, kw)
+        rc, msg, out = R.Case(mh, kw, 300 + i).call(mh.lib(), mh)
+        assert (rc, msg) == (r.rc, r.message), (kw, rule, rc, msg, r)
+        assert (rc != 0) == isinstance(want[0], int), (kw, rule, rc, msg)
+        if rc == 0:
+            ctx = out["ctx"].float()
+            assert bool(torch.isfinite(ctx).all()) and float(ctx.abs().max()) > 0, (kw, rule)
+
+
 @pytest.mark.parametrize("t,r,with_dump", [(80, 100, True), (80, 100, False), (60, 40, True)])
 def test_attn_bwd_align_map_gradient_after_the_dropout(mh, t, r, with_dump):
     """The same flag in the backward: the align map summed P o m / (1 - p), so its gradient d_align enters dP under the forward's mask,
