@@ -139,6 +139,25 @@ int modcr_qkv_attn_bias_fwd(const void* x, const void* hist, const void* wqkv, c
                             void* ctx, float* probs, float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P,
                             int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
                             void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
+/* The forward over the LIVE-ROW layout of a frozen encoder pass.  Sequence n keeps only its first L_n rows (1 <= L_n <= S: the
+ * rows behind them are padded image regions -- keys that every mask hides, queries that no consumer reads), and the kept rows of
+ * all sequences lie back to back:
+ *   row_start  int32 [N + 1] on the device, row_start[0] = 0, row_start[n + 1] = row_start[n] + L_n.  x and ctx are buffers of
+ *              N * S rows of H; row row_start[n] + s of either is row s of sequence n (s < L_n).  Rows from row_start[N] on are
+ *              neither read nor written.  A table entry outside the buffer is clamped into it, not followed.
+ *   key_mask [N, S], dense_mask_bits [N, S, LW], chunk_id [N, chunk_t], align_map [N, T, S - T] and the attention-dropout
+ *              counters stay indexed by (sequence, position) exactly as in modcr_qkv_attn_opt_fwd: they do not depend on the
+ *              layout.  Keys L_n..S-1 of sequence n MUST be hidden by the mask the call gives (their tile rows re-read row
+ *              L_n - 1); with that, every context row and the align map are bit-identical to the dense call on the same rows.
+ * Served by the key-mask, dense-mask and phase-3 (dense mask + chunk_id + align_map) variants of qkv_attn4_kernel on the 128- and
+ * 192-token tiles (bf16, 64 < S <= 192, A even, H % 128 == 0, H >= 256).  No prefix rows, probabilities, lse or q|k|v dump; any
+ * other call returns MODCR_ERR_UNSUPPORTED before anything is launched (modcr_qkv_attn_route with MODCR_ATTN_HAS_ROW_START
+ * answers the same), and the caller keeps the dense layout.  modcr_time_next_attn times this launch too. */
+int modcr_qkv_attn_rows_fwd(const void* x, const void* wqkv, const float* bqkv, const float* key_mask,
+                            const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, void* ctx,
+                            float* align_map, int32_t align_t, const int32_t* row_start, int32_t N, int32_t S, int32_t H,
+                            int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags, int32_t dtype,
+                            modcr_stream_t stream);
 /* The route a forward call takes for the same scalars (no stream), decided by the same host functions: every modcr_qkv_attn_*_fwd
  * entry above, or -- with MODCR_ATTN_HAS_BIAS -- modcr_qkv_attn_bias_fwd.  `present` says which optional arguments the call gives
  * (MODCR_ATTN_HAS_*; key_mask is taken as given where dense_mask_bits is not), workspace_bytes / workspace_aligned16 describe its
@@ -149,7 +168,8 @@ int modcr_qkv_attn_bias_fwd(const void* x, const void* hist, const void* wqkv, c
  * 1 = bias / head mask, 2 = the same with dropout); 0 otherwise -- and info[6] = 1 when concat_prefix_kernel first copies
  * [hist ; x] into the workspace.  The tuning build reports the route its MODCR_ATTN_* knobs select. */
 enum { MODCR_ATTN_HAS_BIAS = 1, MODCR_ATTN_HAS_DENSE_MASK = 2, MODCR_ATTN_HAS_CHUNK_ID = 4, MODCR_ATTN_HAS_PROBS = 8,
-       MODCR_ATTN_HAS_ALIGN_MAP = 16, MODCR_ATTN_HAS_LSE = 32, MODCR_ATTN_HAS_QKV_DUMP = 64 };
+       MODCR_ATTN_HAS_ALIGN_MAP = 16, MODCR_ATTN_HAS_LSE = 32, MODCR_ATTN_HAS_QKV_DUMP = 64,
+       MODCR_ATTN_HAS_ROW_START = 128 /* the call is modcr_qkv_attn_rows_fwd */ };
 enum { MODCR_ATTN_ROUTE_TILE = 1 /* the older tile kernel */, MODCR_ATTN_ROUTE_TILE4 = 2, MODCR_ATTN_ROUTE_LONG_BF16 = 3,
        MODCR_ATTN_ROUTE_F32 = 4 /* exact core, P + S <= 256 */, MODCR_ATTN_ROUTE_LONG_F32 = 5 };
 int modcr_qkv_attn_route(int32_t present, int32_t chunk_t, int32_t align_t, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A,
@@ -514,6 +534,47 @@ int modcr_dropout(const void* x, void* out, int64_t n, int32_t dtype, float p, u
 int modcr_dropout_residual_ln_fwd(const void* x, int32_t x_dtype, const void* residual, int32_t res_dtype, const float* gamma,
                                   const float* beta, float eps, void* out, int32_t out_dtype, void* pre_out, int32_t pre_dtype, int64_t M,
                                   int32_t H, float p, uint64_t seed, uint64_t offset, modcr_stream_t stream);
+/* The two entries above over the LIVE-ROW layout (modcr_qkv_attn_rows_fwd): row m of x / residual / out / pre_out is row
+ * row_id[m] of the padded buffer the mask is defined over, i.e. the counter of element (m, c) is offset + row_id[m] * H + c.
+ * row_id: int32 [M] on the device, one entry for EVERY row of the launch (filler rows: any value; they take some counters and nobody reads them).  NULL = the entries
+ * above, bit for bit; p = 0 never reads it. */
+int modcr_dropout_residual_ln_rows_fwd(const void* x, int32_t x_dtype, const void* residual, int32_t res_dtype, const float* gamma,
+                                       const float* beta, float eps, void* out, int32_t out_dtype, void* pre_out, int32_t pre_dtype,
+                                       int64_t M, int32_t H, float p, uint64_t seed, uint64_t offset, const int32_t* row_id,
+                                       modcr_stream_t stream);
+int modcr_linear_dropout_residual_ln_rows_fwd(const void* A, int64_t lda, const void* W, const float* bias,
+                                              const void* residual, const float* gamma, const float* beta, float eps,
+                                              void* out, void* pre_out, int32_t pre_dtype, int32_t M, int32_t N, int32_t K, float p,
+                                              uint64_t seed, uint64_t offset, const int32_t* row_id, void* workspace,
+                                              int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
+/* dst row i = src row idx[i], i < M (idx int32 on the device; an index outside [0, src_rows) gives a zero row).  Rows of H
+ * elements of `dtype` (bf16 / fp32) that are whole 16-byte pieces; src and dst 16-byte aligned and distinct.  The moves of the
+ * live-row layout: padded rows -> compact rows (idx = row_id), compact rows -> the dense [N, k, H] block a consumer reads
+ * (idx[n k + j] = row_start[n] + j). */
+int modcr_rows_take(const void* src, int64_t src_rows, void* dst, const int32_t* idx, int64_t M, int32_t H, int32_t dtype,
+                    modcr_stream_t stream);
+/* The embedding passes writing the live-row layout directly (no padded buffer in between); every dropout counter is that of
+ * the PADDED position, so a live row holds exactly what the padded passes followed by modcr_rows_take(row_id) give.
+ *   modcr_embed_ln_dropout_rows_fwd: modcr_embed_ln_dropout_fwd with row t of sequence n written to row row_start[n] + t of
+ *     out [out_rows, H] (row_start int32 [N] on the device; a row outside the buffer is not written).  NULL = that entry.
+ *   modcr_rows_place_dropout: modcr_rows_scatter_dropout driven by the destination.  Compact row i < M of dst stands for padded
+ *     row p = row_id[i] of a [*, group_stride, H] buffer; a region row (row0 <= p % group_stride < row0 + rows_per_group)
+ *     receives region j = p % group_stride - row0 of sequence g = p / group_stride from src row g * rows_per_group + j
+ *     (src_start NULL: padded region rows) or src_start[g] + j (region rows back to back), under counter offset + p * H + c;
+ *     text rows are left alone, p < 0 writes a zero row, a source row outside [0, src_rows) or a sequence g >= groups (src_start
+ *     has groups entries) writes nothing.
+ *   modcr_cast_pad_rows: modcr_cast_pad to bf16 with gathered rows: dst row m = src row src_row[m], outside [0, src_rows) a
+ *     zero row.  Needs Kp % 8 == 0, an even lds, ldd % 8 == 0, src 8-byte and dst 16-byte aligned. */
+int modcr_embed_ln_dropout_rows_fwd(const int64_t* input_ids, const int64_t* token_type_ids, const int64_t* position_ids,
+                                    const float* word, const float* pos, const float* type, const float* gamma, const float* beta,
+                                    float eps, void* out, int32_t N, int32_t T, int32_t H, int64_t seq_stride, int32_t vocab,
+                                    int32_t max_pos, int32_t type_vocab, int32_t out_dtype, float p, uint64_t seed, uint64_t offset,
+                                    const int32_t* row_start, int64_t out_rows, modcr_stream_t stream);
+int modcr_rows_place_dropout(const void* src, int64_t src_rows, void* dst, const int32_t* row_id, const int32_t* src_start,
+                             int64_t groups, int64_t M, int32_t H, int32_t rows_per_group, int64_t group_stride, int32_t row0, int32_t dtype, float p,
+                             uint64_t seed, uint64_t offset, modcr_stream_t stream);
+int modcr_cast_pad_rows(const float* src, int64_t lds, int64_t src_rows, void* dst, int64_t ldd, int64_t M, int32_t K, int32_t Kp,
+                        const int32_t* src_row, modcr_stream_t stream);
 
 /* out[n] = a[n] + b[n]: a fp32, b / out fp32 or bf16 (the residual-gradient sums of the layer backward) */
 int modcr_add(const float* a, const void* b, int32_t b_dtype, void* out, int32_t out_dtype, int64_t n,

@@ -72,6 +72,11 @@ struct AttnArgs {
     const float* row_stats = nullptr;
     const float* cfold = nullptr;
 #endif
+    // live-row layout (modcr_qkv_attn_rows_fwd; qkv_attn4_kernel, no prefix rows): sequence n holds only its first
+    // L_n = row_start[n + 1] - row_start[n] rows, and they lie back to back from row row_start[n] of x and ctx on.  Tile rows
+    // L_n..S-1 (padded regions: keys that every mask hides, queries nobody reads) re-read row L_n - 1 and are not stored; masks, chunk
+    // ids, the align map and the dropout counters stay indexed by (n, s).  NULL = the dense [N, S, H] layout.
+    const int32_t* row_start = nullptr;
 };
 
 // attention-probability dropout as the host hands it to a kernel: the 64-bit key of (seed, offset), thr16 = round(p * 2^16) (0 = off)
@@ -575,7 +580,7 @@ struct A4T {
     static constexpr int IMGS = 2 * NH * LP * 128 + NH * 64 * VT_STRIDE;
     static constexpr int MAIN = (IMGS > RING) ? IMGS : RING;
     static constexpr int DROP_OFF = MAIN + LP * 4 + NF * 4 + LP * 4 + 16 + 3 * LP * 4;   // 8 dwords: attention-dropout parameters, P
-    static constexpr int SMEM = DROP_OFF + 32;
+    static constexpr int SMEM = DROP_OFF + 48;                  // + 3 dwords: first context row of the tile's sequence (64 bit), its row count
     static constexpr int FOLD_OFF = SMEM;                       // FOLD variants: sRs[LP] | sRm[LP] | sC[NF] floats behind everything else
     static constexpr int SMEM_FOLD = FOLD_OFF + 2 * LP * 4 + NF * 4;
     static constexpr int FLY4 = 2 * NA + 2 * NBI;               // DMA instructions per wave in four consecutive half-tiles
@@ -694,6 +699,8 @@ __device__ __attribute__((noinline)) void attn4_exact_tail(unsigned char* smem, 
     const int P = (int)sDrop[4];
     float* lse_out = reinterpret_cast<float*>(((uint64_t)sDrop[6] << 32) | sDrop[5]);
     const bool side_post = drop_on && sDrop[7] != 0;        // probabilities / align map after the dropout (reference semantics)
+    const int64_t crow = (int64_t)(((uint64_t)sDrop[9] << 32) | sDrop[8]);      // first context row of sequence n (n * S, or row_start[n])
+    const int Ln = (int)sDrop[10];                          // tile rows of the sequence that exist (P + S, or the live-row count)
     const int thr_s = (int)(short)(drop_thr2 & 0xffffu) + 1;   // signed 16-bit threshold: kept iff field >= thr_s
     constexpr int VT_STRIDE = A4::VT_STRIDE, NKT = A4::NKT, NQB = A4::NQB;
     const int lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
@@ -858,7 +865,7 @@ __device__ __attribute__((noinline)) void attn4_exact_tail(unsigned char* smem, 
         float* dst = align_map + (int64_t)n * T * R;
         for (int j = tid; j < T * R; j += A4::NT) atomicAdd(dst + j, sAm[j]);
     }
-    attn4_store_ctx<A4>(o, inv_ctx, smem + (hd * LP + qbase) * 128, ctx + ((int64_t)n * S + qbase - P) * H + a * 64, H, P - qbase, L - qbase, l15, l4, lane);
+    attn4_store_ctx<A4>(o, inv_ctx, smem + (hd * LP + qbase) * 128, ctx + (crow + qbase - P) * H + a * 64, H, P - qbase, Ln - qbase, l15, l4, lane);
 }
 
 // MODE 0 = generic (probabilities / align map / chunk-mean queries / either mask form, exact row max), one tile
@@ -909,6 +916,8 @@ __global__ __launch_bounds__(512, 2) void qkv_attn4_kernel(AttnArgs p) {
     // concatenates them), tile rows / keys 0..L-1 with L = P + S, query rows = tile rows P..L-1 -> output rows 0..S-1
     const int S = p.S, P = p.P, L = p.S + p.P, H = p.H;
     int n = 0, a0 = 0;                                      // sequence and first head of the current tile
+    int Ln = L;                                             // tile rows of sequence n that exist: L, or its live rows (p.row_start)
+    int64_t crow = 0;                                       // first row of sequence n in x (P = 0) and ctx: n * S, or row_start[n]
 
     // ---- DMA sources: uniform base (sequence / weight matrix + k offset) + 32-bit per-lane byte offset.
     // A half mh: LDS row r (0..95) = token (r / 48) * 96 + mh * 48 + r % 48; piece `wave` (8 rows) by all
@@ -1076,7 +1085,16 @@ __global__ __launch_bounds__(512, 2) void qkv_attn4_kernel(AttnArgs p) {
             const int tile = xcd_remap(vt, ntiles);
             n = tile / hgroups; a0 = (tile % hgroups) * NHD;
         }
-        xb = p.x + (int64_t)n * L * H;
+        if (p.row_start) {
+            // (clamped to the buffer's N * S rows: a table that is not what the host builder makes cannot send an access out of it)
+            Ln = min(max(p.row_start[n + 1] - p.row_start[n], 1), L);
+            crow = min(max(p.row_start[n], 0), p.N * L - Ln);
+            xb = p.x + crow * H;
+        } else {
+            Ln = L;
+            crow = (int64_t)n * S;
+            xb = p.x + (int64_t)n * L * H;
+        }
         wt = p.wqkv + (int64_t)a0 * 64 * H;
     }
     {
@@ -1091,7 +1109,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn4_kernel(AttnArgs p) {
             for (int q = 0; q < 2; ++q) {
                 const int r = q == 0 ? 8 * wave + (lane >> 3)
                                      : (A4::A_HALF_PIECE ? 64 + 4 * wave + ((lane & 31) >> 3) : 64 + 8 * wave + (lane >> 3));
-                const int tok = min((r / QW) * A4::RW + mh * QW + (r % QW), L - 1);      // padding rows re-read row L-1
+                const int tok = min((r / QW) * A4::RW + mh * QW + (r % QW), Ln - 1);     // padding rows re-read the last row
                 const int c = (lane & 7) ^ ((r >> 1) & 7);
                 offA[mh][q] = (unsigned)((tok * H + c * 8) * 2);
             }
@@ -1131,6 +1149,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn4_kernel(AttnArgs p) {
             const uint64_t lp64 = reinterpret_cast<uint64_t>(p.lse);
             sDrop[5] = (uint32_t)lp64; sDrop[6] = (uint32_t)(lp64 >> 32);
             sDrop[7] = (uint32_t)p.side_post_drop;
+            sDrop[8] = (uint32_t)crow; sDrop[9] = (uint32_t)((uint64_t)crow >> 32); sDrop[10] = (uint32_t)Ln;
         }
         if (((KMODE == 0 && p.chunk_id) || KMODE == 3) && tidb < LP) { sFirst[tidb] = LP; sLast[tidb] = -1; sCnt[tidb] = 0; }
         if (tidb < A4::NF) {
@@ -1459,9 +1478,9 @@ __global__ __launch_bounds__(512, 2) void qkv_attn4_kernel(AttnArgs p) {
                 float inv_ctx[NQB];
 #pragma unroll
                 for (int qb = 0; qb < NQB; ++qb) inv_ctx[qb] = inv[qb] * p.drop_keep;
-                attn4_store_ctx<A4>(o, inv_ctx, sQ + qbase * 128, p.ctx + ((int64_t)n * S + qbase - P) * H + a * 64, H, P - qbase, L - qbase, l15b, l4b, laneb);
+                attn4_store_ctx<A4>(o, inv_ctx, sQ + qbase * 128, p.ctx + (crow + qbase - P) * H + a * 64, H, P - qbase, Ln - qbase, l15b, l4b, laneb);
             } else {
-                attn4_store_ctx<A4>(o, inv, sQ + qbase * 128, p.ctx + ((int64_t)n * S + qbase - P) * H + a * 64, H, P - qbase, L - qbase, l15b, l4b, laneb);
+                attn4_store_ctx<A4>(o, inv, sQ + qbase * 128, p.ctx + (crow + qbase - P) * H + a * 64, H, P - qbase, Ln - qbase, l15b, l4b, laneb);
             }
             if (KMODE == 3 && !MODCR_DBG(p.debug & 32)) {                // debug bit 5: timing-only, no align map
                 // head-summed text -> region block, no LDS atomics: each head has its OWN [T][R] tile in LDS (head 0 over the
@@ -2267,12 +2286,17 @@ AttnRoute attn_fwd_route(const AttnCall& c) {
     const int N = c.N, S = c.S, P = c.P, H = c.H, A = c.A, L = P + S;
     const bool bf = c.dtype == MODCR_BF16, bias = c.present & MODCR_ATTN_HAS_BIAS, dense = c.present & MODCR_ATTN_HAS_DENSE_MASK,
                chunk = c.present & MODCR_ATTN_HAS_CHUNK_ID, probs = c.present & MODCR_ATTN_HAS_PROBS,
-               align = c.present & MODCR_ATTN_HAS_ALIGN_MAP, lse = c.present & MODCR_ATTN_HAS_LSE;
+               align = c.present & MODCR_ATTN_HAS_ALIGN_MAP, lse = c.present & MODCR_ATTN_HAS_LSE, rows = c.present & MODCR_ATTN_HAS_ROW_START;
     const bool side_post_drop = c.attn_p > 0.f && (c.flags & MODCR_ATTN_SIDE_POST_DROPOUT);
     auto refuse = [&r](int rc, const char* fmt, auto... a) { modcr_set_error(fmt, a...); r.rc = rc; return r; };
     auto tile = [&r](int nw, int hpw, int occ, int bka, int nslot) { r = {MODCR_OK, MODCR_ATTN_ROUTE_TILE, {nw, hpw, occ, bka, nslot}, 0}; };
     // (prefix rows reach qkv_attn4_kernel through the concatenated copy only)
     auto tile4 = [&r, P](int mode, int lp, int nh) { r = {MODCR_OK, MODCR_ATTN_ROUTE_TILE4, {mode, lp, nh, 0, 0}, P > 0}; };
+    // the live-row layout (modcr_qkv_attn_rows_fwd) exists in the streaming variants of qkv_attn4_kernel on the 128- and 192-token
+    // tiles only; everything else is refused here and the caller keeps the dense layout
+    if (rows && (bias || !bf || P > 0 || L > 192 || probs || (c.present & (MODCR_ATTN_HAS_LSE | MODCR_ATTN_HAS_QKV_DUMP))))
+        return refuse(MODCR_ERR_UNSUPPORTED, "%s: the live-row layout takes bf16 calls of at most 192 keys without prefix rows, probabilities, "
+                      "lse or q|k|v dump (S=%d P=%d)", c.who, S, P);
     // the streaming core of attn_long.hip over projected rows: above 256 keys (eval mode: no dropout, no row statistics, no q|k|v
     // dump -- those exist for the backward, which stops at 256 keys), and every call of modcr_qkv_attn_bias_fwd
     if (bias || L > 256) {
@@ -2339,6 +2363,9 @@ AttnRoute attn_fwd_route(const AttnCall& c) {
         else if (v4l && rows4 && P == 0) tile4(0, 256, 1);
         else tile(8, 1, 2, 64, 2);
     }
+    if (rows && !(r.family == MODCR_ATTN_ROUTE_TILE4 && r.v[0] >= 1 && r.v[1] <= 192))
+        return refuse(MODCR_ERR_UNSUPPORTED, "%s: the live-row layout is served by the key-mask, dense-mask and phase-3 variants of the 128- / 192-token "
+                      "tile kernel only (S=%d A=%d H=%d)", c.who, S, A, H);
     // row statistics and post-dropout side outputs come from qkv_attn4_kernel only
     if (r.family == MODCR_ATTN_ROUTE_TILE && lse)
         return refuse(MODCR_ERR_UNSUPPORTED, "%s: no row statistics (lse) on this route (S=%d P=%d A=%d H=%d)", c.who, S, P, A, H);
@@ -2419,9 +2446,10 @@ int launch_attn_f32(const AttnF32Args& f, hipStream_t st) {
 int attn_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* key_mask, const uint32_t* dense_mask_bits,
              const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs, float* align_map, int32_t align_t, float* lse, void* qkv_dump,
              int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
-             void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream, const AttnLongArgs* bias = nullptr) {
-    const AttnCall c = {bias ? "qkv_attn_bias_fwd" : "qkv_attn_fwd",
-                        (bias ? MODCR_ATTN_HAS_BIAS : 0) | attn_present(dense_mask_bits, chunk_id, probs, align_map, lse, qkv_dump), chunk_t, align_t,
+             void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream, const AttnLongArgs* bias = nullptr,
+             const int32_t* row_start = nullptr) {
+    const AttnCall c = {bias ? "qkv_attn_bias_fwd" : row_start ? "qkv_attn_rows_fwd" : "qkv_attn_fwd",
+                        (bias ? MODCR_ATTN_HAS_BIAS : 0) | (row_start ? MODCR_ATTN_HAS_ROW_START : 0) | attn_present(dense_mask_bits, chunk_id, probs, align_map, lse, qkv_dump), chunk_t, align_t,
                         N, S, P, H, A, attn_p, flags, workspace ? workspace_bytes : 0, modcr_aligned16(workspace), dtype};
     int rc = attn_fwd_setup(c, x && wqkv && bqkv && ctx, hist != nullptr,
                             modcr_aligned16(x) && modcr_aligned16(wqkv) && modcr_aligned16(ctx) && (P == 0 || modcr_aligned16(hist)));
@@ -2440,6 +2468,7 @@ int attn_fwd(const void* x, const void* hist, const void* wqkv, const float* bqk
         p.N = N; p.S = S; p.P = P; p.H = H; p.A = A; p.chunk_t = chunk_t; p.align_t = align_t;
         p.drop_on = d.thr16 != 0; p.drop_thr2 = d.thr2(); p.drop_key = d.key; p.drop_keep = d.keep;
         p.side_post_drop = side_post_drop;
+        p.row_start = row_start;
         // knobs below: tuning build only (common.h); the product library takes the defaults
         p.debug = modcr_knob_int("MODCR_ATTN_DEBUG", 0);
 #ifdef MODCR_TUNING
@@ -2516,6 +2545,18 @@ extern "C" int modcr_qkv_attn_opt_fwd(const void* x, const void* hist, const voi
                     N, S, P, H, A, attn_p, seed, offset, flags, workspace, workspace_bytes, dtype, stream);
 }
 
+// The key-mask / dense-mask / phase-3 forward over the live-row layout (AttnArgs::row_start): x and ctx hold sequence n's first
+// L_n = row_start[n + 1] - row_start[n] rows from row row_start[n] on, inside buffers of N * S rows.  Same kernels, same arithmetic.
+extern "C" int modcr_qkv_attn_rows_fwd(const void* x, const void* wqkv, const float* bqkv, const float* key_mask, const uint32_t* dense_mask_bits,
+                                       const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* align_map, int32_t align_t,
+                                       const int32_t* row_start, int32_t N, int32_t S, int32_t H, int32_t A, float attn_p, uint64_t seed,
+                                       uint64_t offset, int32_t flags, int32_t dtype, modcr_stream_t stream) {
+    MODCR_REQUIRE(row_start && ((uintptr_t)row_start & 3) == 0, "qkv_attn_rows_fwd: row_start is null or not 4-byte aligned");
+    MODCR_REQUIRE((int64_t)N * S < (1ll << 31), "qkv_attn_rows_fwd: N * S = %lld rows exceed the int32 row table", (long long)N * S);
+    return attn_fwd(x, nullptr, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, ctx, nullptr, align_map, align_t, nullptr, nullptr,
+                    N, S, 0, H, A, attn_p, seed, offset, flags, nullptr, 0, dtype, stream, nullptr, row_start);
+}
+
 // Attention forward with an additive fp32 bias (any float mask, broadcastable over sequence / head / query) and / or a per-head
 // multiplier, P + S <= 512: the bias variant of the streaming core (mode 1, or 2 with dropout) at every key count.
 extern "C" int modcr_qkv_attn_bias_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* bias, int64_t bias_stride_n,
@@ -2536,7 +2577,7 @@ extern "C" int modcr_qkv_attn_route(int32_t present, int32_t chunk_t, int32_t al
     const bool bias = present & MODCR_ATTN_HAS_BIAS;
     MODCR_REQUIRE(!bias || !(present & (MODCR_ATTN_HAS_DENSE_MASK | MODCR_ATTN_HAS_LSE | MODCR_ATTN_HAS_QKV_DUMP)),
                   "qkv_attn_route: modcr_qkv_attn_bias_fwd takes no dense_mask_bits, lse or qkv_dump");
-    const AttnCall c = {bias ? "qkv_attn_bias_fwd" : "qkv_attn_fwd", present, chunk_t, align_t, N, S, P, H, A, attn_p, flags, workspace_bytes,
+    const AttnCall c = {bias ? "qkv_attn_bias_fwd" : (present & MODCR_ATTN_HAS_ROW_START) ? "qkv_attn_rows_fwd" : "qkv_attn_fwd", present, chunk_t, align_t, N, S, P, H, A, attn_p, flags, workspace_bytes,
                         workspace_aligned16 != 0, dtype};
     int rc = attn_fwd_setup(c, true, true, true);
     if (rc == MODCR_OK && !bias) rc = attn_opt_checks(c, true, true);

@@ -3071,6 +3071,10 @@ extern "C" int modcr_linear_residual_ln_fwd(const void* A, int64_t lda, const vo
 extern "C" int modcr_dropout_residual_ln_fwd(const void* x, int32_t x_dtype, const void* residual, int32_t res_dtype, const float* gamma,
                                              const float* beta, float eps, void* out, int32_t out_dtype, void* pre_out, int32_t pre_dtype,
                                              int64_t M, int32_t H, float p, uint64_t seed, uint64_t offset, modcr_stream_t stream);
+extern "C" int modcr_dropout_residual_ln_rows_fwd(const void* x, int32_t x_dtype, const void* residual, int32_t res_dtype, const float* gamma,
+                                                  const float* beta, float eps, void* out, int32_t out_dtype, void* pre_out, int32_t pre_dtype,
+                                                  int64_t M, int32_t H, float p, uint64_t seed, uint64_t offset, const int32_t* row_id,
+                                                  modcr_stream_t stream);
 
 extern "C" int64_t modcr_linear_dropout_residual_ln_workspace(int32_t M, int32_t N, int32_t K, int32_t dtype) {
     (void)K; (void)dtype;
@@ -3082,6 +3086,17 @@ extern "C" int modcr_linear_dropout_residual_ln_fwd(const void* A, int64_t lda, 
                                                     void* out, void* pre_out, int32_t pre_dtype, int32_t M, int32_t N, int32_t K, float p,
                                                     uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes,
                                                     int32_t dtype, modcr_stream_t stream) {
+    return modcr_linear_dropout_residual_ln_rows_fwd(A, lda, W, bias, residual, gamma, beta, eps, out, pre_out, pre_dtype, M, N, K, p, seed, offset,
+                                                     nullptr, workspace, workspace_bytes, dtype, stream);
+}
+
+// the same over the live-row layout (row_id [M] int32, NULL = the entry above): the hidden-dropout counter of element (m, c) is
+// offset + row_id[m] * N + c, the counter the row has in the padded buffer
+extern "C" int modcr_linear_dropout_residual_ln_rows_fwd(const void* A, int64_t lda, const void* W, const float* bias,
+                                                         const void* residual, const float* gamma, const float* beta, float eps,
+                                                         void* out, void* pre_out, int32_t pre_dtype, int32_t M, int32_t N, int32_t K, float p,
+                                                         uint64_t seed, uint64_t offset, const int32_t* row_id, void* workspace,
+                                                         int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
     MODCR_REQUIRE(A && W && residual && gamma && beta && out && workspace, "linear_dropout_residual_ln_fwd: null pointer");
     MODCR_REQUIRE(M > 0 && N > 0 && K > 0 && lda >= K, "linear_dropout_residual_ln_fwd: bad shape");
     MODCR_REQUIRE(p >= 0.f && p < 1.f, "linear_dropout_residual_ln_fwd: p=%g out of [0, 1)", p);
@@ -3096,7 +3111,8 @@ extern "C" int modcr_linear_dropout_residual_ln_fwd(const void* A, int64_t lda, 
     const int32_t pre_dt = (dtype == MODCR_BF16 && !pre_out) ? MODCR_F16 : MODCR_F32;
     int rc = modcr_linear_fwd(A, lda, W, K, bias, nullptr, 0, 0, workspace, N, M, N, K, MODCR_ACT_NONE, dtype, pre_dt, stream);
     if (rc != MODCR_OK) return rc;
-    return modcr_dropout_residual_ln_fwd(workspace, pre_dt, residual, dtype, gamma, beta, eps, out, dtype, pre_out, pre_dtype, M, N, p, seed, offset, stream);
+    return modcr_dropout_residual_ln_rows_fwd(workspace, pre_dt, residual, dtype, gamma, beta, eps, out, dtype, pre_out, pre_dtype, M, N, p, seed, offset,
+                                              row_id, stream);
 }
 
 extern "C" int modcr_proj_residual_ln_fwd(const void* ctx, const void* wo, const float* bo, const void* x,

@@ -134,11 +134,15 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int64_t* ids, const
                                                        const float* gamma, const float* beta, float eps,
                                                        TO* out, int N, int T, int H, int64_t seq_stride,
                                                        int vocab, int max_pos, int type_vocab,
-                                                       uint64_t seed, uint64_t offset, uint32_t thr, float scale) {
+                                                       uint64_t seed, uint64_t offset, uint32_t thr, float scale,
+                                                       const int32_t* row_start, int64_t out_rows) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= (int64_t)N * T) return;
     const int n = (int)(row / T), t = (int)(row % T);
+    // live-row layout: sequence n's rows start at row row_start[n] of `out`; the dropout counters stay those of the padded position
+    const int64_t orow = row_start ? (int64_t)row_start[n] + t : (int64_t)n * seq_stride + t;
+    if (row_start && (orow < 0 || orow >= out_rows)) return;       // a bad table never writes outside the buffer
     int64_t id = ids[row];
     int64_t tt = tts ? tts[row] : 0;
     int64_t ps = pos_ids ? pos_ids[row] : t;
@@ -160,7 +164,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int64_t* ids, const
         }
     }
     const int64_t at = ((int64_t)n * seq_stride + t) * H;
-    ln_finish<TO>(v, nv, H, lane, gamma, beta, eps, out + at, seed, offset + (uint64_t)at, thr, scale);
+    ln_finish<TO>(v, nv, H, lane, gamma, beta, eps, out + orow * H, seed, offset + (uint64_t)at, thr, scale);
 }
 
 template <typename TO>
@@ -179,16 +183,22 @@ __global__ void cast_pad_kernel(const float* src, int64_t lds_, TO* dst, int64_t
 // a wave-per-row form with lane-contiguous 8-byte pieces -- 512 contiguous bytes per load instruction instead of 32-byte strides between
 // lanes -- measured the same 145 us: the pass is at the rate of its streams.)  Needs Kp % 8 == 0, even
 // source row stride (8-byte loads; the 2054-float rows are not 16-byte aligned) and a 16-byte aligned destination.
+// src_row (may be NULL): destination row m reads source row src_row[m]; an index outside [0, src_rows) gives a zero row (the
+// live region rows of a batch, and the filler rows behind them).
 __global__ __launch_bounds__(256) void cast_pad8_kernel(const float* __restrict__ src, int64_t lds_, bf16* __restrict__ dst, int64_t ldd, int64_t M,
-                                                        int K, int Kp) {
+                                                        int K, int Kp, const int32_t* __restrict__ src_row, int64_t src_rows) {
     const int cpr = Kp >> 3;                                         // 8-column chunks per row
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M * cpr) return;
     const int64_t m = i / cpr;
     const int k0 = (int)(i - m * cpr) * 8;
-    const float* sp = src + m * lds_ + k0;
+    const int64_t ms = src_row ? (int64_t)src_row[m] : m;
+    const float* sp = src + ms * lds_ + k0;
     float v[8];
-    if (k0 + 8 <= K) {
+    if (src_row && (ms < 0 || ms >= src_rows)) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = 0.f;
+    } else if (k0 + 8 <= K) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float2 t = *reinterpret_cast<const float2*>(sp + 2 * e);
@@ -757,7 +767,21 @@ extern "C" int modcr_embed_ln_dropout_fwd(const int64_t* input_ids, const int64_
                                           void* out, int32_t N, int32_t T, int32_t H, int64_t seq_stride,
                                           int32_t vocab, int32_t max_pos, int32_t type_vocab, int32_t out_dtype,
                                           float p, uint64_t seed, uint64_t offset, modcr_stream_t stream) {
+    return modcr_embed_ln_dropout_rows_fwd(input_ids, token_type_ids, position_ids, word, pos, type, gamma, beta, eps, out, N, T, H, seq_stride,
+                                           vocab, max_pos, type_vocab, out_dtype, p, seed, offset, nullptr, 0, stream);
+}
+
+// the same into the live-row layout: row t of sequence n goes to row row_start[n] + t of `out` [out_rows, H] (rows outside it are
+// not written); its dropout counter stays offset + (n * seq_stride + t) * H + c.  row_start NULL: the entry above, bit for bit.
+extern "C" int modcr_embed_ln_dropout_rows_fwd(const int64_t* input_ids, const int64_t* token_type_ids,
+                                               const int64_t* position_ids, const float* word, const float* pos,
+                                               const float* type, const float* gamma, const float* beta, float eps,
+                                               void* out, int32_t N, int32_t T, int32_t H, int64_t seq_stride,
+                                               int32_t vocab, int32_t max_pos, int32_t type_vocab, int32_t out_dtype,
+                                               float p, uint64_t seed, uint64_t offset, const int32_t* row_start, int64_t out_rows,
+                                               modcr_stream_t stream) {
     MODCR_REQUIRE(input_ids && word && pos && type && gamma && beta && out, "embed_ln_fwd: null pointer");
+    MODCR_REQUIRE(!row_start || (((uintptr_t)row_start & 3) == 0 && out_rows > 0), "embed_ln_fwd: row_start needs 4-byte alignment and out_rows > 0");
     MODCR_REQUIRE(N > 0 && T > 0 && (H % 4) == 0 && H <= 256 * MAXV, "embed_ln_fwd: bad shape");
     MODCR_REQUIRE(position_ids || T <= max_pos, "embed_ln_fwd: T=%d exceeds max_position_embeddings=%d", T, max_pos);
     MODCR_REQUIRE(p >= 0.f && p < 1.f, "embed_ln_fwd: p=%g out of [0, 1)", p);
@@ -767,10 +791,12 @@ extern "C" int modcr_embed_ln_dropout_fwd(const int64_t* input_ids, const int64_
     const float scale = 1.0f / (1.0f - p);
     if (out_dtype == MODCR_BF16)
         hipLaunchKernelGGL((embed_ln_kernel<bf16>), grid, blk, 0, st, input_ids, token_type_ids, position_ids,
-                           word, pos, type, gamma, beta, eps, (bf16*)out, N, T, H, seq_stride, vocab, max_pos, type_vocab, seed, offset, thr, scale);
+                           word, pos, type, gamma, beta, eps, (bf16*)out, N, T, H, seq_stride, vocab, max_pos, type_vocab, seed, offset, thr, scale,
+                           row_start, out_rows);
     else
         hipLaunchKernelGGL((embed_ln_kernel<float>), grid, blk, 0, st, input_ids, token_type_ids, position_ids,
-                           word, pos, type, gamma, beta, eps, (float*)out, N, T, H, seq_stride, vocab, max_pos, type_vocab, seed, offset, thr, scale);
+                           word, pos, type, gamma, beta, eps, (float*)out, N, T, H, seq_stride, vocab, max_pos, type_vocab, seed, offset, thr, scale,
+                           row_start, out_rows);
     return modcr_check_launch("embed_ln");
 }
 
@@ -790,12 +816,26 @@ extern "C" int modcr_cast_pad(const float* src, int64_t lds_, void* dst, int64_t
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(blocks_for(M * Kp, 256)), blk(256);
     if (dtype == MODCR_BF16 && (Kp % 8) == 0 && (lds_ % 2) == 0 && (ldd % 8) == 0 && modcr_aligned16(dst) && (((uintptr_t)src) & 7) == 0)
-        hipLaunchKernelGGL(cast_pad8_kernel, dim3(blocks_for(M * (Kp / 8), 256)), blk, 0, st, src, lds_, (bf16*)dst, ldd, M, K, Kp);
+        hipLaunchKernelGGL(cast_pad8_kernel, dim3(blocks_for(M * (Kp / 8), 256)), blk, 0, st, src, lds_, (bf16*)dst, ldd, M, K, Kp,
+                           (const int32_t*)nullptr, (int64_t)0);
     else if (dtype == MODCR_BF16)
         hipLaunchKernelGGL((cast_pad_kernel<bf16>), grid, blk, 0, st, src, lds_, (bf16*)dst, ldd, M, K, Kp);
     else
         hipLaunchKernelGGL((cast_pad_kernel<float>), grid, blk, 0, st, src, lds_, (float*)dst, ldd, M, K, Kp);
     return modcr_check_launch("cast_pad");
+}
+
+// modcr_cast_pad's bf16 form with gathered source rows: dst row m = the padded cast of src row src_row[m] (outside [0, src_rows): a
+// zero row) -- the operand of the region-embedding GEMM over the live region rows only.
+extern "C" int modcr_cast_pad_rows(const float* src, int64_t lds_, int64_t src_rows, void* dst, int64_t ldd, int64_t M, int32_t K, int32_t Kp,
+                                   const int32_t* src_row, modcr_stream_t stream) {
+    MODCR_REQUIRE(src && dst && src_row && M > 0 && src_rows > 0 && K > 0 && Kp >= K && ldd >= Kp && lds_ >= K, "cast_pad_rows: bad arguments");
+    MODCR_REQUIRE((Kp % 8) == 0 && (lds_ % 2) == 0 && (ldd % 8) == 0 && modcr_aligned16(dst) && (((uintptr_t)src) & 7) == 0 &&
+                      (((uintptr_t)src_row) & 3) == 0,
+                  "cast_pad_rows: needs Kp %% 8 == 0, an even source stride, ldd %% 8 == 0, an 8-byte aligned source and a 16-byte aligned destination");
+    hipLaunchKernelGGL(cast_pad8_kernel, dim3(blocks_for(M * (Kp / 8), 256)), dim3(256), 0, (hipStream_t)stream, src, lds_, (bf16*)dst, ldd, M, K,
+                       Kp, src_row, src_rows);
+    return modcr_check_launch("cast_pad_rows");
 }
 
 extern "C" int modcr_convert(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t n,
@@ -1246,10 +1286,12 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* x, T* out, int64_
 template <typename TX, typename TR, typename TO>
 __global__ __launch_bounds__(256) void layernorm_dropout_kernel(const TX* x, const TR* res, const float* gamma,
                                                                 const float* beta, float eps, TO* y, void* pre_out, int pre_f16, int64_t M, int H,
-                                                                uint64_t seed, uint64_t offset, uint32_t thr, float scale) {
+                                                                uint64_t seed, uint64_t offset, uint32_t thr, float scale, const int32_t* row_id) {
     const int lane = threadIdx.x & 63;
     const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= M) return;
+    // live-row layout: row m of these buffers is row row_id[m] of the padded buffer the mask is defined over (NULL: m itself)
+    const int64_t mc = (thr && row_id) ? (int64_t)row_id[m] : m;
     const int nv = (H + 255) / 256;
     float v[MAXV][4];
 #pragma unroll
@@ -1259,7 +1301,7 @@ __global__ __launch_bounds__(256) void layernorm_dropout_kernel(const TX* x, con
             Vec4<TX>::load(x + m * H + c, v[i]);
             float r[4] = {0.f, 0.f, 0.f, 0.f};
             if (res) Vec4<TR>::load(res + m * H + c, r);
-            if (thr) drop_apply4(v[i], seed, offset + (uint64_t)(m * H + c), thr, scale);
+            if (thr) drop_apply4(v[i], seed, offset + (uint64_t)(mc * H + c), thr, scale);
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[i][j] += r[j];
             // the pre-LayerNorm rows, for a backward pass that wants them (trainable layers)
@@ -1410,9 +1452,106 @@ extern "C" int modcr_rows_scatter_dropout(const void* src, void* dst, int64_t M,
     return modcr_check_launch("rows_scatter_dropout");
 }
 
+// The same pass into the live-row layout, driven by the destination: compact row i of dst stands for row p = row_id[i] of the
+// padded [*, gstride, H] buffer.  Where p is a region row (row0 <= p % gstride < row0 + rpg) it receives region j = p % gstride - row0
+// of sequence g = p / gstride under the counters of the PADDED position (offset + p * H + c); a text row is left to the embedding
+// pass; p < 0 (filler) gets zeros.  src holds the region rows either padded (src_start NULL: row g * rpg + j) or themselves back to
+// back (row src_start[g] + j).  groups = the number of sequences: a row_id behind them is skipped (src_start is not read there).
+namespace {
+template <typename T>
+__global__ __launch_bounds__(256) void rows_place_dropout_kernel(const T* src, int64_t src_rows, T* dst, const int32_t* __restrict__ row_id,
+                                                                const int32_t* __restrict__ src_start, int64_t groups, int64_t M, int H, int rpg,
+                                                                int64_t gstride, int row0, uint64_t seed, uint64_t offset, uint32_t thr, float scale) {
+    const int pieces = H >> 2;
+    const int64_t total = M * pieces;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t m = i / pieces;
+        const int c = (int)(i - m * pieces) * 4;
+        const int64_t p = row_id[m];
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (p >= 0) {
+            const int64_t g = p / gstride;
+            const int64_t j = p - g * gstride - row0;
+            if (g >= groups || j < 0 || j >= rpg) continue;
+            const int64_t sr = (src_start ? (int64_t)src_start[g] : g * rpg) + j;
+            if (sr < 0 || sr >= src_rows) continue;
+            Vec4<T>::load(src + sr * H + c, v);
+            if (thr) drop_apply4(v, seed, offset + (uint64_t)(p * H + c), thr, scale);
+        }
+        Vec4<T>::store(dst + m * H + c, v);
+    }
+}
+}  // namespace
+
+extern "C" int modcr_rows_place_dropout(const void* src, int64_t src_rows, void* dst, const int32_t* row_id, const int32_t* src_start,
+                                        int64_t groups, int64_t M, int32_t H, int32_t rows_per_group, int64_t group_stride, int32_t row0, int32_t dtype, float p,
+                                        uint64_t seed, uint64_t offset, modcr_stream_t stream) {
+    MODCR_REQUIRE(src && dst && row_id && M > 0 && src_rows > 0 && groups > 0 && H > 0 && (H % 4) == 0, "rows_place_dropout: bad arguments");
+    MODCR_REQUIRE(rows_per_group > 0 && row0 >= 0 && group_stride >= (int64_t)row0 + rows_per_group,
+                  "rows_place_dropout: rows_per_group=%d + row0=%d do not fit group_stride=%lld", rows_per_group, row0, (long long)group_stride);
+    MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "rows_place_dropout: dtype");
+    {
+        const uintptr_t am = dtype == MODCR_BF16 ? 7 : 15;
+        MODCR_REQUIRE(((uintptr_t)src & am) == 0 && ((uintptr_t)dst & am) == 0 && ((uintptr_t)row_id & 3) == 0 && ((uintptr_t)src_start & 3) == 0,
+                      "rows_place_dropout: src / dst must be %d-byte aligned, the tables 4-byte aligned", (int)am + 1);
+    }
+    MODCR_REQUIRE(p >= 0.f && p < 1.f, "rows_place_dropout: p=%g out of [0, 1)", p);
+    const int64_t total = M * (H / 4);
+    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    const uint32_t thr = p > 0.f ? drop_threshold(p) : 0u;
+    const float scale = 1.0f / (1.0f - p);
+    if (dtype == MODCR_BF16)
+        hipLaunchKernelGGL((rows_place_dropout_kernel<bf16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)src, src_rows, (bf16*)dst,
+                           row_id, src_start, groups, M, H, rows_per_group, group_stride, row0, seed, offset, thr, scale);
+    else
+        hipLaunchKernelGGL((rows_place_dropout_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)src, src_rows,
+                           (float*)dst, row_id, src_start, groups, M, H, rows_per_group, group_stride, row0, seed, offset, thr, scale);
+    return modcr_check_launch("rows_place_dropout");
+}
+
+// dst row i = src row idx[i] (16-byte pieces; an index outside [0, src_rows) gives a zero row): the two moves of the live-row
+// layout -- padded rows -> compact rows by the row_id table, compact rows -> the dense [N, k, H] block a consumer reads.
+namespace {
+__global__ __launch_bounds__(256) void rows_take_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, const int32_t* __restrict__ idx,
+                                                        int64_t M, int pieces, int64_t src_rows) {
+    const int64_t total = M * pieces;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t m = i / pieces;
+        const int c = (int)(i - m * pieces);
+        const int64_t r = idx[m];
+        dst[i] = (r >= 0 && r < src_rows) ? src[r * pieces + c] : uint4{0u, 0u, 0u, 0u};
+    }
+}
+}  // namespace
+
+extern "C" int modcr_rows_take(const void* src, int64_t src_rows, void* dst, const int32_t* idx, int64_t M, int32_t H, int32_t dtype,
+                               modcr_stream_t stream) {
+    MODCR_REQUIRE(src && dst && idx && M > 0 && src_rows > 0 && H > 0, "rows_take: bad arguments");
+    MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "rows_take: dtype");
+    const int64_t row_bytes = (int64_t)H * (dtype == MODCR_BF16 ? 2 : 4);
+    MODCR_REQUIRE((row_bytes & 15) == 0 && modcr_aligned16(src) && modcr_aligned16(dst) && ((uintptr_t)idx & 3) == 0,
+                  "rows_take: rows of whole 16-byte pieces, src / dst 16-byte aligned");
+    MODCR_REQUIRE(src != dst, "rows_take: in place is not supported");
+    const int pieces = (int)(row_bytes >> 4);
+    const int64_t total = M * pieces;
+    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    hipLaunchKernelGGL(rows_take_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint4*)src, (uint4*)dst, idx, M, pieces, src_rows);
+    return modcr_check_launch("rows_take");
+}
+
 extern "C" int modcr_dropout_residual_ln_fwd(const void* x, int32_t x_dtype, const void* residual, int32_t res_dtype, const float* gamma,
                                              const float* beta, float eps, void* out, int32_t out_dtype, void* pre_out, int32_t pre_dtype,
                                              int64_t M, int32_t H, float p, uint64_t seed, uint64_t offset, modcr_stream_t stream) {
+    return modcr_dropout_residual_ln_rows_fwd(x, x_dtype, residual, res_dtype, gamma, beta, eps, out, out_dtype, pre_out, pre_dtype, M, H, p, seed,
+                                              offset, nullptr, stream);
+}
+
+// the same over the live-row layout: the dropout counter of element (m, c) is offset + row_id[m] * H + c (row_id NULL: m)
+extern "C" int modcr_dropout_residual_ln_rows_fwd(const void* x, int32_t x_dtype, const void* residual, int32_t res_dtype, const float* gamma,
+                                                  const float* beta, float eps, void* out, int32_t out_dtype, void* pre_out, int32_t pre_dtype,
+                                                  int64_t M, int32_t H, float p, uint64_t seed, uint64_t offset, const int32_t* row_id,
+                                                  modcr_stream_t stream) {
+    MODCR_REQUIRE(((uintptr_t)row_id & 3) == 0, "dropout_residual_ln_fwd: row_id not 4-byte aligned");
     MODCR_REQUIRE(x && gamma && beta && out && M > 0 && (H % 4) == 0 && H <= 256 * MAXV, "dropout_residual_ln_fwd: bad arguments");
     MODCR_REQUIRE(!pre_out || pre_dtype == MODCR_F32 || pre_dtype == MODCR_F16, "dropout_residual_ln_fwd: pre_out is fp32 or IEEE half");
     const int pre_f16 = pre_dtype == MODCR_F16;
@@ -1424,7 +1563,7 @@ extern "C" int modcr_dropout_residual_ln_fwd(const void* x, int32_t x_dtype, con
     if (x_dtype == MODCR_F16) {             // fp16 sublayer output of the bf16 path
         MODCR_REQUIRE((!residual || res_dtype == MODCR_BF16) && out_dtype == MODCR_BF16, "dropout_residual_ln_fwd: fp16 rows need a bf16 residual and output");
         hipLaunchKernelGGL((layernorm_dropout_kernel<_Float16, bf16, bf16>), grid, blk, 0, st, (const _Float16*)x, (const bf16*)residual, gamma,
-                           beta, eps, (bf16*)out, pre_out, pre_f16, M, H, seed, offset, thr, scale);
+                           beta, eps, (bf16*)out, pre_out, pre_f16, M, H, seed, offset, thr, scale, row_id);
         return modcr_check_launch("dropout_residual_ln");
     }
     MODCR_REQUIRE(x_dtype == MODCR_F32, "dropout_residual_ln_fwd: x must be fp32 or fp16");
@@ -1432,7 +1571,7 @@ extern "C" int modcr_dropout_residual_ln_fwd(const void* x, int32_t x_dtype, con
 #define LND_CASE(K, TR, TO)                                                                                         \
     case K:                                                                                                        \
         hipLaunchKernelGGL((layernorm_dropout_kernel<float, TR, TO>), grid, blk, 0, st, (const float*)x, (const TR*)residual, gamma, beta, eps, \
-                           (TO*)out, pre_out, pre_f16, M, H, seed, offset, thr, scale);                            \
+                           (TO*)out, pre_out, pre_f16, M, H, seed, offset, thr, scale, row_id);                    \
         break;
     switch (key) {
         LND_CASE(0, bf16, bf16) LND_CASE(1, bf16, float) LND_CASE(2, float, bf16) LND_CASE(3, float, float)

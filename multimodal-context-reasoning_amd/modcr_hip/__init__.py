@@ -35,6 +35,8 @@ SIGNATURES = {
                                       _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
     "modcr_qkv_attn_opt_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32,
                                       _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _i32, _vp, _i64, _i32, _vp]),
+    "modcr_qkv_attn_rows_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _f32, _c.c_uint64,
+                                       _c.c_uint64, _i32, _i32, _vp]),
     "modcr_qkv_attn_bias_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "modcr_qkv_attn_bias_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i32,
                                        _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _i32, _vp, _i64, _i32, _vp]),
@@ -113,6 +115,15 @@ SIGNATURES = {
     "modcr_chunk_mean_q_bwd": (_i32, [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),
     "modcr_dropout": (_i32, [_vp, _vp, _i64, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp]),
     "modcr_dropout_residual_ln_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _f32, _vp, _i32, _vp, _i32, _i64, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp]),
+    "modcr_dropout_residual_ln_rows_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _f32, _vp, _i32, _vp, _i32, _i64, _i32, _f32, _c.c_uint64, _c.c_uint64,
+                                                  _vp, _vp]),
+    "modcr_linear_dropout_residual_ln_rows_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _c.c_uint64,
+                                                         _c.c_uint64, _vp, _vp, _i64, _i32, _vp]),
+    "modcr_rows_take": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp]),
+    "modcr_embed_ln_dropout_rows_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32,
+                                               _i64, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _vp]),
+    "modcr_rows_place_dropout": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i64, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp]),
+    "modcr_cast_pad_rows": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "modcr_add": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _vp]),
     "modcr_embedding_bwd_v": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _vp]),
     "modcr_embedding_bwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp]),
@@ -316,9 +327,10 @@ def linear_residual_ln(a, w, bias, residual, gamma, beta, eps, workspace=None, o
     return out.view(*residual.shape)
 
 
-def linear_dropout_residual_ln(a, w, bias, residual, gamma, beta, eps, p=0.0, seed=0, offset=0, out=None, pre_out=None):
+def linear_dropout_residual_ln(a, w, bias, residual, gamma, beta, eps, p=0.0, seed=0, offset=0, out=None, pre_out=None, row_id=None):
     """LN(dropout(a @ w.T + bias) + residual): BertSelfOutput / BertOutput as one C-ABI call (GEMM -> IEEE-half rows -> mask +
-    residual + LayerNorm pass).  p = 0: no dropout.  pre_out: fp32 or fp16 [M,N] tensor that receives the pre-LayerNorm rows."""
+    residual + LayerNorm pass).  p = 0: no dropout.  pre_out: fp32 or fp16 [M,N] tensor that receives the pre-LayerNorm rows.
+    row_id: int32 [M] device table of the live-row layout (LiveRows): row m carries the dropout counters of row row_id[m]."""
     dt = dt_of(w)
     _same_dtype("linear_dropout_residual_ln", w, a=a, residual=residual, out=out)
     k = a.shape[-1]
@@ -331,6 +343,14 @@ def linear_dropout_residual_ln(a, w, bias, residual, gamma, beta, eps, p=0.0, se
         out = torch.empty((m, n), dtype=a.dtype, device=a.device)
     if pre_out is not None and (pre_out.dtype not in (torch.float32, torch.float16) or pre_out.numel() != m * n or not pre_out.is_contiguous()):
         raise ValueError("linear_dropout_residual_ln: pre_out must be a contiguous fp32 or fp16 [M,N] tensor")
+    if row_id is not None:
+        if row_id.dtype != torch.int32 or row_id.numel() < m or not row_id.is_contiguous():
+            raise ValueError("linear_dropout_residual_ln: row_id must be a contiguous int32 table with an entry for each of the %d rows" % m)
+        _check(lib().modcr_linear_dropout_residual_ln_rows_fwd(_ptr(a2), k, _ptr(_contig(w)), _ptr(bias), _ptr(r2), _ptr(gamma), _ptr(beta), float(eps),
+                                                               _ptr(out), _ptr(pre_out), dt_of(pre_out) if pre_out is not None else F32, m, n, k, float(p),
+                                                               seed, offset, _ptr(row_id), _ptr(ws), need, dt, _stream()),
+               "modcr_linear_dropout_residual_ln_rows_fwd")
+        return out.view(*residual.shape)
     _check(lib().modcr_linear_dropout_residual_ln_fwd(_ptr(a2), k, _ptr(_contig(w)), _ptr(bias), _ptr(r2), _ptr(gamma), _ptr(beta), float(eps),
                                                       _ptr(out), _ptr(pre_out), dt_of(pre_out) if pre_out is not None else F32, m, n, k, float(p), seed, offset,
                                                       _ptr(ws), need, dt, _stream()),
@@ -383,8 +403,11 @@ ATTN_MAX_KEYS = 512
 
 def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=None, want_probs=False,
              align_map=None, align_t=0, num_heads=None, workspace=None, out=None, attn_dropout=None, lse=None, dump=None,
-             side_post_dropout=False, attn_bias=None, head_mask=None):
+             side_post_dropout=False, attn_bias=None, head_mask=None, row_start=None):
     """Fused QKV projection + attention.  x [N,S,H]; returns (ctx [N,S,H], probs or None).
+    row_start: int32 [N+1] device table of the live-row layout (LiveRows; modcr_qkv_attn_rows_fwd): x and ctx are [N,S,H] BUFFERS
+    whose first row_start[N] rows hold the sequences' live rows back to back.  No hist / probs / lse / dump / attn_bias there; a
+    shape the entry does not serve raises (ask qkv_attn_route(..., rows=True) first).
     attn_bias: any float tensor broadcastable to [N, A, S, P+S], ADDED to the scores before the softmax (the reference's additive
     attention_mask, soft biases, -inf entries); head_mask: [A], [1,A,1,1], [N,A] or [N,A,1,1], multiplies the probabilities of a
     head after softmax and dropout.  Either one sends the call to modcr_qkv_attn_bias_fwd (the streaming core with a float bias,
@@ -398,6 +421,19 @@ def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=N
     x = _contig(x)
     n, s, h = x.shape
     a = num_heads
+    if row_start is not None:
+        if hist is not None or want_probs or lse is not None or dump is not None or attn_bias is not None or head_mask is not None:
+            raise ValueError("qkv_attn: the live-row layout takes no hist, probabilities, lse, dump, attn_bias or head_mask")
+        if row_start.dtype != torch.int32 or row_start.numel() != n + 1 or not row_start.is_contiguous():
+            raise ValueError("qkv_attn: row_start must be a contiguous int32 [N + 1] tensor")
+        ctx = torch.empty_like(x) if out is None else out
+        km = _contig(key_mask, torch.float32) if key_mask is not None else None
+        ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
+        _check(lib().modcr_qkv_attn_rows_fwd(_ptr(x), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(km), _ptr(mask_bits), _ptr(chunk_id),
+                                             0 if chunk_id is None else chunk_id.shape[1], _ptr(ctx), _ptr(align_map), align_t, _ptr(row_start),
+                                             n, s, h, a, float(ap), seed, off, ATTN_SIDE_POST_DROPOUT if side_post_dropout else 0, dt, _stream()),
+               "modcr_qkv_attn_rows_fwd")
+        return ctx, None
     p = 0 if hist is None else hist.shape[1]
     if p + s > ATTN_MAX_KEYS:
         raise ValueError("qkv_attn: P + S = %d keys exceeds the %d-key limit of the attention forward" % (p + s, ATTN_MAX_KEYS))
@@ -513,18 +549,20 @@ def additive_mask_is_binary(mask):
 # modcr_qkv_attn_route: kernel families (MODCR_ATTN_ROUTE_*) and the bits of `present` (MODCR_ATTN_HAS_*)
 ATTN_ROUTE_FAMILIES = {1: "tile", 2: "tile4", 3: "long_bf16", 4: "f32", 5: "long_f32"}
 ATTN_HAS_BIAS, ATTN_HAS_DENSE_MASK, ATTN_HAS_CHUNK_ID, ATTN_HAS_PROBS, ATTN_HAS_ALIGN_MAP, ATTN_HAS_LSE, ATTN_HAS_QKV_DUMP = 1, 2, 4, 8, 16, 32, 64
+ATTN_HAS_ROW_START = 128
 AttnRoute = collections.namedtuple("AttnRoute", "rc family inst concat message")
 
 
 def qkv_attn_route(n, s, p, h, a, dtype=BF16, bias=False, dense=False, chunk_t=0, probs=False, align_t=0, lse=False, dump=False,
-                   attn_p=0.0, flags=0, workspace_bytes=None, workspace_aligned=True):
+                   attn_p=0.0, flags=0, workspace_bytes=None, workspace_aligned=True, rows=False):
     """The route the attention forward takes for these arguments (modcr_qkv_attn_route; nothing is launched or read):
     AttnRoute(rc = the call's return code, family = a name of ATTN_ROUTE_FAMILIES, inst = the five numbers that pick the
     instantiation, concat, message = the refusal's text).  bias: the call goes to modcr_qkv_attn_bias_fwd; chunk_t / align_t > 0:
-    chunk_id / align_map are given; workspace_bytes None: what qkv_attn supplies for the shape."""
+    chunk_id / align_map are given; workspace_bytes None: what qkv_attn supplies for the shape; rows: the call is
+    modcr_qkv_attn_rows_fwd (the live-row layout)."""
     present = ((ATTN_HAS_BIAS if bias else 0) | (ATTN_HAS_DENSE_MASK if dense else 0) | (ATTN_HAS_CHUNK_ID if chunk_t else 0) |
                (ATTN_HAS_PROBS if probs else 0) | (ATTN_HAS_ALIGN_MAP if align_t else 0) | (ATTN_HAS_LSE if lse else 0) |
-               (ATTN_HAS_QKV_DUMP if dump else 0))
+               (ATTN_HAS_QKV_DUMP if dump else 0) | (ATTN_HAS_ROW_START if rows else 0))
     if workspace_bytes is None:
         workspace_bytes = (lib().modcr_qkv_attn_bias_workspace if bias else lib().modcr_qkv_attn_workspace)(n, s, p, h, dtype)
     info = (_i32 * 7)()
@@ -580,6 +618,181 @@ def rows_scatter_dropout(src, dst, row0, dropout=None):
     _check(lib().modcr_rows_scatter_dropout(_ptr(src), _ptr(dst), n * r, h, r, s, row0, dt_of(dst), float(p), seed, off, _stream()),
            "modcr_rows_scatter_dropout")
     return dst
+
+
+def embed_ln_rows(input_ids, token_type_ids, position_ids, word, pos, typ, gamma, beta, eps, out, seq_stride, row_start, dropout=None):
+    """embed_ln into the live-row layout: row t of sequence n -> row row_start[n] + t of out [rows, H]; dropout counters = flat
+    indices of the padded [N, seq_stride, H] buffer (modcr_embed_ln_dropout_rows_fwd)"""
+    n, t = input_ids.shape
+    h = word.shape[1]
+    assert out.dim() == 2 and out.is_contiguous() and row_start.dtype == torch.int32 and row_start.numel() >= n
+    p, seed, off = dropout if dropout is not None else (0.0, 0, 0)
+    _check(lib().modcr_embed_ln_dropout_rows_fwd(_ptr(_contig(input_ids)), _ptr(_contig(token_type_ids)),
+                                                 _ptr(_contig(position_ids)), _ptr(word), _ptr(pos), _ptr(typ), _ptr(gamma),
+                                                 _ptr(beta), float(eps), _ptr(out), n, t, h, seq_stride, word.shape[0],
+                                                 pos.shape[0], typ.shape[0], dt_of(out), float(p), seed, off, _ptr(row_start), out.shape[0],
+                                                 _stream()), "modcr_embed_ln_dropout_rows_fwd")
+    return out
+
+
+def rows_place_dropout(src, dst, row_id, r, s, row0, dropout=None, src_start=None):
+    """the region rows of a live-row layout (modcr_rows_place_dropout): dst [M, H] compact rows, row_id int32 [M] their rows in the
+    padded [N, s, H] buffer; region j of sequence g comes from src row g r + j (src_start None) or src_start[g] + j.  Text rows
+    (p % s < row0) are left alone, filler rows (row_id < 0) are zeroed.  dropout = (p, seed, offset): counters of the padded buffer."""
+    m, h = dst.shape
+    assert dst.is_contiguous() and src.is_contiguous() and src.dim() == 2 and src.dtype == dst.dtype and src.shape[1] == h
+    assert row_id.dtype == torch.int32 and row_id.is_contiguous() and row_id.numel() == m and row0 + r <= s
+    assert src_start is None or (src_start.dtype == torch.int32 and src_start.is_contiguous())
+    groups = src.shape[0] // r if src_start is None else src_start.numel() - 1      # (src_start = a row_start table [N + 1])
+    p, seed, off = dropout if dropout is not None else (0.0, 0, 0)
+    _check(lib().modcr_rows_place_dropout(_ptr(src), src.shape[0], _ptr(dst), _ptr(row_id), _ptr(src_start), groups, m, h, r, s, row0, dt_of(dst),
+                                          float(p), seed, off, _stream()), "modcr_rows_place_dropout")
+    return dst
+
+
+def cast_pad_rows(src, kp, src_row):
+    """fp32 [rows, K] -> bf16 [M, kp]: row m = the zero-padded cast of src row src_row[m] (int32 [M]; outside the source: zeros)"""
+    k = src.shape[-1]
+    s2 = _contig(src.reshape(-1, k), torch.float32)
+    assert src_row.dtype == torch.int32 and src_row.is_contiguous()
+    dst = torch.empty((src_row.numel(), kp), dtype=torch.bfloat16, device=src.device)
+    _check(lib().modcr_cast_pad_rows(_ptr(s2), k, s2.shape[0], _ptr(dst), kp, dst.shape[0], k, kp, _ptr(src_row), _stream()), "modcr_cast_pad_rows")
+    return dst
+
+
+def rows_take(src, idx, out=None):
+    """out[i] = src[idx[i]] over rows (modcr_rows_take): src [rows, H] contiguous bf16 / fp32, idx int32 [M] on the device; an index
+    outside [0, rows) gives a zero row.  out: contiguous [M, H] (default: a new tensor)."""
+    assert src.dim() == 2 and src.is_contiguous() and idx.dtype == torch.int32 and idx.is_contiguous()
+    m, h = idx.numel(), src.shape[1]
+    if out is None:
+        out = torch.empty((m, h), dtype=src.dtype, device=src.device)
+    assert out.is_contiguous() and out.dtype == src.dtype and out.numel() == m * h
+    _check(lib().modcr_rows_take(_ptr(src), src.shape[0], _ptr(out), _ptr(idx), m, h, dt_of(src), _stream()), "modcr_rows_take")
+    return out
+
+
+# ---- the live-row layout of a frozen encoder pass (include/modcr_hip.h: modcr_qkv_attn_rows_fwd) ----------------------------------
+LIVE_ROW_ALIGN = 256     # launches use the live-row count rounded up to this (the fast GEMM routes need M % 256 == 0), capped at the capacity
+
+LiveLayout = collections.namedtuple("LiveLayout", "seq_len m_live m_launch capacity row_start row_id take")
+# one layout before its tables are on a device: the LiveLayout fields, with every table as an (offset, length) slice of LiveRows.host
+_LayoutSpec = collections.namedtuple("_LayoutSpec", "seq_len m_live m_launch capacity row_start row_id take")
+
+
+def _round_rows(m, capacity):
+    return min((m + LIVE_ROW_ALIGN - 1) // LIVE_ROW_ALIGN * LIVE_ROW_ALIGN, capacity)
+
+
+class LiveRows(object):
+    """Host-built tables of the live-row layout for one batch of N sequences of T text rows + R region slots of which sequence n
+    fills the first nreg[n] (input_mask[n, T:T+R] = 1...1 0...0).  Four layouts, each a LiveLayout of int32 tables:
+      full  one [text | regions] pass: L_n = T + nreg[n] rows of S = T + R (all S rows where nreg[n] = 0: see `_pass_rows`)
+      img   the image-only [CLS | regions] pass: L_n = 1 + nreg[n] rows of S = 1 + R
+      pair  BertImgModel.forward_pair's buffer of N (T + R) + N (1 + R) rows: the full pass's live rows, then the image-only pass's
+      reg   the region rows the region pipeline computes, back to back: the first (L_n of full) - T of the R slots of sequence n
+    row_start [N + 1]: first compact row of every sequence (full / img: relative to the pass's first row; pair has none);
+    row_id [m_launch]: the flat row of the padded buffer each compact row stands for (-1 for the filler rows up to m_launch; reg:
+    the row of the [N R, D] region features);
+    take[k] [N k]: the compact row of (n, j), j < k -- k = T (the text rows the heads read) and k = 1 ([CLS]); pair: take[T] and
+    take[1] address the full pass, take["img"] [N] the image-only pass's [CLS] rows.
+    All tables are slices of ONE int32 array (`host`, numpy), copied to the device once (`to`): no device -> host traffic."""
+
+    def __init__(self, nreg, t, r):
+        import numpy as np
+        nreg = np.asarray(nreg, dtype=np.int64).reshape(-1)
+        n = int(nreg.shape[0])
+        if n == 0 or t < 1 or r < 1 or nreg.min() < 0 or nreg.max() > r:
+            raise ValueError("LiveRows: need N > 0 region counts in [0, R] (T=%d, R=%d)" % (t, r))
+        if n * (t + r) + n * (1 + r) >= 2 ** 31:
+            raise ValueError("LiveRows: the row tables are int32")
+        self.n, self.t, self.r, self.nreg = n, int(t), int(r), nreg
+        self._parts, self._specs = [], {}
+        rs_full, rid_full = self._pass_rows(t)
+        rs_img, rid_img = self._pass_rows(1)
+        m_full, m_img = int(rs_full[n]), int(rs_img[n])
+        take_t = (rs_full[:n, None] + np.arange(t)[None, :]).reshape(-1)
+        full = self._add("full", t + r, m_full, n * (t + r), rs_full, rid_full, {t: take_t, 1: rs_full[:n]})
+        self._add("img", 1 + r, m_img, n * (1 + r), rs_img, rid_img, {1: rs_img[:n]})
+        pair = self._add("pair", t + r, m_full + m_img, n * (t + r) + n * (1 + r), None, np.concatenate([rid_full, n * (t + r) + rid_img]),
+                         {"img": m_full + rs_img[:n]})
+        pair.take.update({t: full.take[t], 1: full.take[1]})
+        # the region rows of the full pass's layout (it keeps at least the image-only pass's regions of every sequence)
+        lreg = np.diff(rs_full) - t
+        rs_reg = np.zeros(n + 1, np.int64)
+        rs_reg[1:] = np.cumsum(lreg)
+        seq = np.repeat(np.arange(n, dtype=np.int64), lreg)
+        self._add("reg", r, int(rs_reg[n]), n * r, rs_reg, seq * r + (np.arange(int(rs_reg[n]), dtype=np.int64) - rs_reg[seq]), {})
+        self.host = np.concatenate(self._parts)
+        del self._parts
+        self.blob = None
+        self.full = self.img = self.pair = self.reg = None
+
+    def _pass_rows(self, k_text):
+        """(row_start, row_id) of one pass over [k_text text rows | R region slots].
+        A [text | regions] sequence WITHOUT a live region keeps all its rows: under the phase masks a text row whose chunk-mask row is
+        empty (padded text) then has every key hidden, its softmax is the uniform one over all S keys -- padded regions included --
+        and padded text rows are read by the heads.  (With a live region such a row sees exactly the live regions; the image-only
+        pass always has [CLS] as a live key.)"""
+        import numpy as np
+        n, r, nreg = self.n, self.r, self.nreg
+        ln = k_text + (np.where(nreg == 0, r, nreg) if k_text > 1 else nreg)
+        rs = np.zeros(n + 1, np.int64)
+        rs[1:] = np.cumsum(ln)
+        seq = np.repeat(np.arange(n, dtype=np.int64), ln)
+        return rs, seq * (k_text + r) + (np.arange(int(rs[n]), dtype=np.int64) - rs[seq])
+
+    def _put(self, a):
+        import numpy as np
+        off = sum(p_.shape[0] for p_ in self._parts)
+        self._parts.append(np.ascontiguousarray(a, dtype=np.int32).reshape(-1))
+        return (off, self._parts[-1].shape[0])
+
+    def _add(self, name, seq_len, m_live, capacity, row_start, row_id, take):
+        import numpy as np
+        m_launch = _round_rows(m_live, capacity)
+        rid = np.full(m_launch, -1, np.int64)
+        rid[:m_live] = row_id
+        spec = _LayoutSpec(seq_len, m_live, m_launch, capacity, None if row_start is None else self._put(row_start), self._put(rid),
+                           {k: self._put(v) for k, v in take.items()})
+        self._specs[name] = spec
+        return spec
+
+    def to(self, device, non_blocking=True):
+        """copies the tables to `device` (one transfer, from pinned memory when that is a GPU, so that it does not hold the host)
+        and builds the LiveLayouts over the device array; returns self"""
+        host = torch.from_numpy(self.host)
+        if torch.device(device).type == "cuda":
+            host = host.pin_memory()
+        self.blob = host.to(device, non_blocking=non_blocking)
+        cut = lambda ol: None if ol is None else self.blob[ol[0]:ol[0] + ol[1]]
+        for name, sp in self._specs.items():
+            setattr(self, name, LiveLayout(sp.seq_len, sp.m_live, sp.m_launch, sp.capacity, cut(sp.row_start), cut(sp.row_id),
+                                           {k: cut(v) for k, v in sp.take.items()}))
+        return self
+
+    def matches(self, n, t, r, device):
+        return self.blob is not None and (self.n, self.t, self.r) == (n, t, r) and self.blob.device == device
+
+    @property
+    def dead_rows(self):
+        return self._specs["pair"].capacity - self._specs["pair"].m_live
+
+
+def live_rows_from_mask(input_mask, t):
+    """LiveRows of a HOST input_mask [N, T + R] (0/1), or None when the layout does not apply: a device tensor (reading it would
+    stall the stream), no region columns, a region part that is not in prefix form 1...1 0...0, or a dead [CLS] (then a query row
+    could have every key hidden, and the padded route's uniform softmax over padded keys would matter)."""
+    if not torch.is_tensor(input_mask) or input_mask.is_cuda or input_mask.dim() != 2 or input_mask.shape[1] <= t or t < 1:
+        return None
+    m = input_mask.detach().to(torch.float32).numpy()
+    img = m[:, t:]
+    nreg = (img != 0).sum(axis=1)
+    import numpy as np
+    want = (np.arange(img.shape[1])[None, :] < nreg[:, None]).astype(np.float32)
+    if not np.array_equal(img, want) or not np.all(m[:, 0] == 1):
+        return None
+    return LiveRows(nreg, t, img.shape[1])
 
 
 def cast_pad(src, kp, dtype):
@@ -822,11 +1035,14 @@ def qkv_attn_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, mask_bits=Non
     return dx
 
 
-def add(a, b, out_dtype=F32):
-    """a (fp32) + b (fp32 or bf16) -> out_dtype"""
+def add(a, b, out_dtype=F32, out=None):
+    """a (fp32) + b (fp32 or bf16) -> out_dtype (out: a contiguous tensor of that dtype and a's size to write into)"""
     a = _contig(a, torch.float32)
     b = _contig(b)
-    out = torch.empty(a.shape, dtype=torch_dtype(out_dtype), device=a.device)
+    if out is None:
+        out = torch.empty(a.shape, dtype=torch_dtype(out_dtype), device=a.device)
+    elif out.dtype != torch_dtype(out_dtype) or out.numel() != a.numel() or not out.is_contiguous():
+        raise ValueError("add: out must be a contiguous %s tensor of %d elements" % (torch_dtype(out_dtype), a.numel()))
     _check(lib().modcr_add(_ptr(a), _ptr(b), dt_of(b), _ptr(out), out_dtype, a.numel(), _stream()), "modcr_add")
     return out
 

@@ -108,10 +108,20 @@ class BertEmbeddings(nn.Module):
         self.register_buffer("position_ids", torch.arange(config.max_position_embeddings).expand((1, -1)))
         self.eps = config.layer_norm_eps
 
-    def forward(self, input_ids=None, token_type_ids=None, position_ids=None, out=None, dtype=torch.bfloat16, dropout=None):
-        """dropout = (p, seed, offset) of the caller's ONE dropout over `out` (text rows here, region rows by embed_regions): a_bert:210"""
+    def forward(self, input_ids=None, token_type_ids=None, position_ids=None, out=None, dtype=torch.bfloat16, dropout=None,
+                row_start=None, seq_stride=None):
+        """dropout = (p, seed, offset) of the caller's ONE dropout over `out` (text rows here, region rows by embed_regions): a_bert:210
+        row_start (int32 [N], with seq_stride): `out` is a [rows, H] buffer in the live-row layout (mh.LiveRows) -- sequence n's rows
+        go to row_start[n] + t under the dropout counters of the padded [N, seq_stride, H] buffer."""
         n, t = input_ids.shape
         h = self.word_embeddings.weight.shape[1]
+        if row_start is not None:
+            if position_ids is not None and position_ids.shape[0] != n:
+                position_ids = position_ids.expand(n, t)
+            return mh.embed_ln_rows(input_ids, token_type_ids, position_ids, self.word_embeddings.weight.detach(),
+                                    self.position_embeddings.weight.detach(), self.token_type_embeddings.weight.detach(),
+                                    self.LayerNorm.weight.detach(), self.LayerNorm.bias.detach(), self.eps, out, seq_stride, row_start,
+                                    dropout=dropout)
         if out is None:
             out = torch.empty((n, t, h), dtype=dtype, device=input_ids.device)
         if position_ids is not None and position_ids.shape[0] != n:
@@ -148,10 +158,15 @@ class BertSelfAttention(nn.Module):
                                                 self.query.bias, self.key.bias, self.value.bias], build)
 
 
-def _dropout_residual_ln(hidden_states, w, b, input_tensor, gamma, beta, eps, p, out=None):
+def _dropout_residual_ln(hidden_states, w, b, input_tensor, gamma, beta, eps, p, out=None, live=None):
     """LN(dropout(dense(h)) + input): training-mode BertSelfOutput / BertOutput (a_bert:369-373, :446-451; dropout is
     live inside the no_grad encoders under model.train()).  One C-ABI call: GEMM -> IEEE-half rows (fp32 on the
-    parity path) -> counter-based mask + residual + LayerNorm pass."""
+    parity path) -> counter-based mask + residual + LayerNorm pass.
+    live = (row_id table, rows of the padded buffer): the rows are a live-row layout (mh.LiveRows) -- the call consumes the
+    padded buffer's counters and every row takes the ones of its padded position, i.e. the keep decisions of the padded call."""
+    if live is not None:
+        seed, off = mh.DROPOUT.take(live[1] * input_tensor.shape[-1])
+        return mh.linear_dropout_residual_ln(hidden_states, w, b, input_tensor, gamma, beta, eps, p, seed, off, out=out, row_id=live[0])
     seed, off = mh.DROPOUT.take(input_tensor.numel())
     return mh.linear_dropout_residual_ln(hidden_states, w, b, input_tensor, gamma, beta, eps, p, seed, off, out=out)
 
@@ -167,12 +182,12 @@ class BertSelfOutput(nn.Module):
         self.eps = config.layer_norm_eps
         self._cache = PackCache()
 
-    def forward(self, hidden_states, input_tensor, workspace=None):
+    def forward(self, hidden_states, input_tensor, workspace=None, live=None):
         dt = hidden_states.dtype
         w, b = packed_linear(self._cache, ("w", dt), self.dense, dt)
         g, be = packed_ln(self._cache, "ln", self.LayerNorm)
         if self.training and self.dropout.p > 0.0:
-            return _dropout_residual_ln(hidden_states, w, b, input_tensor, g, be, self.eps, self.dropout.p)
+            return _dropout_residual_ln(hidden_states, w, b, input_tensor, g, be, self.eps, self.dropout.p, live=live)
         return mh.linear_dropout_residual_ln(hidden_states, w, b, input_tensor, g, be, self.eps)
 
 
@@ -203,12 +218,12 @@ class BertOutput(nn.Module):
         self.eps = config.layer_norm_eps
         self._cache = PackCache()
 
-    def forward(self, hidden_states, input_tensor, workspace=None, out=None):
+    def forward(self, hidden_states, input_tensor, workspace=None, out=None, live=None):
         dt = hidden_states.dtype
         w, b = packed_linear(self._cache, ("w", dt), self.dense, dt)
         g, be = packed_ln(self._cache, "ln", self.LayerNorm)
         if self.training and self.dropout.p > 0.0:
-            return _dropout_residual_ln(hidden_states, w, b, input_tensor, g, be, self.eps, self.dropout.p, out=out)
+            return _dropout_residual_ln(hidden_states, w, b, input_tensor, g, be, self.eps, self.dropout.p, out=out, live=live)
         # eval mode: the same two launches with p = 0 (the row pass adds the residual: see modcr_linear_dropout_residual_ln_fwd)
         return mh.linear_dropout_residual_ln(hidden_states, w, b, input_tensor, g, be, self.eps, out=out)
 

@@ -32,9 +32,10 @@ class CaptionBertSelfAttention(BertSelfAttention):
         self.side_post_dropout = bool(getattr(config, "modcr_align_map_post_dropout", True))
 
     def hip_forward(self, x, key_mask=None, mask_bits=None, hist=None, chunk_id=None, want_probs=False,
-                    align_map=None, align_t=0, workspace=None, out=None, attn_bias=None, head_mask=None):
+                    align_map=None, align_t=0, workspace=None, out=None, attn_bias=None, head_mask=None, row_start=None):
         """attn_bias / head_mask (instead of key_mask / mask_bits): an additive float mask broadcastable to [N,A,S,L] and a
-        per-head multiplier of the probabilities, mh.qkv_attn's general route."""
+        per-head multiplier of the probabilities, mh.qkv_attn's general route.  row_start: x and out are [N,S,H] buffers in the
+        live-row layout (mh.LiveRows); the attention-dropout counters are those of the dense call."""
         w, b = self.packed_qkv(x.dtype)
         drop = None
         if self.training and self.dropout.p > 0.0:      # nn.Dropout on the probabilities (modeling_bert.py:69), training mode
@@ -55,7 +56,7 @@ class CaptionBertSelfAttention(BertSelfAttention):
                            want_probs=want_probs, align_map=align_map, align_t=align_t,
                            num_heads=self.num_attention_heads, workspace=workspace, out=out, attn_dropout=drop,
                            side_post_dropout=self.side_post_dropout and drop is not None and (want_probs or align_map is not None),
-                           attn_bias=attn_bias, head_mask=head_mask)
+                           attn_bias=attn_bias, head_mask=head_mask, **({} if row_start is None else {"row_start": row_start}))
 
     def forward(self, hidden_states, attention_mask, head_mask=None, history_state=None):
         n, s, _ = hidden_states.shape

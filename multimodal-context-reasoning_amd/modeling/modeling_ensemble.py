@@ -68,7 +68,9 @@ class Abstract_Specific(nn.Module):
     def forward(self, image, text, roberta_input_ids, roberta_token_type_ids, roberta_attention_mask, input_ids,
                 img_feat, input_mask=None, token_type_ids=None, position_ids=None, head_mask=None,
                 encoder_history_states=None, offsets=None, chunk_attention_mask=None, gather_index=None,
-                label=None, align_pos=None, total_label=None):
+                label=None, align_pos=None, total_label=None, live_rows=None):
+        # live_rows (not in the reference's signature): the batch's mh.LiveRows tables (train_utils.batch_to_device builds them
+        # from the host input_mask) -- the frozen encoder passes then skip the padded region rows (modeling_transfomres.LIVE_ROWS)
         n = input_ids.size(0)
         ag.set_exact(not self.mapping_network_vision.bf16)
         from .modeling_transfomres import ImgEmbedMixin, PACK_SHORT
@@ -87,11 +89,14 @@ class Abstract_Specific(nn.Module):
             if pair is not None:
                 # this image-only pass and calec's full pass run the same frozen encoder: one batch of rows through the
                 # token-wise blocks, attention per pass (BertImgModel.forward_pair)
-                global_outputs, image_features_ = pair(input_ids, token_type_ids, input_mask, img_feat, img_attention_mask)
+                global_outputs, image_features_ = pair(input_ids, token_type_ids, input_mask, img_feat, img_attention_mask,
+                                                       **({} if live_rows is None else {"live_rows": live_rows}))
             else:
                 # (opt-in, config.modcr_last_layer_rows: only the [CLS] row of this pass is read, two lines below)
                 lr = ({"modcr_last_rows": 1} if getattr(getattr(self.calec.global_enc, "config", None), "modcr_last_layer_rows", False)
                       and not (getattr(self.calec.global_enc, "trainable", False) and torch.is_grad_enabled()) else {})
+                if live_rows is not None and not lr and not (getattr(genc, "trainable", False) and grad_outside) and hasattr(genc, "live_route"):
+                    lr = {"live_rows": live_rows}
                 image_features_ = self.calec.global_enc(input_ids[:, :1], img_feats=img_feat,
                                                         attention_mask=img_attention_mask, position_ids=None,
                                                         token_type_ids=None, head_mask=None, encoder_history_states=None, **lr)
@@ -104,7 +109,8 @@ class Abstract_Specific(nn.Module):
             position_ids=position_ids, head_mask=head_mask, encoder_history_states=encoder_history_states,
             offsets=offsets, chunk_attention_mask=chunk_attention_mask, gather_index=gather_index,
             align_pos=align_pos, total_label=total_label, abstract_hidden_states=None,
-            **({"global_outputs": global_outputs} if global_outputs is not None else {}))
+            **({"global_outputs": global_outputs} if global_outputs is not None else {}),
+            **({"live_rows": live_rows} if live_rows is not None else {}))
 
         Alignment_prompt = self.mapping_network_alignment(CALeC_encoder_output).unsqueeze(1).view(n, 5, 1024)
         align_mask = input_mask[:, :1].repeat(1, 5)

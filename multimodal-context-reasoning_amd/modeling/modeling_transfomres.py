@@ -14,6 +14,34 @@ from .modeling_bert import CaptionBertAttention, split_additive_mask
 
 FFN_SPLIT = 1      # tools may raise it for an A/B run: FFN row chunks per layer
 PACK_SHORT = 64    # sequences of at most this many rows are packed several to an attention row block (0 = off)
+# The frozen encoders' internal route (Abstract_Specific -> ChunkAlign -> the two encoder classes, when the batch carries
+# mh.LiveRows tables) runs every layer over the LIVE rows only: padded image-region rows are keys that every mask hides and
+# queries that nobody reads, about a quarter of all rows of a PMR batch.  Live rows carry the padded route's values bit for bit
+# (same kernels, same operands, the dropout counters of their padded positions).  The reference-signature forward()s without
+# `live_rows` compute and return every row as before.  Tools and tests clear the switch for an A/B run.
+LIVE_ROWS = True
+
+
+def live_attn_supported(n, s, h, a, attn_p, modes, align_t=0, chunk_t=0):
+    """True when modcr_qkv_attn_rows_fwd serves the attention calls of a pass over sequences of s rows: modes = the subset of
+    (1 key mask, 2 dense mask, 3 dense mask + chunk ids + align map) the pass launches"""
+    for mode in modes:
+        r = mh.qkv_attn_route(n, s, 0, h, a, dense=mode >= 2, chunk_t=chunk_t if mode == 3 else 0, align_t=align_t if mode == 3 else 0,
+                              attn_p=attn_p, flags=mh.ATTN_SIDE_POST_DROPOUT if (mode == 3 and attn_p > 0.0) else 0, rows=True)
+        if r.rc != 0:
+            return False
+    return True
+
+
+def live_buffers(lay, h, dtype, device):
+    """(x, ctx) for a pass over the live-row layout `lay`: two [capacity, H] buffers (the padded size, so that the allocator sees the
+    same sizes every step) of which the first lay.m_launch rows are used.  x is for the embedding passes to fill (embed_live); ctx
+    is the layers' attention output buffer, its filler rows zeroed once."""
+    x = torch.empty((lay.capacity, h), dtype=dtype, device=device)
+    ctx = torch.empty_like(x)
+    if lay.m_launch > lay.m_live:
+        ctx[lay.m_live:lay.m_launch].zero_()
+    return x, ctx
 
 
 class CaptionBertLayer(nn.Module):
@@ -62,6 +90,21 @@ class CaptionBertLayer(nn.Module):
                 self.output(self.intermediate(ac), ac, pre, out=y[c * rows:(c + 1) * rows])
             y = y.view(n, s, h)
         return y, probs
+
+    def hip_forward_live(self, x, ctx, lay, passes):
+        """One layer over a live-row layout (mh.LiveLayout `lay`).  x, ctx: [capacity, H] buffers (compact_rows); passes: one
+        (first row, sequences, rows per sequence, row_start table, attention keywords) per attention launch.  The token-wise
+        blocks run once over the first lay.m_launch rows, with the hidden-dropout counters of the padded buffer.  Returns the new
+        [capacity, H] buffer."""
+        h = x.shape[1]
+        for r0, n, s, row_start, kw in passes:
+            self.attention.self.hip_forward(x[r0:r0 + n * s].view(n, s, h), out=ctx[r0:r0 + n * s].view(n, s, h), row_start=row_start, **kw)
+        m = lay.m_launch
+        live = (lay.row_id, lay.capacity)
+        a = self.attention.output(ctx[:m], x[:m], live=live)
+        y = torch.empty_like(x)
+        self.output(self.intermediate(a), a, out=y[:m], live=live)
+        return y
 
     def forward(self, hidden_states, attention_mask, head_mask=None, history_state=None):
         n, s, _ = hidden_states.shape
@@ -153,6 +196,24 @@ class CaptionBertEncoder(nn.Module):
             outputs = outputs + (all_att,)
         return outputs
 
+    def hip_forward_live(self, xc, ctx, n, key_mask, lay):
+        """hip_forward's key-mask route over the live rows of one pass: xc, ctx [capacity, H] (live_buffers, xc filled by embed_live)
+        -> the compact [capacity, H] rows of the last layer (rows lay.row_start[n] + j = row j of sequence n)"""
+        s = lay.seq_len
+        for layer in self.layer:
+            xc = layer.hip_forward_live(xc, ctx, lay, [(0, n, s, lay.row_start, {"key_mask": key_mask})])
+        return xc
+
+    def hip_forward_pair_live(self, xc, ctx, n, s1, s2, mask1, mask2, live):
+        """hip_forward_pair over the live rows of both passes (live.pair; xc, ctx: live_buffers, xc filled by embed_live): returns
+        the compact rows"""
+        lay = live.pair
+        m1 = live.full.m_live
+        passes = [(0, n, s1, live.full.row_start, {"key_mask": mask1}), (m1, n, s2, live.img.row_start, {"key_mask": mask2})]
+        for layer in self.layer:
+            xc = layer.hip_forward_live(xc, ctx, lay, passes)
+        return xc
+
     def hip_forward_pair(self, rows, n, s1, s2, mask1, mask2, ws=None):
         """Two passes of the SAME encoder over different sequences (ModCR: the full [text | regions] pass of
         calec and the image-only [CLS | regions] pass of Abstract_Specific, modeling_ensemble.py:466-471) as one
@@ -213,14 +274,16 @@ class ImgEmbedMixin(object):
     _cast_cache = None      # (img_feats tensor, its version, kp, dtype, epoch) -> padded copy in the storage dtype, shared by all encoders
     _epoch = 0              # bumped by every Abstract_Specific.forward: nothing computed in one model call is re-used by the next
 
-    def region_rows(self, img_feats, dt):
+    def region_rows(self, img_feats, dt, reg=None):
         """LayerNorm(img_embedding(img_feats)) as [N*R, H] rows in the storage dtype `dt` (modeling_transfomres.py:676-680), before
         the dropout.  One ModCR step embeds the SAME region features three times (global_enc full pass, global_enc image-only pass,
         seq_enc: modeling_ensemble.py:466-471, v10:896-907).  The padded storage-dtype copy of the features is shared by
         all three, and an encoder whose weights have not changed re-uses its LayerNorm-ed region rows for a second call
         on the same tensor (global_enc's two passes).  Validity = the very same tensor object at the same version (a
         reference is held, so its memory cannot be recycled under the cache) within ONE forward of the whole model
-        (`_epoch`): a common subexpression of a step is computed once, nothing is carried from step to step."""
+        (`_epoch`): a common subexpression of a step is computed once, nothing is carried from step to step.
+        reg (mh.LiveRows.reg): the cast, the GEMM and the LayerNorm run over the layout's region rows only -- [reg.m_launch, H] rows
+        back to back, row reg.row_start[n] + j = region j of sequence n (the same values: every kernel here works row by row)."""
         n, r, d = img_feats.shape
         if not self.use_img_layernorm:
             raise NotImplementedError("use_img_layernorm=False: the Oscar checkpoints ModCR loads set it (run_PMR_ModCR.py:720)")
@@ -230,18 +293,21 @@ class ImgEmbedMixin(object):
         rc = getattr(self, "_region_cache", None)
         ep = ImgEmbedMixin._epoch
         if (rc is not None and rc[0] is img_feats and rc[1] == img_feats._version and rc[2] is w and rc[3] is g and rc[4].dtype == dt
-                and rc[5] == ep and not torch.is_grad_enabled()):
+                and rc[5] == ep and rc[6] is reg and not torch.is_grad_enabled()):
             return rc[4]
         cc = ImgEmbedMixin._cast_cache
-        if cc is not None and cc[0] is img_feats and cc[1] == img_feats._version and cc[2] == kp and cc[3] == dt and cc[5] == ep:
+        if cc is not None and cc[0] is img_feats and cc[1] == img_feats._version and cc[2] == kp and cc[3] == dt and cc[5] == ep and cc[6] is reg:
             src = cc[4]
         else:
-            src = mh.cast_pad(img_feats, kp, mh.BF16 if dt == torch.bfloat16 else mh.F32)     # fp32 [N*R,2054] -> dtype [N*R,Kp]
-            ImgEmbedMixin._cast_cache = (img_feats, img_feats._version, kp, dt, src, ep)
+            if reg is not None:
+                src = mh.cast_pad_rows(img_feats, kp, reg.row_id)                                 # live region rows only (bf16)
+            else:
+                src = mh.cast_pad(img_feats, kp, mh.BF16 if dt == torch.bfloat16 else mh.F32)     # fp32 [N*R,2054] -> dtype [N*R,Kp]
+            ImgEmbedMixin._cast_cache = (img_feats, img_feats._version, kp, dt, src, ep, reg)
         pre = mh.linear(src, w, b, out_dtype=mh.F32)
         rows = mh.layernorm(pre, g, be, self.config.img_layer_norm_eps, out_dtype=mh.BF16 if dt == torch.bfloat16 else mh.F32)
         if not torch.is_grad_enabled():
-            self._region_cache = (img_feats, img_feats._version, w, g, rows, ep)
+            self._region_cache = (img_feats, img_feats._version, w, g, rows, ep, reg)
         return rows
 
     def embed_regions(self, img_feats, out, t, dropout=None):
@@ -249,6 +315,27 @@ class ImgEmbedMixin(object):
         dropout = (p, seed, offset): self.dropout of the reference (:681) rides on the pass that places the rows
         (counters = flat indices of `out`; BertEmbeddings.forward(dropout=) covers the text rows under the same (seed, offset))."""
         return mh.rows_scatter_dropout(self.region_rows(img_feats, out.dtype), out, t, dropout)
+
+    def live_rows_usable(self, live_rows, n, t, r, device):
+        """what both encoder classes ask before a frozen pass runs over live rows: the switch, tables made for this batch shape and
+        device, bf16, a plain frozen pass (nothing materialised, no row chunks, every last-layer row wanted)"""
+        enc, cfg = self.encoder, self.config
+        return not (not LIVE_ROWS or live_rows is None or not live_rows.matches(n, t, r, device) or compute_dtype(cfg) != torch.bfloat16
+                    or torch.is_grad_enabled() and getattr(self, "trainable", False) or FFN_SPLIT > 1
+                    or enc.output_hidden_states or (enc.output_attentions and enc.materialize) or getattr(cfg, "modcr_last_layer_rows", False))
+
+    def embed_live(self, input_ids, token_type_ids, position_ids, img_feats, x, lay, live, dropout=None, filler=True):
+        """embeddings + embed_regions of one pass written straight into the live-row layout `lay` (live.full or live.img of the
+        mh.LiveRows `live`): x [>= lay.m_launch, H] gets the layout's rows back to back and zero filler rows.  dropout = (p, seed,
+        offset) of the ONE dropout over the padded [N, lay.seq_len, H] buffer: every row takes the counters of its padded position,
+        so x holds what the padded passes followed by a gather of the live rows would.  filler=False: only the lay.m_live live rows
+        are written (forward_pair: another pass's rows follow at once)."""
+        t = input_ids.shape[1]
+        m = lay.m_launch if filler else lay.m_live
+        self.embeddings(input_ids, token_type_ids, position_ids, out=x, dropout=dropout, row_start=lay.row_start, seq_stride=lay.seq_len)
+        mh.rows_place_dropout(self.region_rows(img_feats, x.dtype, live.reg), x[:m], lay.row_id[:m], live.r, lay.seq_len, t, dropout,
+                              src_start=live.reg.row_start)
+        return x
 
 
 class BertImgModel(BertPreTrainedModel, ImgEmbedMixin):
@@ -272,7 +359,19 @@ class BertImgModel(BertPreTrainedModel, ImgEmbedMixin):
         self._ws = Workspace()
         self.init_weights()
 
-    def forward_pair(self, input_ids, token_type_ids, attention_mask, img_feats, img_attention_mask, position_ids=None):
+    def live_route(self, live_rows, n, t, r, device, passes):
+        """the mh.LiveRows to run this frozen pass over, or None (the padded route): live_rows_usable and attention shapes
+        modcr_qkv_attn_rows_fwd serves.  passes: the sequence lengths whose key-mask attention the pass launches"""
+        cfg = self.config
+        if not self.live_rows_usable(live_rows, n, t, r, device):
+            return None
+        sa = self.encoder.layer[0].attention.self
+        attn_p = float(sa.dropout.p) if sa.training else 0.0
+        if not all(s > PACK_SHORT and live_attn_supported(n, s, cfg.hidden_size, cfg.num_attention_heads, attn_p, (1,)) for s in passes):
+            return None
+        return live_rows
+
+    def forward_pair(self, input_ids, token_type_ids, attention_mask, img_feats, img_attention_mask, position_ids=None, live_rows=None):
         """forward(input_ids, token_type_ids, attention_mask, img_feats=...) AND forward(input_ids[:, :1],
         attention_mask=img_attention_mask, img_feats=...) (the image-only call of modeling_ensemble.py:466-471) in
         one batch; returns the two output tuples (sequence_output, pooled_output).  The region embeddings are
@@ -282,12 +381,27 @@ class BertImgModel(BertPreTrainedModel, ImgEmbedMixin):
         h = self.config.hidden_size
         dt = compute_dtype(self.config)
         s1, s2 = t + r, 1 + r
-        rows = torch.empty((n * s1 + n * s2, h), dtype=dt, device=input_ids.device)
-        xa, xb = rows[:n * s1].view(n, s1, h), rows[n * s1:].view(n, s2, h)
         da = db = None
         if self.training and self.dropout.p > 0.0:          # BertEmbeddings.dropout + self.dropout (:681) of each of the two calls
-            da = (self.dropout.p,) + tuple(mh.DROPOUT.take(xa.numel()))
-            db = (self.dropout.p,) + tuple(mh.DROPOUT.take(xb.numel()))
+            da = (self.dropout.p,) + tuple(mh.DROPOUT.take(n * s1 * h))
+            db = (self.dropout.p,) + tuple(mh.DROPOUT.take(n * s2 * h))
+        live = self.live_route(live_rows, n, t, r, input_ids.device, (s1, s2))
+        if live is not None:
+            # live rows only, embedded in place; what the callers read comes back dense: the text rows of the full pass [N,T,H],
+            # [CLS] of the other [N,1,H]
+            xc, ctx = live_buffers(live.pair, h, dt, input_ids.device)
+            m1, m2 = live.full.m_live, live.img.m_live
+            self.embed_live(input_ids, token_type_ids, position_ids, img_feats, xc, live.full, live, da, filler=False)
+            self.embed_live(input_ids[:, :1].contiguous(), None, None, img_feats, xc[m1:], live.img, live, db, filler=False)
+            if live.pair.m_launch > m1 + m2:
+                xc[m1 + m2:live.pair.m_launch].zero_()
+            yc = self.encoder.hip_forward_pair_live(xc, ctx, n, s1, s2, attention_mask.to(torch.float32), img_attention_mask.to(torch.float32), live)
+            ya = mh.rows_take(yc, live.pair.take[t]).view(n, t, h)
+            yb = mh.rows_take(yc, live.pair.take["img"]).view(n, 1, h)
+            att = ((None,) * len(self.encoder.layer),) if self.encoder.output_attentions else ()
+            return (ya, self.pooler(ya)) + att, (yb, self.pooler(yb)) + att
+        rows = torch.empty((n * s1 + n * s2, h), dtype=dt, device=input_ids.device)
+        xa, xb = rows[:n * s1].view(n, s1, h), rows[n * s1:].view(n, s2, h)
         self.embeddings(input_ids, token_type_ids, position_ids, out=xa, dropout=da)
         self.embed_regions(img_feats, xa, t, dropout=da)
         self.embeddings(input_ids[:, :1].contiguous(), None, None, out=xb, dropout=db)
@@ -298,9 +412,11 @@ class BertImgModel(BertPreTrainedModel, ImgEmbedMixin):
         return (ya, self.pooler(ya)) + att, (yb, self.pooler(yb)) + att
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, position_ids=None, head_mask=None,
-                img_feats=None, encoder_history_states=None, modcr_last_rows=None):
+                img_feats=None, encoder_history_states=None, modcr_last_rows=None, live_rows=None):
         """modcr_last_rows = k (not in the reference's signature; frozen route only): sequence_output is [N,k,H], the first k rows of
-        every sequence -- the last layer computes nothing behind its attention for the rows the caller does not read."""
+        every sequence -- the last layer computes nothing behind its attention for the rows the caller does not read.
+        live_rows (not in the reference's signature; this project's own callers on the frozen route): the batch's mh.LiveRows --
+        the layers run over the live rows only and sequence_output is [N,T,H], the text rows (T = 1: the image-only call's [CLS])."""
         if head_mask is not None:
             raise NotImplementedError("head_mask is never set on the ModCR path")
         if attention_mask is None:
@@ -326,10 +442,23 @@ class BertImgModel(BertPreTrainedModel, ImgEmbedMixin):
         n, t = input_ids.shape
         r = 0 if img_feats is None else img_feats.shape[1]
         dt = compute_dtype(self.config)
-        x = torch.empty((n, t + r, self.config.hidden_size), dtype=dt, device=input_ids.device)
+        h = self.config.hidden_size
         drop = None
         if self.training and self.dropout.p > 0.0:          # BertEmbeddings.dropout (a_bert:210) and self.dropout (:681): same p,
-            drop = (self.dropout.p,) + tuple(mh.DROPOUT.take(x.numel()))      # one mask over x, applied by the passes that write its rows
+            drop = (self.dropout.p,) + tuple(mh.DROPOUT.take(n * (t + r) * h))     # one mask over x, applied by the passes that write its rows
+        live = None
+        if (live_rows is not None and img_feats is not None and dense_bits is None and modcr_last_rows is None and not encoder_history_states
+                and live_rows.r == r and t in (live_rows.t, 1)):
+            live = self.live_route(live_rows, n, live_rows.t, r, input_ids.device, (t + r,))
+        if live is not None:
+            lay = live.full if t == live.t else live.img          # (T = 1: both are the same layout)
+            xc, ctx = live_buffers(lay, h, dt, input_ids.device)
+            self.embed_live(input_ids, token_type_ids, position_ids, img_feats, xc, lay, live, drop)
+            yc = self.encoder.hip_forward_live(xc, ctx, n, attention_mask.to(torch.float32), lay)
+            sequence_output = mh.rows_take(yc, lay.take[t]).view(n, t, h)
+            att = ((None,) * len(self.encoder.layer),) if self.encoder.output_attentions else ()
+            return (sequence_output, self.pooler(sequence_output)) + att
+        x = torch.empty((n, t + r, h), dtype=dt, device=input_ids.device)
         self.embeddings(input_ids, token_type_ids, position_ids, out=x, dropout=drop)
         if img_feats is not None:
             self.embed_regions(img_feats, x, t, dropout=drop)

@@ -21,6 +21,7 @@ from .bert_primitives import (BertEmbeddings, BertIntermediate, BertOutput, Bert
                               BertSelfOutput, EncoderOutputs, PackCache, additive_to_binary, compute_dtype)
 from .hip_layers import Workspace
 from .modeling_bert import CaptionBertSelfAttention as _GlobalSelfAttention, split_additive_mask
+from . import modeling_transfomres as _mt
 from .modeling_transfomres import CaptionBertLayer as _GlobalLayer, ImgEmbedMixin
 
 BertLayerNorm = torch.nn.LayerNorm
@@ -172,6 +173,39 @@ class CaptionBertEncoder(nn.Module):
         outputs.align_map = amap
         return outputs, chunk_hidden_states
 
+    def hip_forward_live(self, xc, ctx, n, input_mask, chunk_mask, chunk_id, hypo_len, img_len, lay):
+        """hip_forward over the live rows of the pass (mh.LiveLayout `lay`, modeling_transfomres.LIVE_ROWS; xc, ctx: live_buffers, xc
+        filled by embed_live): same masks, same schedule; add_local_residual / add_residual are flat adds over the compact rows.
+        Returns (compact rows of the last layer, compact chunk_hidden_states, align map): row lay.row_start[n] + j of either = row j
+        of sequence n."""
+        s = lay.seq_len
+        m = lay.m_launch
+        bits1 = mh.build_phase_mask(input_mask, chunk_mask, 1)
+        bits3 = amap = chunk_hidden_states = None
+
+        def add(y, former):          # y + former over the launch rows, into a buffer of the full capacity
+            out = torch.empty_like(y)
+            mh.add(mh.convert(y[:m], mh.F32), former[:m], out_dtype=mh.dt_of(former), out=out[:m])
+            return out
+        for i, layer in enumerate(self.layer):
+            if i in self.cross_modal_layers:
+                if i == self.cross_modal_layers[0]:
+                    chunk_hidden_states = xc                      # v10:196-197
+                    bits3 = mh.build_phase_mask(input_mask, chunk_mask, 3)
+                    amap = torch.zeros((n, hypo_len, img_len), dtype=torch.float32, device=xc.device)
+                former = xc
+                xc = layer.hip_forward_live(xc, ctx, lay, [(0, n, s, lay.row_start, {"mask_bits": bits3, "chunk_id": chunk_id,
+                                                                                     "align_map": amap, "align_t": hypo_len})])
+                if self.add_local_residual:                       # v10:212-215
+                    xc = add(xc, former)
+            elif i not in self.chunk_attention_layers:
+                xc = layer.hip_forward_live(xc, ctx, lay, [(0, n, s, lay.row_start, {"key_mask": input_mask})])
+            else:
+                xc = layer.hip_forward_live(xc, ctx, lay, [(0, n, s, lay.row_start, {"mask_bits": bits1})])
+        if self.add_residual:                                     # v10:221-223
+            xc = add(xc, chunk_hidden_states)
+        return xc, chunk_hidden_states, amap
+
     def forward(self, hidden_states, chunk_attention_mask, gather_index, img_mask, input_mask, hypo_len, img_len,
                 head_mask=None, encoder_history_states=None, offsets=None):
         """Reference signature: the three masks arrive ADDITIVE and extended (v10:296-314)."""
@@ -203,12 +237,25 @@ class SeqBertImgModel(BertPreTrainedModel, ImgEmbedMixin):
         self.max_hypo = config.max_hypo
         self.edge_dense = nn.Embedding(1, config.hidden_size)
 
+    def live_route(self, live_rows, n, t, r, device, cid):
+        """the mh.LiveRows to run this frozen pass over, or None (the padded route): live_rows_usable and the three attention calls
+        of seq_enc (dense mask, key mask, the phase-3 call with its align map) served by modcr_qkv_attn_rows_fwd"""
+        enc, cfg = self.encoder, self.config
+        if not self.live_rows_usable(live_rows, n, t, r, device) or not enc.cross_modal_layers:
+            return None
+        sa = enc.layer[0].attention.self
+        attn_p = float(sa.dropout.p) if sa.training else 0.0
+        if not _mt.live_attn_supported(n, t + r, cfg.hidden_size, cfg.num_attention_heads, attn_p, (1, 2, 3), align_t=t, chunk_t=cid.shape[1]):
+            return None
+        return live_rows
+
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, input_mask=None, position_ids=None,
                 head_mask=None, img_feats=None, img_mask=None, encoder_history_states=None, offsets=None,
-                gather_index=None, modcr_last_rows=None):
+                gather_index=None, modcr_last_rows=None, live_rows=None):
         """attention_mask = chunk_attention_mask [N,T,T] 0/1, input_mask [N,T+R] 0/1 (v10:903-907).
         Returns ((sequence_output, pooled_output, attentions), chunk_hidden_states).  modcr_last_rows = k (not in the reference's
-        signature; frozen route only): sequence_output is [N,k,H], see BertImgModel.forward."""
+        signature; frozen route only): sequence_output is [N,k,H], see BertImgModel.forward.  live_rows (likewise): the batch's
+        mh.LiveRows -- the layers run over the live rows only; sequence_output and chunk_hidden_states are [N,T,H], the text rows."""
         if head_mask is not None:
             raise NotImplementedError("head_mask is never set on the ModCR path")
         if attention_mask is None or attention_mask.dim() != 3:
@@ -230,13 +277,26 @@ class SeqBertImgModel(BertPreTrainedModel, ImgEmbedMixin):
             outputs.align_map = amap                        # differentiable (hip_autograd.AlignMapFn)
             return outputs, chunk_hidden_states
         dt = compute_dtype(self.config)
-        x = torch.empty((n, t + r, self.config.hidden_size), dtype=dt, device=input_ids.device)
+        h = self.config.hidden_size
         drop = None
         if self.training and self.dropout.p > 0.0:          # BertEmbeddings.dropout (a_bert:210) and self.dropout (v10:343): same p,
-            drop = (self.dropout.p,) + tuple(mh.DROPOUT.take(x.numel()))      # one mask over x, applied by the passes that write its rows
+            drop = (self.dropout.p,) + tuple(mh.DROPOUT.take(n * (t + r) * h))     # one mask over x, applied by the passes that write its rows
+        cid = gather_index if torch.is_tensor(gather_index) else pack_chunk_ids(gather_index, t, input_ids.device)
+        live = self.live_route(live_rows, n, t, r, input_ids.device, cid) if (modcr_last_rows is None and not encoder_history_states) else None
+        if live is not None:
+            xc, ctx = _mt.live_buffers(live.full, h, dt, input_ids.device)
+            self.embed_live(input_ids, token_type_ids, position_ids, img_feats, xc, live.full, live, drop)
+            yc, chs, amap = self.encoder.hip_forward_live(xc, ctx, n, input_mask.to(torch.float32), attention_mask.to(torch.float32), cid, t, r,
+                                                          live.full)
+            sequence_output = mh.rows_take(yc, live.full.take[t]).view(n, t, h)
+            chunk_hidden_states = mh.rows_take(chs, live.full.take[t]).view(n, t, h)
+            att = ((None,) * len(self.encoder.layer),) if self.encoder.output_attentions else ()
+            outputs = EncoderOutputs((sequence_output, self.pooler(sequence_output)) + att)
+            outputs.align_map = amap
+            return outputs, chunk_hidden_states
+        x = torch.empty((n, t + r, h), dtype=dt, device=input_ids.device)
         self.embeddings(input_ids, token_type_ids, position_ids, out=x, dropout=drop)
         self.embed_regions(img_feats, x, t, dropout=drop)
-        cid = gather_index if torch.is_tensor(gather_index) else pack_chunk_ids(gather_index, t, input_ids.device)
         encoder_outputs, chunk_hidden_states = self.encoder.hip_forward(
             x, input_mask.to(torch.float32), attention_mask.to(torch.float32), cid, t, r, encoder_history_states,
             ws=self._ws, last_rows=modcr_last_rows)
@@ -444,9 +504,11 @@ class ChunkAlign_CLS_enc4_align_ensemble(nn.Module):
     def forward(self, input_ids, img_feat, input_mask=None, label=None, token_type_ids=None, position_ids=None,
                 head_mask=None, encoder_history_states=None, offsets=None, chunk_attention_mask=None,
                 gather_index=None, align_pos=None, total_label=None, abstract_hidden_states=None,
-                global_outputs=None):
+                global_outputs=None, live_rows=None):
         # global_outputs (not in the reference's signature): the global_enc outputs of exactly this call when the
         # caller has already computed them (Abstract_Specific batches this pass with its image-only pass)
+        # live_rows (likewise): the batch's mh.LiveRows; the frozen encoders then skip the padded region rows and hand back the text
+        # rows [N,T,H] -- everything below reads [:, 1:hypo_len] of their outputs, the pooled [CLS] rows and the align map
         hypo_len = input_ids.size(1)
         ag.set_exact(getattr(self.global_enc.config, "modcr_dtype", "bf16") == "fp32")
         # opt-in (config.modcr_last_layer_rows): everything below reads text rows and the pooled [CLS] only, so the frozen encoders'
@@ -455,6 +517,8 @@ class ChunkAlign_CLS_enc4_align_ensemble(nn.Module):
         if (getattr(self.global_enc.config, "modcr_last_layer_rows", False) and not (self.train_encoders and torch.is_grad_enabled())
                 and encoder_history_states is None):
             lr = {"modcr_last_rows": hypo_len}
+        if live_rows is not None and not lr and not (self.train_encoders and torch.is_grad_enabled()) and encoder_history_states is None:
+            lr = {"live_rows": live_rows}
         with (torch.enable_grad() if self.train_encoders and torch.is_grad_enabled() else torch.no_grad()):
             outputs = global_outputs if global_outputs is not None else self.global_enc(
                 input_ids, img_feats=img_feat, attention_mask=input_mask, position_ids=position_ids,

@@ -586,6 +586,9 @@ def pack_gather_index(gather_index, t):
 
 
 def batch_to_device(batch, device):
+    """the batch on `device` (non-blocking copies).  A HOST batch with a prefix-form image mask also gets `live_rows`: the
+    mh.LiveRows tables of the live-row layout, built here from the host input_mask (no device -> host read) and copied with the
+    rest; `live_rows_tables` is their device array (a tensor, so that whoever tracks the batch's tensors tracks it too)."""
     out = {}
     if isinstance(batch.get("gather_index"), list) and torch.is_tensor(batch.get("input_ids")):
         batch = dict(batch, gather_index=pack_gather_index(batch["gather_index"], batch["input_ids"].shape[1]))
@@ -596,12 +599,19 @@ def batch_to_device(batch, device):
             out[k] = [t.to(device, non_blocking=True) for t in v]
         else:
             out[k] = v
+    if torch.is_tensor(batch.get("input_mask")) and torch.is_tensor(batch.get("input_ids")) and torch.is_tensor(batch.get("img_feat")):
+        import modcr_hip as mh
+        live = mh.live_rows_from_mask(batch["input_mask"], batch["input_ids"].shape[1])
+        if live is not None and live.r == batch["img_feat"].shape[1]:
+            out["live_rows"] = live.to(device)
+            out["live_rows_tables"] = live.blob
     return out
 
 
 def forward_inputs(batch):
-    """the kwargs dict of run_PMR_ModCR.py:189-200"""
-    return {'input_ids': batch['input_ids'], 'image': batch['image'], 'text': batch['text'],
+    """the kwargs dict of run_PMR_ModCR.py:189-200 (+ the live-row tables batch_to_device attached, if any)"""
+    live = {'live_rows': batch['live_rows']} if batch.get('live_rows') is not None else {}
+    return {**live, 'input_ids': batch['input_ids'], 'image': batch['image'], 'text': batch['text'],
             'roberta_input_ids': batch['r_input_ids'], 'roberta_token_type_ids': batch['r_token_type_ids'],
             'roberta_attention_mask': batch['r_attention_mask'], 'token_type_ids': batch['token_type_ids'],
             'input_mask': batch['input_mask'], 'img_feat': batch['img_feat'], 'label': batch['label'],
