@@ -128,7 +128,8 @@ int modcr_qkv_attn_opt_fwd(const void* x, const void* hist, const void* wqkv, co
  *   attn_p > 0 (P + S <= 256 only, MODCR_ERR_UNSUPPORTED above): the keep decisions every other route makes for the same
  *             (seed, offset); the context uses P o m / (1 - p), the side outputs the un-dropped probabilities, or with
  *             MODCR_ATTN_SIDE_POST_DROPOUT the post-dropout ones.
- *   chunk_id / ctx / probs / align_map / align_t: as modcr_qkv_attn_fwd.  No lse, no qkv_dump, no backward.
+ *   chunk_id / ctx / probs / align_map / align_t: as modcr_qkv_attn_fwd.  No lse, no qkv_dump; the backward is
+ *             modcr_qkv_attn_bias_bwd (S <= 256, no prefix rows), which recomputes the row statistics.
  *   workspace: modcr_qkv_attn_bias_workspace = N (P+S) 3H elements of the storage dtype at EVERY key count: [hist ; x] is
  *             projected into it (modcr_linear_fwd), the chunk-mean applied, then the streaming core of csrc/attn_long.hip runs.
  * Every argument is validated before the first launch.  modcr_time_next_attn times this core too. */
@@ -450,6 +451,28 @@ int modcr_qkv_attn_opt_bwd(const void* dctx, const void* x, const void* wqkv, co
                            int32_t S, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset,
                            const float* d_align, int32_t align_t, const void* ctx, const float* lse, const void* qkv_dump, int32_t flags,
                            void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
+/* Backward of modcr_qkv_attn_bias_fwd without prefix rows and without an align-map gradient: the gradient through
+ * softmax(q.k / 8 + bias), the attention dropout of (attn_p, seed, offset) and the head mask, S <= 256, bf16 and fp32.
+ *   attn_bias / bias_stride_* / head_mask / head_mask_stride_n: the forward's operands, read as given (strides in elements,
+ *             0 = broadcast, key stride 1; never expanded); at least one of the two.  bias_stride_q <= 2^20.
+ *   d_bias    fp32 contiguous [N, A, S, S] or NULL: receives dS = P o (dP - rowsum(dP o P)), the gradient of the DENSE bias (a
+ *             broadcast bias's gradient is its sum over the broadcast dimensions: the caller's reduction).  Every element is
+ *             written, by exactly one lane: no atomics, repeated calls are bit-identical.  A -inf entry has probability 0 and
+ *             d_bias 0; a query row whose every key is -inf (the forward's P = 0 row) adds exactly nothing to dx, dwqkv,
+ *             dbqkv and has a zero d_bias row.  No gradient for head_mask: it is a constant (head pruning).
+ *   dctx, x, wqkv, bqkv, chunk_id, dx_residual, dx, dwqkv, dbqkv, accumulate: as modcr_qkv_attn_dropout_bwd.
+ * The core recomputes the row statistics from the recomputed q | k | v rows (the bias forward writes no lse / dump):
+ * attn_bias_bwd_mfma_kernel (bf16, S <= 192) or the exact attn_bias_bwd_f32_kernel (fp32; bf16 with 192 < S <= 256), both in
+ * csrc/attn_bias_bwd.hip.  modcr_qkv_attn_bias_bwd_route says which without launching: 0 = the call is refused, 1 = MFMA core,
+ * 2 = exact core.  Every argument is validated before the first launch; S > 256 returns MODCR_ERR_UNSUPPORTED. */
+int64_t modcr_qkv_attn_bias_bwd_workspace(int32_t N, int32_t S, int32_t H, int32_t dtype);
+int modcr_qkv_attn_bias_bwd_route(int32_t N, int32_t S, int32_t H, int32_t A, int32_t dtype);
+int modcr_qkv_attn_bias_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv,
+                            const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                            const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
+                            const float* dx_residual, void* dx, float* dwqkv, float* dbqkv, int32_t accumulate, float* d_bias,
+                            int32_t N, int32_t S, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset,
+                            void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
 
 /* ---- backward of the encoder layer's GEMM blocks (autograd of BertSelfOutput / BertIntermediate / BertOutput,
  * a_bert:362-373, :425-437, :440-451).  Gradients of parameters are fp32; dgamma / dbeta are ACCUMULATED (caller

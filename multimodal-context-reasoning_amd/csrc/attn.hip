@@ -2740,3 +2740,81 @@ extern "C" int modcr_qkv_attn_opt_bwd(const void* dctx, const void* x, const voi
     return attn_bwd(dctx, x, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, dx_residual, dx, dwqkv, dbqkv, accumulate,
                     N, S, H, A, attn_p, seed, offset, d_align, align_t, ctx, lse, qkv_dump, flags, workspace, workspace_bytes, dtype, stream);
 }
+
+// ---- backward of modcr_qkv_attn_bias_fwd (no prefix rows, no align-map gradient) --------------------------------------------------
+// The body is attn_bwd()'s, step for step, with the cores of attn_bias_bwd.hip in step 2.
+extern "C" int64_t modcr_qkv_attn_bias_bwd_workspace(int32_t N, int32_t S, int32_t H, int32_t dtype) {
+    return modcr_qkv_attn_bwd_workspace(N, S, H, dtype);
+}
+
+// 0 = refused, 1 = attn_bias_bwd_mfma_kernel, 2 = attn_bias_bwd_f32_kernel
+extern "C" int modcr_qkv_attn_bias_bwd_route(int32_t N, int32_t S, int32_t H, int32_t A, int32_t dtype) {
+    if (N <= 0 || S <= 0 || S > 256 || A <= 0 || H != A * 64 || (dtype != MODCR_BF16 && dtype != MODCR_F32)) return 0;
+    return dtype == MODCR_BF16 && S <= AB::LP ? 1 : 2;
+}
+
+extern "C" int modcr_qkv_attn_bias_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* attn_bias,
+                                       int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q, const float* head_mask,
+                                       int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx,
+                                       float* dwqkv, float* dbqkv, int32_t accumulate, float* d_bias, int32_t N, int32_t S, int32_t H, int32_t A,
+                                       float attn_p, uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                                       modcr_stream_t stream) {
+    const char* who = "qkv_attn_bias_bwd";
+    MODCR_REQUIRE(dctx && x && wqkv && bqkv && dx && dwqkv && dbqkv, "%s: null pointer", who);
+    MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "%s: unknown dtype %d", who, dtype);
+    MODCR_REQUIRE(N > 0 && S > 0 && A > 0, "%s: bad shape (N=%d S=%d H=%d A=%d)", who, N, S, H, A);
+    MODCR_REQUIRE(H == A * 64, "%s: head size must be 64 (H=%d, A=%d)", who, H, A);
+    if (S > 256) {
+        modcr_set_error("%s: S=%d exceeds the 256-key limit of the attention backward", who, S);
+        return MODCR_ERR_UNSUPPORTED;
+    }
+    MODCR_REQUIRE(attn_bias || head_mask, "%s: neither bias nor head_mask (that call belongs to modcr_qkv_attn_opt_bwd)", who);
+    MODCR_REQUIRE(attn_bias || !d_bias, "%s: d_bias without a bias", who);
+    MODCR_REQUIRE(attn_p >= 0.f && attn_p < 1.f, "%s: attention dropout p=%g out of [0, 1)", who, attn_p);
+    MODCR_REQUIRE(bias_stride_n >= 0 && bias_stride_a >= 0 && bias_stride_q >= 0 && head_mask_stride_n >= 0, "%s: negative stride", who);
+    // (the cores address a (sequence, head) slice of the bias with 32-bit element offsets)
+    MODCR_REQUIRE(bias_stride_q <= (1 << 20), "%s: bias query stride %lld exceeds 2^20 elements", who, (long long)bias_stride_q);
+    MODCR_REQUIRE(((uintptr_t)attn_bias & 3) == 0 && ((uintptr_t)head_mask & 3) == 0 && ((uintptr_t)d_bias & 3) == 0,
+                  "%s: bias / head_mask / d_bias not 4-byte aligned", who);
+    MODCR_REQUIRE(!chunk_id || (chunk_t > 0 && chunk_t <= S), "%s: chunk_t=%d out of range", who, chunk_t);
+    MODCR_REQUIRE(dtype != MODCR_BF16 || (modcr_aligned16(dctx) && modcr_aligned16(x) && modcr_aligned16(wqkv) && modcr_aligned16(dx)),
+                  "%s(bf16): 16-byte alignment", who);
+    const int64_t need = modcr_qkv_attn_bias_bwd_workspace(N, S, H, dtype);
+    MODCR_REQUIRE(workspace && workspace_bytes >= need && modcr_aligned16(workspace), "%s: workspace %lld < %lld bytes (or unaligned)", who,
+                  (long long)workspace_bytes, (long long)need);
+    const int core = modcr_qkv_attn_bias_bwd_route(N, S, H, A, dtype);
+    const int M = N * S;
+    const int64_t rows = (((int64_t)M * 3 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
+    void* qkv = workspace;
+    void* dqkv = (char*)workspace + rows;
+    void* sub = dtype == MODCR_BF16 ? (void*)((char*)workspace + 2 * rows) : nullptr;
+    const int64_t sub_bytes = dtype == MODCR_BF16 ? attn_bwd_sub_ws(M, H) : 0;
+    // 1. recompute q | k | v rows (MFMA core: bf16, exact core: fp32), chunk-mean queries as the forward
+    const int32_t qdt = core == 1 ? MODCR_BF16 : MODCR_F32;
+    int rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, qkv, 3 * H, M, 3 * H, H, MODCR_ACT_NONE, dtype, qdt, stream);
+    if (rc != MODCR_OK) return rc;
+    if (chunk_id) {
+        rc = modcr_chunk_mean_q_fwd(qkv, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, qdt, stream);
+        if (rc != MODCR_OK) return rc;
+    }
+    // 2. attention core backward
+    AttnBiasBwdArgs b;
+    b.qkv = qkv; b.dctx = dctx; b.dqkv = dqkv;
+    b.bias = attn_bias; b.bias_sn = bias_stride_n; b.bias_sa = bias_stride_a; b.bias_sq = bias_stride_q;
+    b.head_mask = head_mask; b.head_mask_sn = head_mask_stride_n;
+    b.d_bias = d_bias;
+    const AttnDrop d = attn_drop(attn_p, seed, offset);     // (as the forward)
+    b.drop_thr16 = d.thr16; b.drop_key = d.key; b.drop_keep = d.keep;
+    b.N = N; b.S = S; b.H = H; b.A = A;
+    rc = modcr_launch_attn_bias_bwd(b, core, dtype, (hipStream_t)stream);
+    if (rc != MODCR_OK) return rc;
+    // 3. the chunk mean is its own adjoint
+    if (chunk_id) {
+        rc = modcr_chunk_mean_q_fwd(dqkv, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, qdt, stream);
+        if (rc != MODCR_OK) return rc;
+    }
+    // 4. dX = dqkv . Wqkv (+ dx_residual);  dWqkv (+)= dqkv^T . X;  dbqkv (+)= column sums
+    rc = modcr_linear_bwd_input_res(dqkv, 3 * H, qdt, wqkv, H, dx_residual, H, dx, H, M, 3 * H, H, dtype, dtype, sub, sub_bytes, stream);
+    if (rc != MODCR_OK) return rc;
+    return modcr_linear_bwd_weight(dqkv, 3 * H, qdt, x, H, dwqkv, dbqkv, M, 3 * H, H, accumulate, dtype, sub, sub_bytes, stream);
+}

@@ -125,6 +125,23 @@ struct AttnBwdArgs {
 // attn_bwd.hip: launches attn_bwd5_kernel on `b` (bf16 rows, 0 < S <= 192, lse and ctx given, no align-map gradient)
 __attribute__((visibility("hidden"))) int modcr_launch_attn_bwd5(const AttnBwdArgs& b, hipStream_t stream);
 
+// attn_bias_bwd.hip: the attention core backward under an additive bias and / or a head mask (modcr_qkv_attn_bias_bwd), from the
+// recomputed q | k | v rows [N*S][3H] to the dq | dk | dv rows of the same layout and, when wanted, d_bias = dS [N, A, S, S] fp32.
+struct AttnBiasBwdArgs {
+    const void* qkv; const void* dctx; void* dqkv;         // core 1: bf16 rows in and out; core 2: fp32 rows, dctx in the storage dtype
+    // bias[n sn + a sa + q sq + j] fp32 (strides in elements, 0 = broadcast; NULL = no bias), head_mask[n hsn + a] (NULL = 1)
+    const float* bias; int64_t bias_sn, bias_sa, bias_sq;
+    const float* head_mask; int64_t head_mask_sn;
+    float* d_bias;                                          // or NULL
+    // the forward's attention-probability dropout: 0 = off, else thr16 = round(p * 2^16); the 64-bit key; 1 / (1 - p)
+    uint32_t drop_thr16;
+    uint64_t drop_key;
+    float drop_keep;
+    int N, S, H, A;
+};
+// core: 1 = attn_bias_bwd_mfma_kernel (bf16, S <= 192), 2 = attn_bias_bwd_f32_kernel (S <= 256)
+__attribute__((visibility("hidden"))) int modcr_launch_attn_bias_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype, hipStream_t stream);
+
 // attn_long.hip: the streaming attention core (P + S <= 512) over q | k | v rows the dispatcher projected: qx [N*S][3H] (queries,
 // chunk-mean applied), qh [N*P][3H] (prefix rows) -- bf16 or fp32 as `dtype`.  Binary masks (key_mask / bits: above 256 keys, no
 // dropout), or -- bias and / or head_mask set -- the additive-bias variant of modcr_qkv_attn_bias_fwd at any P + S <= 512.

@@ -96,6 +96,10 @@ SIGNATURES = {
                                       _f32, _c.c_uint64, _c.c_uint64, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "modcr_qkv_attn_opt_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
                                       _f32, _c.c_uint64, _c.c_uint64, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp]),
+    "modcr_qkv_attn_bias_bwd_workspace": (_i64, [_i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_bias_bwd_route": (_i32, [_i32, _i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_bias_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
+                                       _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
     "modcr_linear_residual_ln_bwd_workspace": (_i64, [_i32, _i32, _i32]),
     "modcr_linear_residual_ln_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
                                             _vp, _i64, _i32, _vp]),
@@ -1001,12 +1005,24 @@ def adamw_step(p, g, m, v, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay,
 
 def qkv_attn_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, mask_bits=None, chunk_id=None, num_heads=None,
                  accumulate=False, attn_dropout=None, d_align=None, align_t=0, dx_residual=None, ctx=None, lse=None, dump=None,
-                 side_post_dropout=False):
+                 side_post_dropout=False, attn_bias=None, head_mask=None, d_bias=None):
     """Backward of qkv_attn (no prefix rows): returns dx [N,S,H] in x's dtype; dwqkv [3H,H] / dbqkv [3H] fp32 are
     written (or added into when accumulate).  attn_dropout = the (p, seed, offset) the forward ran with; d_align [N,T,R] =
     gradient of the align map the forward accumulated (align_t = T); dx_residual (fp32, x's shape) is added to dx in the
     epilogue of its GEMM.  ctx + lse: the forward's context rows and the row statistics qkv_attn(lse=) wrote -- the attention
-    core then runs as the five-product kernel (csrc/attn_bwd.hip) instead of recomputing the statistics."""
+    core then runs as the five-product kernel (csrc/attn_bwd.hip) instead of recomputing the statistics.
+    attn_bias / head_mask: the operands of a forward that ran qkv_attn(attn_bias=, head_mask=) (modcr_qkv_attn_bias_bwd, S <= 256);
+    d_bias: a contiguous fp32 [N, A, S, S] tensor that receives the gradient of the DENSE bias (sum_to_size it to the bias's own
+    shape).  They replace key_mask / mask_bits and do not combine with ctx / lse / dump / d_align."""
+    if attn_bias is not None or head_mask is not None or d_bias is not None:
+        if key_mask is not None or mask_bits is not None:
+            raise ValueError("qkv_attn_bwd: attn_bias / head_mask replace key_mask / mask_bits")
+        if ctx is not None or lse is not None or dump is not None:
+            raise ValueError("qkv_attn_bwd: no ctx / lse / dump on the attn_bias / head_mask route (it recomputes the row statistics)")
+        if d_align is not None:
+            raise ValueError("qkv_attn_bwd: no align-map gradient (d_align) on the attn_bias / head_mask route")
+        return _qkv_attn_bias_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, num_heads, accumulate,
+                                  attn_dropout, dx_residual)
     dt = dt_of(x)
     x, dctx = _contig(x), _contig(dctx)
     if (ctx is None) != (lse is None):
@@ -1032,6 +1048,42 @@ def qkv_attn_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, mask_bits=Non
                                         _ptr(ctx), _ptr(lse), _ptr(dump), ATTN_SIDE_POST_DROPOUT if side_post_dropout else 0,
                                         _ptr(ws), need, dt, _stream()),
            "modcr_qkv_attn_bwd")
+    return dx
+
+
+ATTN_BWD_MAX_KEYS = 256
+ATTN_BIAS_BWD_CORES = {0: "refused", 1: "mfma", 2: "exact"}
+
+
+def qkv_attn_bias_bwd_route(n, s, h, a, dtype=BF16):
+    """The core modcr_qkv_attn_bias_bwd runs for this shape (nothing is launched): "mfma", "exact" or "refused"."""
+    return ATTN_BIAS_BWD_CORES[lib().modcr_qkv_attn_bias_bwd_route(n, s, h, a, dtype)]
+
+
+def _qkv_attn_bias_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, a, accumulate, attn_dropout, dx_residual):
+    """qkv_attn_bwd with attn_bias / head_mask: modcr_qkv_attn_bias_bwd"""
+    dt = dt_of(x)
+    x, dctx = _contig(x), _contig(dctx)
+    n, s, h = x.shape
+    if s > ATTN_BWD_MAX_KEYS:
+        raise ValueError("qkv_attn_bwd: S = %d exceeds the %d-key limit of the attention backward" % (s, ATTN_BWD_MAX_KEYS))
+    if attn_bias is None and head_mask is None:
+        raise ValueError("qkv_attn_bwd: d_bias without attn_bias")
+    bias, (bsn, bsa, bsq) = (None, (0, 0, 0)) if attn_bias is None else _bias_strides(attn_bias, n, a, s, s)
+    hm, hsn = (None, 0) if head_mask is None else _head_mask_2d(head_mask, n, a)
+    if d_bias is not None and (bias is None or d_bias.dtype != torch.float32 or tuple(d_bias.shape) != (n, a, s, s) or not d_bias.is_contiguous()):
+        raise ValueError("qkv_attn_bwd: d_bias must be a contiguous fp32 [N, A, S, S] tensor, given together with attn_bias")
+    dx = torch.empty_like(x)
+    need = lib().modcr_qkv_attn_bias_bwd_workspace(n, s, h, dt)
+    ws = _workspace("attn_bwd", need, x.device)
+    chunk_t = 0 if chunk_id is None else chunk_id.shape[1]
+    ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
+    _check(lib().modcr_qkv_attn_bias_bwd(_ptr(dctx), _ptr(x), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq, _ptr(hm), hsn,
+                                         _ptr(chunk_id), chunk_t,
+                                         _ptr(_contig(dx_residual, torch.float32)) if dx_residual is not None else None,
+                                         _ptr(dx), _ptr(dwqkv), _ptr(dbqkv), 1 if accumulate else 0, _ptr(d_bias),
+                                         n, s, h, a, float(ap), seed, off, _ptr(ws), need, dt, _stream()),
+           "modcr_qkv_attn_bias_bwd")
     return dx
 
 

@@ -351,70 +351,112 @@ class BertLayerFn(_NotedFn):
 
     @staticmethod
     def forward(ctx, x, key_mask, mask_bits, chunk_id, num_heads, eps, p, attn_p, packed, *params):
-        from . import hip_layers
-        s = x.shape[1]
-        if s > mh.ATTN_TILE_KEYS and _caller_grad_mode()[-1] and (x.requires_grad or any(
-                isinstance(p_, torch.Tensor) and p_.requires_grad for p_ in params)):
-            # the attention forward serves up to 512 keys, its backward (modcr_qkv_attn_bwd) 256: refuse before any launch
-            raise NotImplementedError("a trainable layer at S = %d exceeds the %d keys the attention backward takes; run it under "
-                                      "torch.no_grad() (eval) up to %d keys" % (s, mh.ATTN_TILE_KEYS, mh.ATTN_MAX_KEYS))
-        align = packed.get("_align") if isinstance(packed, dict) else None       # (map buffer, T, gradient holder) of AlignMapFn
-        amap, at = (align[0], align[1]) if align is not None else (None, 0)
-        y, saved = hip_layers.layer_forward_train(packed, x.detach(), num_heads, eps, key_mask=key_mask,
-                                                  mask_bits=mask_bits, chunk_id=chunk_id, p=p, attn_p=attn_p,
-                                                  align_map=amap, align_t=at,
-                                                  side_post_dropout=bool(packed.get("_side_post", True)) if isinstance(packed, dict) else True)
-        ctx.saved, ctx.packed = saved, packed
-        ctx.holder = align[2] if align is not None else None
-        ctx.params = params                  # (the Parameter objects: the gradient sink writes into their .grad views)
-        ctx.need = [p_.requires_grad for p_ in params]
-        ctx.need_x = x.requires_grad
-        # gradient sink: this node is ONE use of each of its parameters.  A layer applied twice in a graph (global_enc with trainable
-        # encoders: the image-only pass and the full pass) has two: the node whose backward runs first still writes in place, but the
-        # sink counts the bucket down only when the LAST use has reported (FlatGrads.done) -- or autograd's hook does, which fires
-        # after every node of the parameter has run.  Counting down on the first report would let the bucket's all-reduce start,
-        # at N > 1, before the second contribution has been added.
-        _note_uses(ctx, [(9 + i, p_ if isinstance(p_, torch.nn.Parameter) else None) for i, p_ in enumerate(params)])
-        return y
+        return _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, params, key_mask=key_mask, mask_bits=mask_bits)
 
     @staticmethod
     def backward(ctx, dy):
-        from . import hip_layers
-        d_align = ctx.holder.get("d_align") if ctx.holder is not None else None
-        sink, outs, sunk = grad_sink(), {}, {}
-        if sink is not None:
-            pmap = dict(zip(BertLayerFn.NAMES, zip(ctx.params, ctx.need)))
-            # the LayerNorm parameters only as a group (the kernels accumulate into all four)
-            ln_ok = all(pmap[nm][1] for nm in ACCUMULATING)
-            for nm in IN_PLACE_NAMES:
-                prm, need = pmap[nm]
-                if not need or (nm in ACCUMULATING and not ln_ok):
-                    continue
-                t = sink.take(prm, accumulates=nm in ACCUMULATING)
-                if t is not None:
-                    outs[nm], sunk[nm] = t, prm
-            if any(nm in outs for nm in ACCUMULATING) and not all(nm in outs for nm in ACCUMULATING):
-                for nm in ACCUMULATING:
-                    if nm in outs:
-                        sink.untake(sunk.pop(nm))
-                        del outs[nm]
-            # the q | k | v weight (bias) gradients: one [3H, H] product ([3H] column sum) -- written in place where the sink laid the
-            # three tensors out back to back (FlatGrads(names=...))
-            if hasattr(sink, "take_span"):
-                for kind in ("weight", "bias"):
-                    nms = ["attention.self.%s.%s" % (q, kind) for q in ("query", "key", "value")]
-                    if all(pmap[nm][1] for nm in nms):
-                        t = sink.take_span([pmap[nm][0] for nm in nms])
-                        if t is not None:
-                            outs["attention.self.qkv." + kind] = t
-                            for nm in nms:
-                                sunk[nm] = pmap[nm][0]
-        dx, g = hip_layers.layer_backward(ctx.packed, ctx.saved, dy.contiguous(), mfma=not EXACT, d_align=d_align, outs=outs)
-        ctx.saved = None
-        grads = [None if (n in sunk or not need) else g[n] for n, need in zip(BertLayerFn.NAMES, ctx.need)]
-        for prm in sunk.values():
-            sink.done(prm)
-        return (dx if ctx.need_x else None,) + (None,) * 8 + tuple(grads)
+        dx, grads, _ = _bert_layer_backward(ctx, dy)
+        return (dx,) + (None,) * 8 + grads
+
+
+def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, params, key_mask=None, mask_bits=None, attn_bias=None,
+                        head_mask=None):
+    """forward of BertLayerFn / BertLayerBiasFn: both take nine arguments before the 16 parameters, so parameter i is input 9 + i"""
+    from . import hip_layers
+    s = x.shape[1]
+    wants_grad = _caller_grad_mode()[-1] and (x.requires_grad or any(isinstance(p_, torch.Tensor) and p_.requires_grad for p_ in params) or
+                                              (attn_bias is not None and attn_bias.requires_grad))
+    if s > mh.ATTN_TILE_KEYS and wants_grad:
+        # the attention forward serves up to 512 keys, its backward (modcr_qkv_attn_bwd) 256: refuse before any launch
+        raise NotImplementedError("a trainable layer at S = %d exceeds the %d keys the attention backward takes; run it under "
+                                  "torch.no_grad() (eval) up to %d keys" % (s, mh.ATTN_TILE_KEYS, mh.ATTN_MAX_KEYS))
+    if head_mask is not None and head_mask.requires_grad and _caller_grad_mode()[-1]:
+        raise NotImplementedError("head_mask is a constant of the trainable layer (head pruning): no gradient is formed for it; detach() it")
+    align = packed.get("_align") if isinstance(packed, dict) else None       # (map buffer, T, gradient holder) of AlignMapFn
+    amap, at = (align[0], align[1]) if align is not None else (None, 0)
+    y, saved = hip_layers.layer_forward_train(packed, x.detach(), num_heads, eps, key_mask=key_mask,
+                                              mask_bits=mask_bits, chunk_id=chunk_id, p=p, attn_p=attn_p,
+                                              align_map=amap, align_t=at,
+                                              side_post_dropout=bool(packed.get("_side_post", True)) if isinstance(packed, dict) else True,
+                                              attn_bias=None if attn_bias is None else attn_bias.detach(),
+                                              head_mask=None if head_mask is None else head_mask.detach())
+    ctx.saved, ctx.packed = saved, packed
+    ctx.holder = align[2] if align is not None else None
+    ctx.params = params                  # (the Parameter objects: the gradient sink writes into their .grad views)
+    ctx.need = [p_.requires_grad for p_ in params]
+    ctx.need_x = x.requires_grad
+    ctx.need_bias = attn_bias is not None and attn_bias.requires_grad
+    # gradient sink: this node is ONE use of each of its parameters.  A layer applied twice in a graph (global_enc with trainable
+    # encoders: the image-only pass and the full pass) has two: the node whose backward runs first still writes in place, but the
+    # sink counts the bucket down only when the LAST use has reported (FlatGrads.done) -- or autograd's hook does, which fires
+    # after every node of the parameter has run.  Counting down on the first report would let the bucket's all-reduce start,
+    # at N > 1, before the second contribution has been added.
+    _note_uses(ctx, [(9 + i, p_ if isinstance(p_, torch.nn.Parameter) else None) for i, p_ in enumerate(params)])
+    return y
+
+
+def _bert_layer_backward(ctx, dy):
+    """backward of BertLayerFn / BertLayerBiasFn: (dx or None, the 16 parameter gradients -- None where the sink took them --,
+    the dense [N, A, S, S] bias gradient or None)"""
+    from . import hip_layers
+    d_align = ctx.holder.get("d_align") if ctx.holder is not None else None
+    sink, outs, sunk = grad_sink(), {}, {}
+    if sink is not None:
+        pmap = dict(zip(BertLayerFn.NAMES, zip(ctx.params, ctx.need)))
+        # the LayerNorm parameters only as a group (the kernels accumulate into all four)
+        ln_ok = all(pmap[nm][1] for nm in ACCUMULATING)
+        for nm in IN_PLACE_NAMES:
+            prm, need = pmap[nm]
+            if not need or (nm in ACCUMULATING and not ln_ok):
+                continue
+            t = sink.take(prm, accumulates=nm in ACCUMULATING)
+            if t is not None:
+                outs[nm], sunk[nm] = t, prm
+        if any(nm in outs for nm in ACCUMULATING) and not all(nm in outs for nm in ACCUMULATING):
+            for nm in ACCUMULATING:
+                if nm in outs:
+                    sink.untake(sunk.pop(nm))
+                    del outs[nm]
+        # the q | k | v weight (bias) gradients: one [3H, H] product ([3H] column sum) -- written in place where the sink laid the
+        # three tensors out back to back (FlatGrads(names=...))
+        if hasattr(sink, "take_span"):
+            for kind in ("weight", "bias"):
+                nms = ["attention.self.%s.%s" % (q, kind) for q in ("query", "key", "value")]
+                if all(pmap[nm][1] for nm in nms):
+                    t = sink.take_span([pmap[nm][0] for nm in nms])
+                    if t is not None:
+                        outs["attention.self.qkv." + kind] = t
+                        for nm in nms:
+                            sunk[nm] = pmap[nm][0]
+    dx, g = hip_layers.layer_backward(ctx.packed, ctx.saved, dy.contiguous(), mfma=not EXACT, d_align=d_align, outs=outs,
+                                      want_d_bias=ctx.need_bias)
+    ctx.saved = None
+    grads = [None if (n in sunk or not need) else g[n] for n, need in zip(BertLayerFn.NAMES, ctx.need)]
+    for prm in sunk.values():
+        sink.done(prm)
+    return (dx if ctx.need_x else None), tuple(grads), g.get("attn_bias")
+
+
+class BertLayerBiasFn(_NotedFn):
+    """BertLayerFn under an additive attention mask / bias and a head mask (the reference's attention_mask + head_mask arguments,
+    modeling_bert.py:55-68): attn_bias is any float tensor broadcastable to [N, A, S, S] and a DIFFERENTIABLE input -- its gradient
+    is the dense dS [N, A, S, S] of modcr_qkv_attn_bias_bwd summed to the bias's own shape; head_mask ([A], [N, A], ...) is a constant.
+    Either may be None, not both.  Same argument count before the parameters as BertLayerFn, same gradient-sink protocol."""
+
+    @staticmethod
+    def forward(ctx, x, attn_bias, head_mask, chunk_id, num_heads, eps, p, attn_p, packed, *params):
+        if attn_bias is None and head_mask is None:
+            raise ValueError("BertLayerBiasFn: neither attn_bias nor head_mask (that layer is BertLayerFn)")
+        ctx.bias_shape = None if attn_bias is None else (tuple(attn_bias.shape), attn_bias.dtype)
+        return _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, params, attn_bias=attn_bias, head_mask=head_mask)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx, grads, d_bias = _bert_layer_backward(ctx, dy)
+        if d_bias is not None:
+            shape, dtype = ctx.bias_shape
+            d_bias = d_bias.sum_to_size(shape).to(dtype)
+        return (dx, d_bias) + (None,) * 7 + grads
 
 
 class ResidualAddFn(torch.autograd.Function):

@@ -183,13 +183,21 @@ def attn_dropout_supported(x, num_heads):
 
 
 def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None, chunk_id=None, p=0.0, attn_p=0.0,
-                        align_map=None, align_t=0, side_post_dropout=True):
+                        align_map=None, align_t=0, side_post_dropout=True, attn_bias=None, head_mask=None):
     """p: hidden_dropout_prob of BertSelfOutput / BertOutput in training mode (a_bert:369-373, :446-451);
     attn_p: attention_probs_dropout_prob (modeling_bert.py:69), applied inside the attention kernels;
     align_map [N,T,R] fp32 (+= head-summed text->region probabilities of this layer, v10:982), align_t = T;
     side_post_dropout: the map sums the probabilities AFTER that dropout (v10:94-106, the reference's semantics) and its gradient
-    re-enters under the same mask; False = the un-dropped probabilities"""
+    re-enters under the same mask; False = the un-dropped probabilities;
+    attn_bias / head_mask: the additive float mask and the head multiplier of mh.qkv_attn(attn_bias=, head_mask=), instead of
+    key_mask / mask_bits.  Both are kept for the backward (modcr_qkv_attn_bias_bwd, S <= 256: it recomputes the row statistics, so
+    no lse / dump is written); no align map on this route."""
     n, s, h = x.shape
+    biased = attn_bias is not None or head_mask is not None
+    if biased and (key_mask is not None or mask_bits is not None):
+        raise ValueError("layer_forward_train: attn_bias / head_mask replace key_mask / mask_bits")
+    if biased and align_map is not None:
+        raise ValueError("layer_forward_train: no align map (and no align-map gradient) on the attn_bias / head_mask route")
     adrop = None
     if attn_p > 0.0:
         if not attn_dropout_supported(x, num_heads):
@@ -197,16 +205,20 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
         seed, off = mh.DROPOUT.take(n * num_heads * s * s)
         adrop = (float(attn_p), seed, off)
     # row statistics of the softmax for the five-product attention backward (csrc/attn_bwd.hip), where the forward runs a tile kernel
-    lse = torch.empty((n, num_heads, s), dtype=torch.float32, device=x.device) if mh.lse_supported(x, num_heads) else None
+    lse = torch.empty((n, num_heads, s), dtype=torch.float32, device=x.device) if not biased and mh.lse_supported(x, num_heads) else None
     # ... and the Q | K | V images the kernel held in LDS (72 KB per sequence and head at S = 180: 453 MB per layer at 128 examples,
     # 11 GB over 24 layers of the 288 GB), so that the backward recomputes no projection.
     dump = None
     if lse is not None and SAVE_QKV:
         dump = torch.empty((mh.qkv_dump_numel(n, s, num_heads),), dtype=torch.bfloat16, device=x.device)
     post = bool(side_post_dropout and adrop is not None and align_map is not None)
-    ctx, _ = mh.qkv_attn(x, layer["wqkv"], layer["bqkv"], key_mask=key_mask, mask_bits=mask_bits, chunk_id=chunk_id,
-                         num_heads=num_heads, attn_dropout=adrop, align_map=align_map, align_t=align_t, lse=lse, dump=dump,
-                         side_post_dropout=post)
+    if biased:
+        ctx, _ = mh.qkv_attn(x, layer["wqkv"], layer["bqkv"], chunk_id=chunk_id, num_heads=num_heads, attn_dropout=adrop,
+                             attn_bias=attn_bias, head_mask=head_mask)
+    else:
+        ctx, _ = mh.qkv_attn(x, layer["wqkv"], layer["bqkv"], key_mask=key_mask, mask_bits=mask_bits, chunk_id=chunk_id,
+                             num_heads=num_heads, attn_dropout=adrop, align_map=align_map, align_t=align_t, lse=lse, dump=dump,
+                             side_post_dropout=post)
     x2 = x.reshape(n * s, h)
     dt = mh.dt_of(x)
     pre1, a, drop1 = _sub_ln_fwd(ctx.reshape(n * s, h), layer["wo"], layer["bo"], x2, layer["ln1_g"], layer["ln1_b"], eps, p, dt)
@@ -220,7 +232,8 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
     pre2, y, drop2 = _sub_ln_fwd(inter, layer["w2"], layer["b2"], a, layer["ln2_g"], layer["ln2_b"], eps, p, dt)
     saved = dict(x=x, ctx=ctx, pre1=pre1, a=a, inter=inter, u=u, pre2=pre2, num_heads=num_heads, eps=eps,
                  key_mask=key_mask, mask_bits=mask_bits, chunk_id=chunk_id, drop1=drop1, drop2=drop2, adrop=adrop,
-                 align_t=align_t if align_map is not None else 0, lse=lse, dump=dump, side_post=post)
+                 align_t=align_t if align_map is not None else 0, lse=lse, dump=dump, side_post=post,
+                 attn_bias=attn_bias, head_mask=head_mask)
     return y.view(n, s, h), saved
 
 
@@ -238,13 +251,15 @@ def _sub_ln_bwd(dy, pre, a_in, w, gamma, eps, dgamma, dbeta, drop, mfma, dw_out=
     return d_pre, da, dw, db
 
 
-def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None):
+def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None, want_d_bias=False):
     """dy [N,S,H] -> (dx [N,S,H] in x's dtype, {HF parameter name: fp32 gradient}).  Four C-ABI composites:
     modcr_ffn_down_residual_ln_bwd, modcr_ffn_up_gelu_bwd, modcr_proj_residual_ln_bwd, modcr_qkv_attn_bwd
     (the two residual-gradient sums ride in the epilogues of the dX GEMMs).  `mfma` is implied by the storage dtype (bf16 = MFMA route).
     outs: {HF parameter name: fp32 tensor} -- gradients listed there are WRITTEN into the given tensor (dense weights / biases: a view of
     the flat gradient buffer on its first use in an accumulation window) or ACCUMULATED into it (the four LayerNorm parameters: the
-    kernels add) instead of into a fresh tensor; the returned dict holds the same tensor objects."""
+    kernels add) instead of into a fresh tensor; the returned dict holds the same tensor objects.
+    want_d_bias (a layer that ran with attn_bias): the dict also holds "attn_bias", the fp32 [N, A, S, S] gradient of the DENSE bias
+    (dS of every sequence and head; the caller reduces it to the bias's own shape)."""
     outs = outs or {}
     x, ctx, a, inter = saved["x"], saved["ctx"], saved["a"], saved["inter"]
     n, s, h = x.shape
@@ -296,13 +311,23 @@ def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None):
     dwqkv, dbqkv = outs.get("attention.self.qkv.weight"), outs.get("attention.self.qkv.bias")      # (spans of the flat gradient buffer)
     dwqkv = dwqkv.view(3 * h, h) if dwqkv is not None else torch.empty(3 * h, h, dtype=f32, device=dev)
     dbqkv = dbqkv if dbqkv is not None else torch.empty(3 * h, dtype=f32, device=dev)
-    dx = mh.qkv_attn_bwd(d_ctx.view(n, s, h), x, layer["wqkv"], layer["bqkv"], dwqkv, dbqkv,
-                         key_mask=saved["key_mask"], mask_bits=saved["mask_bits"], chunk_id=saved["chunk_id"],
-                         num_heads=saved["num_heads"], attn_dropout=saved.get("adrop"),
-                         d_align=d_align if saved.get("align_t") else None, align_t=saved.get("align_t", 0),
-                         dx_residual=d_pre1.view(n, s, h),
-                         ctx=ctx if saved.get("lse") is not None else None, lse=saved.get("lse"), dump=saved.get("dump"),
-                         side_post_dropout=bool(saved.get("side_post")))
+    if saved.get("attn_bias") is not None or saved.get("head_mask") is not None:
+        if want_d_bias and saved.get("attn_bias") is None:
+            raise ValueError("layer_backward: want_d_bias for a layer that ran without attn_bias")
+        d_bias = torch.empty((n, saved["num_heads"], s, s), dtype=f32, device=dev) if want_d_bias else None
+        dx = mh.qkv_attn_bwd(d_ctx.view(n, s, h), x, layer["wqkv"], layer["bqkv"], dwqkv, dbqkv, chunk_id=saved["chunk_id"],
+                             num_heads=saved["num_heads"], attn_dropout=saved.get("adrop"), dx_residual=d_pre1.view(n, s, h),
+                             attn_bias=saved.get("attn_bias"), head_mask=saved.get("head_mask"), d_bias=d_bias)
+        if want_d_bias:
+            g["attn_bias"] = d_bias
+    else:
+        dx = mh.qkv_attn_bwd(d_ctx.view(n, s, h), x, layer["wqkv"], layer["bqkv"], dwqkv, dbqkv,
+                             key_mask=saved["key_mask"], mask_bits=saved["mask_bits"], chunk_id=saved["chunk_id"],
+                             num_heads=saved["num_heads"], attn_dropout=saved.get("adrop"),
+                             d_align=d_align if saved.get("align_t") else None, align_t=saved.get("align_t", 0),
+                             dx_residual=d_pre1.view(n, s, h),
+                             ctx=ctx if saved.get("lse") is not None else None, lse=saved.get("lse"), dump=saved.get("dump"),
+                             side_post_dropout=bool(saved.get("side_post")))
     for i, nm in enumerate(("query", "key", "value")):
         g["attention.self.%s.weight" % nm] = dwqkv[i * h:(i + 1) * h]
         g["attention.self.%s.bias" % nm] = dbqkv[i * h:(i + 1) * h]

@@ -10,6 +10,8 @@ that every block is a torch.autograd.Function whose backward is the matching C-A
     layers       BertLayerFn: modcr_qkv_attn_fwd / modcr_qkv_attn_bwd with the padding mask (global_enc, seq_enc
                  layers 3-8), the phase-1 bit mask (seq_enc 0-2) or the phase-3 bit mask + chunk-mean queries
                  (seq_enc 9-11), then the projection / FFN composites
+                 BertLayerBiasFn (encoder_layers): modcr_qkv_attn_bias_fwd / modcr_qkv_attn_bias_bwd under any additive float
+                 mask and a head mask, the mask a differentiable input
     pooler       LinearFn with the tanh epilogue on the [CLS] row
 
 The align map (sum of the last three seq_enc layers' text->region probabilities over all heads) is a differentiable
@@ -88,6 +90,41 @@ def _run_layer(model, i, layer, hidden, key_mask=None, mask_bits=None, chunk_id=
         packed = dict(packed, _align=align, _side_post=bool(getattr(cfg, "modcr_align_map_post_dropout", True)))
     return ag.BertLayerFn.apply(hidden, key_mask, mask_bits, chunk_id, cfg.num_attention_heads, cfg.layer_norm_eps, float(p), float(ap),
                                 packed, *params)
+
+
+def _run_layer_bias(model, i, layer, hidden, attn_bias, head_mask):
+    """_run_layer under an additive float mask / bias and a head mask (hip_autograd.BertLayerBiasFn)"""
+    cfg = model.config
+    params = _layer_params(layer)
+    p = cfg.hidden_dropout_prob if model.training else 0.0
+    ap = getattr(cfg, "attention_probs_dropout_prob", 0.0) if model.training else 0.0
+    packed = _packed(model, i, layer, params, hidden.device, hidden.dtype)
+    return ag.BertLayerBiasFn.apply(hidden, attn_bias, head_mask, None, cfg.num_attention_heads, cfg.layer_norm_eps, float(p), float(ap),
+                                    packed, *params)
+
+
+def encoder_layers(model, hidden, attention_mask, head_mask=None):
+    """CaptionBertEncoder.forward(hidden_states, attention_mask, head_mask) with gradients: the layers of model.encoder over
+    hidden [N,S,H] (storage dtype) under the reference's 4-D ADDITIVE attention_mask (broadcastable to [N,A,S,S]) and
+    head_mask[i] per layer (None, or a sequence / tensor indexed by layer; an entry may be None).  A 0 / -10000 mask on a layer
+    without head mask runs _run_layer with the binary mask, as global_encoder does; anything else -- a soft bias, -5000, -inf, a
+    per-head mask, a head mask -- runs the bias form, and attention_mask is then a differentiable input."""
+    from .modeling_bert import split_additive_mask
+    n, s, _ = hidden.shape
+    plain = None                                            # the split of the mask alone (one reduction and one host read)
+    for i, layer in enumerate(model.encoder.layer):
+        hm = None if head_mask is None else head_mask[i]
+        if hm is None:
+            if plain is None:
+                plain = split_additive_mask(attention_mask, n, s, s)
+            args = plain
+        else:
+            args = dict(attn_bias=attention_mask, head_mask=hm)
+        if "attn_bias" in args:
+            hidden = _run_layer_bias(model, i, layer, hidden, args["attn_bias"], args["head_mask"])
+        else:
+            hidden = _run_layer(model, i, layer, hidden, **args)
+    return hidden
 
 
 def global_encoder(model, input_ids, token_type_ids, attention_mask, position_ids, img_feats):
