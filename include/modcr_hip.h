@@ -473,6 +473,29 @@ int modcr_qkv_attn_bias_bwd(const void* dctx, const void* x, const void* wqkv, c
                             const float* dx_residual, void* dx, float* dwqkv, float* dbqkv, int32_t accumulate, float* d_bias,
                             int32_t N, int32_t S, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset,
                             void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
+/* Backward of modcr_qkv_attn_bias_fwd WITH prefix rows (hist [N, P, H], P >= 1; the forward's encoder_history_states): S queries
+ * against L = P + S <= 256 keys, keys j < P the prefix rows, keys j >= P the sequence's own rows.  bf16 and fp32.
+ *   hist      [N, P, H] in the storage dtype: the forward's prefix rows.  They take part as keys and values only: they are projected
+ *             with rows H..3H of wqkv / bqkv (no Q projection), receive dK and dV and no dQ.
+ *   d_hist    [N, P, H] in the storage dtype, written: d(k|v)_prefix . Wqkv[H:3H].
+ *   dx        [N, S, H], written: dqkv . Wqkv (+ dx_residual, fp32 or NULL).
+ *   dwqkv / dbqkv: the own rows' product is written (accumulate = 0) or added (accumulate != 0); the prefix rows' contribution is
+ *             then added into rows H..3H.
+ *   attn_bias / bias_stride_* / head_mask / head_mask_stride_n: as modcr_qkv_attn_bias_bwd, the key dimension being L.
+ *   d_bias    fp32 contiguous [N, A, S, L] or NULL, as modcr_qkv_attn_bias_bwd's (one lane per element, no atomics).
+ *   attn_p, seed, offset: the forward's dropout; the mask is that of counter row (n A + a) x 256 + query, key index over [hist ; x].
+ * No chunk mean and no align-map gradient.  Cores (csrc/attn_prefix_bwd.hip): attn_prefix_bwd_mfma_kernel (bf16, L <= 192) or the
+ * exact attn_prefix_bwd_f32_kernel (fp32; bf16 with 192 < L <= 256); modcr_qkv_attn_prefix_bwd_route says which without launching:
+ * 0 = refused, 1 = MFMA core, 2 = exact core.  Every argument is validated before the first launch: P = 0 or hist == NULL returns
+ * MODCR_ERR_INVALID (that call belongs to modcr_qkv_attn_bias_bwd), P + S > 256 returns MODCR_ERR_UNSUPPORTED. */
+int64_t modcr_qkv_attn_prefix_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype);
+int modcr_qkv_attn_prefix_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype);
+int modcr_qkv_attn_prefix_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                              const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                              const float* head_mask, int64_t head_mask_stride_n, const float* dx_residual, void* dx, void* d_hist,
+                              float* dwqkv, float* dbqkv, int32_t accumulate, float* d_bias, int32_t N, int32_t S, int32_t P,
+                              int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, void* workspace,
+                              int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
 
 /* ---- backward of the encoder layer's GEMM blocks (autograd of BertSelfOutput / BertIntermediate / BertOutput,
  * a_bert:362-373, :425-437, :440-451).  Gradients of parameters are fp32; dgamma / dbeta are ACCUMULATED (caller

@@ -2818,3 +2818,96 @@ extern "C" int modcr_qkv_attn_bias_bwd(const void* dctx, const void* x, const vo
     if (rc != MODCR_OK) return rc;
     return modcr_linear_bwd_weight(dqkv, 3 * H, qdt, x, H, dwqkv, dbqkv, M, 3 * H, H, accumulate, dtype, sub, sub_bytes, stream);
 }
+
+// ---- backward of modcr_qkv_attn_bias_fwd WITH prefix rows (hist [N, P, H], P >= 1, P + S <= 256; no chunk mean, no align-map gradient) ----
+// The body is modcr_qkv_attn_bias_bwd's, step for step, with the rectangular cores of attn_prefix_bwd.hip in step 2 and a second,
+// K | V only set of GEMMs for the prefix rows: rows H..3H of wqkv / bqkv are a contiguous [2H, H] sub-block (ldw = H).
+static int64_t attn_prefix_bwd_sub_ws(int32_t N, int32_t S, int32_t P, int32_t H) {
+    const int64_t a = modcr_linear_bwd_input_workspace(N * P, 2 * H, H), b = modcr_linear_bwd_weight_workspace(N * P, 2 * H, H);
+    const int64_t h = ((a > b ? a : b) + 255) & ~(int64_t)255, x = attn_bwd_sub_ws(N * S, H);
+    return h > x ? h : x;
+}
+extern "C" int64_t modcr_qkv_attn_prefix_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
+    (void)dtype;
+    if (N <= 0 || S <= 0 || P <= 0 || H <= 0) return 0;
+    const int64_t rows_x = (((int64_t)N * S * 3 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
+    const int64_t rows_h = (((int64_t)N * P * 2 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
+    return 2 * rows_x + 2 * rows_h + attn_prefix_bwd_sub_ws(N, S, P, H);
+}
+
+// 0 = refused, 1 = attn_prefix_bwd_mfma_kernel, 2 = attn_prefix_bwd_f32_kernel
+extern "C" int modcr_qkv_attn_prefix_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype) {
+    if (N <= 0 || S <= 0 || P <= 0 || (int64_t)P + S > 256 || A <= 0 || H != A * 64 || (dtype != MODCR_BF16 && dtype != MODCR_F32)) return 0;
+    return dtype == MODCR_BF16 && P + S <= AB::LP ? 1 : 2;
+}
+
+extern "C" int modcr_qkv_attn_prefix_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                                         const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                                         const float* head_mask, int64_t head_mask_stride_n, const float* dx_residual, void* dx, void* d_hist,
+                                         float* dwqkv, float* dbqkv, int32_t accumulate, float* d_bias, int32_t N, int32_t S, int32_t P, int32_t H,
+                                         int32_t A, float attn_p, uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes,
+                                         int32_t dtype, modcr_stream_t stream) {
+    const char* who = "qkv_attn_prefix_bwd";
+    MODCR_REQUIRE(P >= 1 && hist, "%s: no prefix rows (P=%d, hist %s): that call belongs to modcr_qkv_attn_bias_bwd", who, P, hist ? "given" : "null");
+    MODCR_REQUIRE(dctx && x && wqkv && bqkv && dx && d_hist && dwqkv && dbqkv, "%s: null pointer", who);
+    MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "%s: unknown dtype %d", who, dtype);
+    MODCR_REQUIRE(N > 0 && S > 0 && A > 0, "%s: bad shape (N=%d S=%d P=%d H=%d A=%d)", who, N, S, P, H, A);
+    MODCR_REQUIRE(H == A * 64, "%s: head size must be 64 (H=%d, A=%d)", who, H, A);
+    if ((int64_t)P + S > 256) {
+        modcr_set_error("%s: P + S = %lld keys exceeds the 256-key limit of the attention backward", who, (long long)P + S);
+        return MODCR_ERR_UNSUPPORTED;
+    }
+    MODCR_REQUIRE(attn_bias || head_mask, "%s: neither bias nor head_mask", who);
+    MODCR_REQUIRE(attn_bias || !d_bias, "%s: d_bias without a bias", who);
+    MODCR_REQUIRE(attn_p >= 0.f && attn_p < 1.f, "%s: attention dropout p=%g out of [0, 1)", who, attn_p);
+    MODCR_REQUIRE(bias_stride_n >= 0 && bias_stride_a >= 0 && bias_stride_q >= 0 && head_mask_stride_n >= 0, "%s: negative stride", who);
+    // (the cores address a (sequence, head) slice of the bias with 32-bit element offsets)
+    MODCR_REQUIRE(bias_stride_q <= (1 << 20), "%s: bias query stride %lld exceeds 2^20 elements", who, (long long)bias_stride_q);
+    MODCR_REQUIRE(((uintptr_t)attn_bias & 3) == 0 && ((uintptr_t)head_mask & 3) == 0 && ((uintptr_t)d_bias & 3) == 0,
+                  "%s: bias / head_mask / d_bias not 4-byte aligned", who);
+    MODCR_REQUIRE(dtype != MODCR_BF16 || (modcr_aligned16(dctx) && modcr_aligned16(x) && modcr_aligned16(hist) && modcr_aligned16(wqkv) &&
+                                          modcr_aligned16(dx) && modcr_aligned16(d_hist)),
+                  "%s(bf16): 16-byte alignment", who);
+    const int64_t need = modcr_qkv_attn_prefix_bwd_workspace(N, S, P, H, dtype);
+    MODCR_REQUIRE(workspace && workspace_bytes >= need && modcr_aligned16(workspace), "%s: workspace %lld < %lld bytes (or unaligned)", who,
+                  (long long)workspace_bytes, (long long)need);
+    const int core = modcr_qkv_attn_prefix_bwd_route(N, S, P, H, A, dtype);
+    const int M = N * S, Mh = N * P;
+    const int64_t rows_x = (((int64_t)M * 3 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
+    const int64_t rows_h = (((int64_t)Mh * 2 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
+    char* w = (char*)workspace;
+    void* qkv = w;
+    void* dqkv = w + rows_x;
+    void* kvh = w + 2 * rows_x;
+    void* dkvh = w + 2 * rows_x + rows_h;
+    void* sub = dtype == MODCR_BF16 ? (void*)(w + 2 * rows_x + 2 * rows_h) : nullptr;
+    const int64_t sub_bytes = dtype == MODCR_BF16 ? attn_prefix_bwd_sub_ws(N, S, P, H) : 0;
+    const size_t esz = dtype == MODCR_BF16 ? 2 : 4;
+    const void* wkv = (const char*)wqkv + (size_t)H * H * esz;                  // rows H..3H of wqkv: the K | V projection [2H, H]
+    // 1. recompute the rows (MFMA core: bf16, exact core: fp32): q | k | v of the own rows, k | v of the prefix rows
+    const int32_t qdt = core == 1 ? MODCR_BF16 : MODCR_F32;
+    int rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, qkv, 3 * H, M, 3 * H, H, MODCR_ACT_NONE, dtype, qdt, stream);
+    if (rc != MODCR_OK) return rc;
+    rc = modcr_linear_fwd(hist, H, wkv, H, bqkv + H, nullptr, 0, 0, kvh, 2 * H, Mh, 2 * H, H, MODCR_ACT_NONE, dtype, qdt, stream);
+    if (rc != MODCR_OK) return rc;
+    // 2. attention core backward
+    AttnPrefixBwdArgs b;
+    b.qkv = qkv; b.kvh = kvh; b.dctx = dctx; b.dqkv = dqkv; b.dkvh = dkvh;
+    b.bias = attn_bias; b.bias_sn = bias_stride_n; b.bias_sa = bias_stride_a; b.bias_sq = bias_stride_q;
+    b.head_mask = head_mask; b.head_mask_sn = head_mask_stride_n;
+    b.d_bias = d_bias;
+    const AttnDrop d = attn_drop(attn_p, seed, offset);     // (as the forward)
+    b.drop_thr16 = d.thr16; b.drop_key = d.key; b.drop_keep = d.keep;
+    b.N = N; b.S = S; b.P = P; b.H = H; b.A = A;
+    rc = modcr_launch_attn_prefix_bwd(b, core, dtype, (hipStream_t)stream);
+    if (rc != MODCR_OK) return rc;
+    // 3. own rows: dX = dqkv . Wqkv (+ dx_residual);  dWqkv (+)= dqkv^T . X;  dbqkv (+)= column sums
+    rc = modcr_linear_bwd_input_res(dqkv, 3 * H, qdt, wqkv, H, dx_residual, H, dx, H, M, 3 * H, H, dtype, dtype, sub, sub_bytes, stream);
+    if (rc != MODCR_OK) return rc;
+    rc = modcr_linear_bwd_weight(dqkv, 3 * H, qdt, x, H, dwqkv, dbqkv, M, 3 * H, H, accumulate, dtype, sub, sub_bytes, stream);
+    if (rc != MODCR_OK) return rc;
+    // 4. prefix rows, K | V only: d_hist = d(k|v) . Wqkv[H:3H];  dWqkv[H:3H] += d(k|v)^T . hist;  dbqkv[H:3H] += column sums
+    rc = modcr_linear_bwd_input_res(dkvh, 2 * H, qdt, wkv, H, nullptr, 0, d_hist, H, Mh, 2 * H, H, dtype, dtype, sub, sub_bytes, stream);
+    if (rc != MODCR_OK) return rc;
+    return modcr_linear_bwd_weight(dkvh, 2 * H, qdt, hist, H, dwqkv + (size_t)H * H, dbqkv + H, Mh, 2 * H, H, 1, dtype, sub, sub_bytes, stream);
+}

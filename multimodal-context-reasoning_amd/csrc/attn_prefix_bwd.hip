@@ -1,0 +1,504 @@
+// Attention core backward with PREFIX rows (history_state) under an additive fp32 bias and a head mask (CDNA4 / gfx950; head size
+// 64, P > 0 prefix keys, S queries, L = P + S <= 256 keys): the backward of modcr_qkv_attn_bias_fwd's arithmetic with prefix rows.
+// Per (sequence n, head a), keys j < P are the prefix rows, keys j >= P the sequence's own rows (the forward's order):
+//     s_ij = q_i.k_j / 8 + bias[n, a, i, j]     P = softmax_j(s)     P' = P o m / (1 - p)     P'' = hm[n, a] P'     ctx = P''.V
+//     dV = P''^T.dctx     dP = hm (m / (1 - p)) o (dctx.V^T)     dS = P o (dP - rowsum(dP o P))
+//     dQ = dS.K / 8  [S rows]     dK = dS^T.Q / 8  [L rows]     d_bias = dS  [N, A, S, L]
+// The cores are those of attn_bias_bwd.hip made rectangular -- attn_prefix_bwd_mfma_kernel is attn_bias_bwd_mfma_kernel (bf16 rows,
+// L <= 192), attn_prefix_bwd_f32_kernel is attn_bias_bwd_f32_kernel (fp32 rows, L <= 256) -- with
+//   * the K | V images (pass A: K, V in LDS) holding L rows from TWO row buffers: the prefix rows' k | v projection [N*P][2H] and the
+//     own rows' q | k | v projection [N*S][3H]; the Qs | dO images (pass B: Q, dO in LDS) holding S rows;
+//   * the sub-pass that owns the QUERIES writing dQ for S rows and d_bias rows of length L, the sub-pass that owns the KEYS writing
+//     dK | dV for L rows: the first P to the prefix gradient rows [N*P][2H], the rest to the own rows' dq | dk | dv [N*S][3H];
+//   * the dropout mask of the forward: counter row (n A + a) x 256 + QUERY index (0 .. S - 1), key index over [prefix ; x];
+//   * the conventions of attn_bias_bwd.hip otherwise: keys beyond L carry -inf, a query row whose every key is -inf has P = 0 and adds
+//     exactly nothing, hm is a factor of every result (hm = 0: everything exactly 0), every output element is written by exactly one
+//     lane -- no atomics, two launches are bit-identical.
+#include "common.h"
+#include "attn_common.h"
+
+namespace {
+
+struct APB {
+    static constexpr int LP = 192, NT = 384;
+    static constexpr int ROWS = LP * 128;                   // [token][64] bf16, 128-byte rows, swz128
+    static constexpr int IMG = 2 * ROWS;                    // sub-pass Q: K | V    sub-pass K: Qs | dO
+    static constexpr int SMEM = IMG + 3 * LP * 4;           // + row max, 1 / row sum, delta
+};
+
+typedef __attribute__((address_space(3))) bf16x4* lds_tr_b;
+
+// Transposed fragment of a row image (attn_bias_bwd.hip's): feature 16 db + l15, tokens tok0 + 4 l4 + {0..3} and tok0 + 16 + 4 l4 + {0..3}
+__device__ __forceinline__ bf16x8 apb_tr8(const unsigned char* img, int tok0, int db, int l15, int l4) {
+    const int r = tok0 + 4 * l4 + (l15 >> 2);
+    const int ch = db * 2 + ((l15 & 3) >> 1), within = (l15 & 1) * 8;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_tr_b)(img + swz128(r, ch) + within));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_tr_b)(img + swz128(r + 16, ch) + within));
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { o[e] = lo[e]; o[4 + e] = hi[e]; }
+    return o;
+}
+
+// BIAS: a bias is given (else the head mask alone); DBIAS: dS leaves as d_bias.
+template <bool BIAS, bool DBIAS>
+__global__ __launch_bounds__(384, 3) void attn_prefix_bwd_mfma_kernel(AttnPrefixBwdArgs p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int LP = APB::LP;
+    unsigned char* img0 = smem;                             // rows image 0 (K | Qs)
+    unsigned char* img1 = smem + APB::ROWS;                 // rows image 1 (V | dO)
+    float* sM = reinterpret_cast<float*>(smem + APB::IMG);
+    float* sInv = sM + LP;
+    float* sDl = sInv + LP;
+    const int S = p.S, P = p.P, L = p.S + p.P, H = p.H;
+    const int n = blockIdx.x / p.A, a = blockIdx.x % p.A;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15_ = lane & 15, l4_ = lane >> 4;
+    const bf16* qkv = reinterpret_cast<const bf16*>(p.qkv) + (int64_t)n * S * 3 * H + a * 64;      // own rows: q | k | v
+    const bf16* kvh = reinterpret_cast<const bf16*>(p.kvh) + (int64_t)n * P * 2 * H + a * 64;      // prefix rows: k | v
+    const bf16* dctx = reinterpret_cast<const bf16*>(p.dctx) + (int64_t)n * S * H + a * 64;
+    const float* bias = BIAS ? p.bias + (int64_t)n * p.bias_sn + (int64_t)a * p.bias_sa : nullptr;
+    float* dbias = DBIAS ? p.d_bias + ((int64_t)n * p.A + a) * S * L : nullptr;
+    constexpr float QS = 0.125f * LOG2E;
+    // (hm enters where the results are stored: attn_bias_bwd_mfma_kernel)
+    const float hm = p.head_mask ? p.head_mask[(int64_t)n * p.head_mask_sn + a] : 1.0f;
+    const uint32_t dthr = p.drop_thr16;
+
+    auto zero8 = [] {
+        bf16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (bf16)0.f;
+        return o;
+    };
+    // 8 consecutive features of KEY j's k (part 0) or v (part 1) row: prefix rows first, then the own rows; zeros beyond L
+    auto kv8 = [&](int j, int part, int c) {
+        if (j >= L) return zero8();
+        const bf16* row = j < P ? kvh + (int64_t)j * 2 * H + part * H : qkv + (int64_t)(j - P) * 3 * H + (1 + part) * H;
+        return *reinterpret_cast<const bf16x8*>(row + c * 8);
+    };
+    // ... of QUERY i's q row scaled by log2e / 8 and rounded again, or of its dctx row; zeros beyond S
+    auto q8 = [&](int i, int c) {
+        if (i >= S) return zero8();
+        bf16x8 o = *reinterpret_cast<const bf16x8*>(qkv + (int64_t)i * 3 * H + c * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (bf16)((float)o[e] * QS);
+        return o;
+    };
+    auto do8 = [&](int i, int c) { return i < S ? *reinterpret_cast<const bf16x8*>(dctx + (int64_t)i * H + c * 8) : zero8(); };
+    auto put_rows = [&](unsigned char* img, int t, int c, const bf16x8& v) { *reinterpret_cast<bf16x8*>(img + swz128(t, c)) = v; };
+    // score init (log2 domain) of query q, key: the bias, -inf on a padded key.  A padded query row takes the bias of row S - 1 in
+    // both sub-passes: its probabilities are finite and consistent, its dO is zero.
+    const uint32_t bsq = (uint32_t)p.bias_sq;
+    auto init1 = [&](int q, int key) {
+        if (key >= L) return -INFINITY;
+        if (!BIAS) return 0.f;
+        return bias[(uint32_t)min(q, S - 1) * bsq + (uint32_t)key] * LOG2E;
+    };
+
+    // ---- the images of sub-pass Q: K | V, L rows --------------------------------------------------------------------
+    for (int it = tid; it < LP * 8; it += APB::NT) {
+        const int t = it >> 3, c = it & 7;
+        put_rows(img0, t, c, kv8(t, 0, c));
+        put_rows(img1, t, c, kv8(t, 1, c));
+    }
+    __syncthreads();
+
+    const int t0 = wave * 32;                               // this wave's queries (sub-pass Q) / keys (sub-pass K)
+    // ---- sub-pass Q: one 16-query block at a time (its 16 x 192 scores = 48 registers); a wave whose 32 queries all lie beyond S
+    // has nothing to do (sub-pass K reads the statistics of the 32-query tiles below S only) ----------------------------------
+#pragma unroll 1
+    for (int qb = 0; qb < (t0 < S ? 2 : 0); ++qb) {
+        int l15 = l15_, l4 = l4_;
+        asm volatile("" : "+v"(l15), "+v"(l4));
+        const int qrow = t0 + qb * 16 + l15;
+        bf16x8 fq[2], fdo[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            fq[ks] = q8(qrow, ks * 4 + l4);
+            fdo[ks] = do8(qrow, ks * 4 + l4);
+        }
+        // the lane's bias values: query qrow, keys 32 kt + 16 kb + 4 l4 + {0..3}; every load is issued before the first product
+        f32x4 sc[6][2];
+#pragma unroll
+        for (int kt = 0; kt < 6; ++kt)
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sc[kt][kb][e] = init1(qrow, kt * 32 + kb * 16 + 4 * l4 + e);
+#pragma unroll
+        for (int kt = 0; kt < 6; ++kt)
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                const int krow = kt * 32 + kb * 16;
+                const bf16x8 fk0 = *reinterpret_cast<const bf16x8*>(img0 + swz128(krow + l15, l4));
+                const bf16x8 fk1 = *reinterpret_cast<const bf16x8*>(img0 + swz128(krow + l15, 4 + l4));
+                f32x4 c = sc[kt][kb];
+                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk0, fq[0], c, 0, 0, 0);
+                sc[kt][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk1, fq[1], c, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);          // no hoisting of the next blocks' fragment reads: registers
+            }
+        {
+            float m = -INFINITY;
+#pragma unroll
+            for (int kt = 0; kt < 6; ++kt)
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) m = fmaxf(m, sc[kt][kb][e]);
+            m = fmaxf(m, __shfl_xor(m, 16, 64));
+            m = fmaxf(m, __shfl_xor(m, 32, 64));
+            if (m == -INFINITY) m = 0.f;                    // every key at -inf: exponentials against 0, all of them 0
+            float l = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < 6; ++kt)
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { const float ex = __builtin_amdgcn_exp2f(sc[kt][kb][e] - m); sc[kt][kb][e] = ex; l += ex; }
+            l += __shfl_xor(l, 16, 64);
+            l += __shfl_xor(l, 32, 64);
+            const float inv = l > 0.f ? 1.0f / l : 0.f;     // ... and the row's probabilities are 0, not 0 / 0
+#pragma unroll
+            for (int kt = 0; kt < 6; ++kt)
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sc[kt][kb][e] *= inv;
+            if (l4 == 0) { sM[qrow] = m; sInv[qrow] = inv; }
+        }
+        // ctx = hm (P o m / (1 - p)) V, so dP = hm m / (1 - p) o (dO V^T); without hm here
+        const uint32_t dbase = attn_drop_base((uint32_t)((n * p.A + a) * 256 + qrow), (uint32_t)l4, p.drop_key);
+        auto dp_masked = [&](int kt, int kb) {
+            const int krow = kt * 32 + kb * 16;
+            const bf16x8 fv0 = *reinterpret_cast<const bf16x8*>(img1 + swz128(krow + l15, l4));
+            const bf16x8 fv1 = *reinterpret_cast<const bf16x8*>(img1 + swz128(krow + l15, 4 + l4));
+            f32x4 dp = {0.f, 0.f, 0.f, 0.f};
+            dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv0, fdo[0], dp, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv1, fdo[1], dp, 0, 0, 0);
+            if (dthr) {
+                const uint32_t hx = attn_drop_word(dbase, (2 * kt + kb) * 2, p.drop_key);
+                const uint32_t hy = attn_drop_word(dbase, (2 * kt + kb) * 2 + 1, p.drop_key);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dp[e] *= attn_keep_field(hx, hy, e, dthr) ? p.drop_keep : 0.f;
+            }
+            return dp;
+        };
+        float dl = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < 6; ++kt)
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                const f32x4 dp = dp_masked(kt, kb);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dl += sc[kt][kb][e] * dp[e];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        dl += __shfl_xor(dl, 16, 64);
+        dl += __shfl_xor(dl, 32, 64);
+        if (l4 == 0) sDl[qrow] = dl;
+        f32x4 dq[4];
+#pragma unroll
+        for (int db = 0; db < 4; ++db) dq[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // (16-byte stores of d_bias where the row pieces are aligned: L % 4 == 0 and an aligned base)
+        const bool dvec = DBIAS && (L & 3) == 0 && ((uintptr_t)p.d_bias & 15) == 0;
+#pragma unroll
+        for (int kt = 0; kt < 6; ++kt) {
+            bf16x8 dsb;
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                const f32x4 dp = dp_masked(kt, kb);
+                f32x4 ds;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { ds[e] = sc[kt][kb][e] * (dp[e] - dl); dsb[4 * kb + e] = (bf16)ds[e]; }
+                if (DBIAS && qrow < S) {
+                    const int key0 = kt * 32 + kb * 16 + 4 * l4;
+                    float* at = dbias + (int64_t)qrow * L + key0;
+                    if (dvec && key0 < L) *reinterpret_cast<f32x4*>(at) = ds * hm;
+                    else
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (key0 + e < L) at[e] = ds[e] * hm;
+                }
+            }
+#pragma unroll
+            for (int db = 0; db < 4; ++db)
+                dq[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(apb_tr8(img0, kt * 32, db, l15, l4), dsb, dq[db], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const float qscale = 0.125f * hm;
+        if (qrow < S) {
+            bf16* oq = reinterpret_cast<bf16*>(p.dqkv) + ((int64_t)n * S + qrow) * 3 * H + a * 64 + 4 * l4;
+#pragma unroll
+            for (int db = 0; db < 4; ++db) {
+                const f32x4 o = dq[db];
+                *reinterpret_cast<bf16x4*>(oq + db * 16) =
+                    bf16x4{(bf16)(o[0] * qscale), (bf16)(o[1] * qscale), (bf16)(o[2] * qscale), (bf16)(o[3] * qscale)};
+            }
+        }
+    }
+    __syncthreads();
+    // ---- images of sub-pass K: Qs rows, dO rows (S of them) -------------------------------------------------------
+    for (int it = tid; it < LP * 8; it += APB::NT) {
+        const int t = it >> 3, c = it & 7;
+        put_rows(img0, t, c, q8(t, c));
+        put_rows(img1, t, c, do8(t, c));
+    }
+    __syncthreads();
+    const int qtiles = (S + 31) >> 5;                       // 32-query tiles that hold a query
+    // ---- sub-pass K: one 16-key block at a time; blocks beyond L hold no key ------------------------------------------
+#pragma unroll 1
+    for (int kb = 0; kb < 2; ++kb) {
+        if (t0 + kb * 16 >= L) break;
+        const int key = t0 + kb * 16 + l15_;
+        bf16x8 fkk[2], fvv[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            fkk[ks] = kv8(key, 0, ks * 4 + l4_);
+            fvv[ks] = kv8(key, 1, ks * 4 + l4_);
+        }
+        f32x4 dk[4], dv[4];
+#pragma unroll
+        for (int db = 0; db < 4; ++db) { dk[db] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[db] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        const float kpad = key < L ? 0.f : -INFINITY;
+        const int keyc = min(key, L - 1);
+#pragma unroll 1
+        for (int qt = 0; qt < qtiles; ++qt) {
+            int l15 = l15_, l4 = l4_;
+            asm volatile("" : "+v"(l15), "+v"(l4));
+            // the lane's bias values of the 32-query tile: key `key`, queries 32 qt + 16 qb + 4 l4 + {0..3} (a padded query takes row
+            // S - 1, as in sub-pass Q); requested ahead of the products, added after them
+            f32x4 bq[2];
+            if constexpr (BIAS) {
+#pragma unroll
+                for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) bq[qb][e] = bias[(uint32_t)min(qt * 32 + qb * 16 + 4 * l4 + e, S - 1) * bsq + (uint32_t)keyc];
+            }
+            bf16x8 pB, dsB;
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) {
+                const int qrow = qt * 32 + qb * 16;
+                const bf16x8 fq0 = *reinterpret_cast<const bf16x8*>(img0 + swz128(qrow + l15, l4));
+                const bf16x8 fq1 = *reinterpret_cast<const bf16x8*>(img0 + swz128(qrow + l15, 4 + l4));
+                const bf16x8 fd0 = *reinterpret_cast<const bf16x8*>(img1 + swz128(qrow + l15, l4));
+                const bf16x8 fd1 = *reinterpret_cast<const bf16x8*>(img1 + swz128(qrow + l15, 4 + l4));
+                const f32x4 m4 = *reinterpret_cast<const f32x4*>(sM + qrow + 4 * l4);
+                const f32x4 i4 = *reinterpret_cast<const f32x4*>(sInv + qrow + 4 * l4);
+                const f32x4 d4 = *reinterpret_cast<const f32x4*>(sDl + qrow + 4 * l4);
+                f32x4 c = {kpad, kpad, kpad, kpad};
+                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fq0, fkk[0], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fq1, fkk[1], c, 0, 0, 0);
+                f32x4 dp = {0.f, 0.f, 0.f, 0.f};
+                dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd0, fvv[0], dp, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd1, fvv[1], dp, 0, 0, 0);
+                // dropout: a lane's four values are four queries of ONE key, four hash counters; each lane of a quad hashes one
+                // and they are exchanged by quad broadcasts (attn_bwd_mfma_kernel)
+                uint32_t hqx = 0, hqy = 0;
+                if (dthr) attn_drop_words((uint32_t)((n * p.A + a) * 256 + qrow + 4 * l4 + (l15 & 3)), key >> 2, p.drop_key, hqx, hqy);
+                const uint32_t xq[4] = {quad_bcast<0>(hqx), quad_bcast<1>(hqx), quad_bcast<2>(hqx), quad_bcast<3>(hqx)};
+                const uint32_t yq[4] = {quad_bcast<0>(hqy), quad_bcast<1>(hqy), quad_bcast<2>(hqy), quad_bcast<3>(hqy)};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float pe = __builtin_amdgcn_exp2f(BIAS ? fmaf(bq[qb][e], LOG2E, c[e] - m4[e]) : c[e] - m4[e]) * i4[e];
+                    float mk = 1.0f;                        // dropout factor of (query qrow + 4 l4 + e, key)
+                    if (dthr) mk = attn_keep_field(xq[e], yq[e], key & 3, dthr) ? p.drop_keep : 0.f;
+                    pB[4 * qb + e] = (bf16)(pe * mk);       // dV takes the masked probabilities
+                    dsB[4 * qb + e] = (bf16)(pe * (mk * dp[e] - d4[e]));
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int db = 0; db < 4; ++db) {
+                const bf16x8 qf = apb_tr8(img0, qt * 32, db, l15, l4), df = apb_tr8(img1, qt * 32, db, l15, l4);
+                dv[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df, pB, dv[db], 0, 0, 0);
+                dk[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, dsB, dk[db], 0, 0, 0);
+            }
+        }
+        if (key < L) {
+            // the key's dk | dv row: a prefix key's in the prefix gradient rows [N*P][2H], an own key's in dq | dk | dv [N*S][3H]
+            bf16* ob = key < P ? reinterpret_cast<bf16*>(p.dkvh) + ((int64_t)n * P + key) * 2 * H
+                               : reinterpret_cast<bf16*>(p.dqkv) + ((int64_t)n * S + (key - P)) * 3 * H + H;
+            ob += a * 64 + 4 * l4_;
+            const float kscale = hm * (1.0f / LOG2E);
+#pragma unroll
+            for (int db = 0; db < 4; ++db) {
+                const f32x4 ok = dk[db], ov = dv[db];
+                *reinterpret_cast<bf16x4*>(ob + db * 16) = bf16x4{(bf16)(ok[0] * kscale), (bf16)(ok[1] * kscale), (bf16)(ok[2] * kscale), (bf16)(ok[3] * kscale)};
+                *reinterpret_cast<bf16x4*>(ob + H + db * 16) = bf16x4{(bf16)(ov[0] * hm), (bf16)(ov[1] * hm), (bf16)(ov[2] * hm), (bf16)(ov[3] * hm)};
+            }
+        }
+    }
+}
+
+// ---- exact fp32 (VALU): one block (4 waves) per (n, head), L <= 256; attn_bias_bwd_f32_kernel made rectangular ---------------------
+// Pass A (K, V of the L keys in LDS; one query per wave-iteration, S of them): p_ij, dp_ij, delta_i, ds_ij (-> d_bias row i), dQ_i;
+// (max, 1 / sum, delta) of every query row stay in LDS.  Pass B (Q, dO of the S queries in LDS; one key per wave-iteration, L of
+// them): p and ds rebuilt from them, dV_j and dK_j to the prefix or the own rows.
+template <typename TD>
+__global__ __launch_bounds__(256) void attn_prefix_bwd_f32_kernel(AttnPrefixBwdArgs p) {
+    extern __shared__ float sm[];
+    const int S = p.S, P = p.P, L = p.S + p.P, H = p.H;
+    float* sA = sm;                          // pass A: K [L][65]   | pass B: Q  [S][65]
+    float* sB = sA + (size_t)L * 65;         // pass A: V [L][65]   | pass B: dO [S][65]
+    float* sMx = sB + (size_t)L * 65;        // row max, 1 / row sum, delta  [3][S]
+    float* sInv = sMx + S;
+    float* sDl = sInv + S;
+    float* sW = sDl + S;                     // per wave: 64 + 64 + L + L floats
+    const int n = blockIdx.x / p.A, a = blockIdx.x % p.A;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float* wq = sW + (size_t)wave * (128 + 2 * L);      // query row (A) / key row (B)
+    float* wd = wq + 64;                                 // dO row (A) / value row (B)
+    float* wp = wd + 64;                                 // p_j (B: p_i)
+    float* ws = wp + L;                                  // ds_j (B: ds_i)
+    const float* qkv = reinterpret_cast<const float*>(p.qkv) + (int64_t)n * S * 3 * H + a * 64;
+    const float* kvh = reinterpret_cast<const float*>(p.kvh) + (int64_t)n * P * 2 * H + a * 64;
+    const TD* dctx = reinterpret_cast<const TD*>(p.dctx) + (int64_t)n * S * H + a * 64;
+    float* dqkv = reinterpret_cast<float*>(p.dqkv) + (int64_t)n * S * 3 * H + a * 64;
+    float* dkvh = reinterpret_cast<float*>(p.dkvh) + (int64_t)n * P * 2 * H + a * 64;
+    const float* bias = p.bias ? p.bias + (int64_t)n * p.bias_sn + (int64_t)a * p.bias_sa : nullptr;
+    float* dbias = p.d_bias ? p.d_bias + ((int64_t)n * p.A + a) * S * L : nullptr;
+    auto bias_at = [&](int i, int j) { return bias ? bias[(int64_t)i * p.bias_sq + j] : 0.f; };
+    // key j's k row (its v row H further): prefix rows first, then the own rows
+    auto krow = [&](int j) { return j < P ? kvh + (int64_t)j * 2 * H : qkv + (int64_t)(j - P) * 3 * H + H; };
+    const uint32_t dthr = p.drop_thr16;
+    const float keepv = (p.head_mask ? p.head_mask[(int64_t)n * p.head_mask_sn + a] : 1.0f) * (dthr ? p.drop_keep : 1.0f);
+    auto dmask = [&](int i, int j) {        // hm x keep / (1 - p) of weight (query i, key j)
+        if (!dthr) return keepv;
+        uint32_t hx, hy;
+        attn_drop_words((uint32_t)((n * p.A + a) * 256 + i), j >> 2, p.drop_key, hx, hy);
+        return attn_keep_field(hx, hy, j & 3, dthr) ? keepv : 0.f;
+    };
+    // ---- pass A ------------------------------------------------------------------------------------------
+    for (int idx = tid; idx < L * 64; idx += 256) {
+        const int j = idx >> 6, d = idx & 63;
+        const float* r = krow(j);
+        sA[j * 65 + d] = r[d];
+        sB[j * 65 + d] = r[H + d];
+    }
+    __syncthreads();
+    for (int i = wave; i < S; i += 4) {
+        wq[lane] = qkv[(int64_t)i * 3 * H + lane];
+        wd[lane] = to_f32(dctx[(int64_t)i * H + lane]);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        float sv[4], dp[4], mx = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int j = lane + 64 * c;
+            sv[c] = -INFINITY; dp[c] = 0.f;
+            if (j < L) {
+                float s = 0.f, t = 0.f;
+                for (int d = 0; d < 64; ++d) { s = fmaf(wq[d], sA[j * 65 + d], s); t = fmaf(wd[d], sB[j * 65 + d], t); }
+                s = s / 8.0f + bias_at(i, j);
+                sv[c] = s; dp[c] = t * dmask(i, j);
+                mx = fmaxf(mx, s);
+            }
+        }
+        mx = wave_max(mx);
+        if (mx == -INFINITY) mx = 0.f;      // every key at -inf: the row's probabilities are 0
+        float sum = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) if (lane + 64 * c < L) { sv[c] = expf(sv[c] - mx); sum += sv[c]; }
+        sum = wave_sum(sum);
+        const float inv = sum > 0.f ? 1.0f / sum : 0.f;
+        float dl = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) if (lane + 64 * c < L) { sv[c] *= inv; dl += sv[c] * dp[c]; }
+        dl = wave_sum(dl);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (lane + 64 * c < L) {
+                const float ds = sv[c] * (dp[c] - dl);
+                ws[lane + 64 * c] = ds;
+                if (dbias) dbias[(int64_t)i * L + lane + 64 * c] = ds;
+            }
+        if (lane == 0) { sMx[i] = mx; sInv[i] = inv; sDl[i] = dl; }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        float g = 0.f;
+        for (int j = 0; j < L; ++j) g = fmaf(ws[j], sA[j * 65 + lane], g);
+        dqkv[(int64_t)i * 3 * H + lane] = g / 8.0f;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    }
+    __syncthreads();
+    // ---- pass B ------------------------------------------------------------------------------------------
+    for (int idx = tid; idx < S * 64; idx += 256) {
+        const int i = idx >> 6, d = idx & 63;
+        sA[i * 65 + d] = qkv[(int64_t)i * 3 * H + d];
+        sB[i * 65 + d] = to_f32(dctx[(int64_t)i * H + d]);
+    }
+    __syncthreads();
+    for (int j = wave; j < L; j += 4) {
+        const float* r = krow(j);
+        wq[lane] = r[lane];
+        wd[lane] = r[H + lane];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int i = lane + 64 * c;
+            if (i < S) {
+                float s = 0.f, t = 0.f;
+                for (int d = 0; d < 64; ++d) { s = fmaf(sA[i * 65 + d], wq[d], s); t = fmaf(sB[i * 65 + d], wd[d], t); }
+                s = s / 8.0f + bias_at(i, j);
+                const float pij = expf(s - sMx[i]) * sInv[i];
+                const float mij = dmask(i, j);
+                wp[i] = pij * mij;
+                ws[i] = pij * (t * mij - sDl[i]);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        float gv = 0.f, gk = 0.f;
+        for (int i = 0; i < S; ++i) { gv = fmaf(wp[i], sB[i * 65 + lane], gv); gk = fmaf(ws[i], sA[i * 65 + lane], gk); }
+        float* o = j < P ? dkvh + (int64_t)j * 2 * H : dqkv + (int64_t)(j - P) * 3 * H + H;
+        o[lane] = gk / 8.0f;
+        o[H + lane] = gv;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    }
+}
+
+template <typename K>
+int apb_configure(K kernel, int bytes, bool& configured) {
+    if (configured) return MODCR_OK;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+        modcr_set_error("attn_prefix_bwd: cannot reserve %d bytes of LDS: %s", bytes, hipGetErrorString(e));
+        return MODCR_ERR_LAUNCH;
+    }
+    configured = true;
+    return MODCR_OK;
+}
+
+template <bool BIAS, bool DBIAS>
+int launch_mfma(const AttnPrefixBwdArgs& b, hipStream_t st) {
+    static bool configured_dev[MODCR_MAX_DEV] = {};
+    const int rc = apb_configure(&attn_prefix_bwd_mfma_kernel<BIAS, DBIAS>, APB::SMEM, configured_dev[modcr_device_index()]);
+    if (rc != MODCR_OK) return rc;
+    hipLaunchKernelGGL((attn_prefix_bwd_mfma_kernel<BIAS, DBIAS>), dim3(b.N * b.A), dim3(APB::NT), APB::SMEM, st, b);
+    return modcr_check_launch("attn_prefix_bwd_mfma");
+}
+
+template <typename TD>
+int launch_f32(const AttnPrefixBwdArgs& b, hipStream_t st) {
+    static bool configured_dev[MODCR_MAX_DEV] = {};
+    const int rc = apb_configure(&attn_prefix_bwd_f32_kernel<TD>, 160 * 1024, configured_dev[modcr_device_index()]);
+    if (rc != MODCR_OK) return rc;
+    const size_t S = (size_t)b.S, L = (size_t)b.S + (size_t)b.P;
+    const size_t smem = (2 * L * 65 + 3 * S + 4 * (128 + 2 * L)) * sizeof(float);         // < 146 KB at L = 256 (S < L)
+    hipLaunchKernelGGL(attn_prefix_bwd_f32_kernel<TD>, dim3(b.N * b.A), dim3(256), smem, st, b);
+    return modcr_check_launch("attn_prefix_bwd_f32");
+}
+
+}  // namespace
+
+int modcr_launch_attn_prefix_bwd(const AttnPrefixBwdArgs& b, int core, int32_t dtype, hipStream_t stream) {
+    MODCR_REQUIRE(b.qkv && b.kvh && b.dctx && b.dqkv && b.dkvh && (b.bias || b.head_mask) && (b.bias || !b.d_bias), "attn_prefix_bwd: null pointer");
+    MODCR_REQUIRE(b.N > 0 && b.A > 0 && b.H == b.A * 64 && b.S > 0 && b.P > 0 && b.S + b.P <= (core == 1 ? APB::LP : 256),
+                  "attn_prefix_bwd: unsupported call (S=%d P=%d)", b.S, b.P);
+    if (core == 1) {
+        MODCR_REQUIRE(dtype == MODCR_BF16 && modcr_aligned16(b.qkv) && modcr_aligned16(b.kvh) && modcr_aligned16(b.dctx) && modcr_aligned16(b.dqkv) &&
+                          modcr_aligned16(b.dkvh),
+                      "attn_prefix_bwd: the MFMA core takes 16-byte aligned bf16 rows");
+        if (!b.bias) return launch_mfma<false, false>(b, stream);
+        return b.d_bias ? launch_mfma<true, true>(b, stream) : launch_mfma<true, false>(b, stream);
+    }
+    return dtype == MODCR_BF16 ? launch_f32<bf16>(b, stream) : launch_f32<float>(b, stream);
+}

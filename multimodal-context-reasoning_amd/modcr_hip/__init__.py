@@ -100,6 +100,10 @@ SIGNATURES = {
     "modcr_qkv_attn_bias_bwd_route": (_i32, [_i32, _i32, _i32, _i32, _i32]),
     "modcr_qkv_attn_bias_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
                                        _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
+    "modcr_qkv_attn_prefix_bwd_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_prefix_bwd_route": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_prefix_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
+                                         _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
     "modcr_linear_residual_ln_bwd_workspace": (_i64, [_i32, _i32, _i32]),
     "modcr_linear_residual_ln_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
                                             _vp, _i64, _i32, _vp]),
@@ -1005,15 +1009,28 @@ def adamw_step(p, g, m, v, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay,
 
 def qkv_attn_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, mask_bits=None, chunk_id=None, num_heads=None,
                  accumulate=False, attn_dropout=None, d_align=None, align_t=0, dx_residual=None, ctx=None, lse=None, dump=None,
-                 side_post_dropout=False, attn_bias=None, head_mask=None, d_bias=None):
-    """Backward of qkv_attn (no prefix rows): returns dx [N,S,H] in x's dtype; dwqkv [3H,H] / dbqkv [3H] fp32 are
+                 side_post_dropout=False, attn_bias=None, head_mask=None, d_bias=None, hist=None):
+    """Backward of qkv_attn: returns dx [N,S,H] in x's dtype; dwqkv [3H,H] / dbqkv [3H] fp32 are
     written (or added into when accumulate).  attn_dropout = the (p, seed, offset) the forward ran with; d_align [N,T,R] =
     gradient of the align map the forward accumulated (align_t = T); dx_residual (fp32, x's shape) is added to dx in the
     epilogue of its GEMM.  ctx + lse: the forward's context rows and the row statistics qkv_attn(lse=) wrote -- the attention
     core then runs as the five-product kernel (csrc/attn_bwd.hip) instead of recomputing the statistics.
     attn_bias / head_mask: the operands of a forward that ran qkv_attn(attn_bias=, head_mask=) (modcr_qkv_attn_bias_bwd, S <= 256);
     d_bias: a contiguous fp32 [N, A, S, S] tensor that receives the gradient of the DENSE bias (sum_to_size it to the bias's own
-    shape).  They replace key_mask / mask_bits and do not combine with ctx / lse / dump / d_align."""
+    shape).  They replace key_mask / mask_bits and do not combine with ctx / lse / dump / d_align.
+    hist [N,P,H]: the prefix rows of a forward that ran qkv_attn(hist=, attn_bias= / head_mask=) (modcr_qkv_attn_prefix_bwd,
+    P + S <= 256).  Returns (dx, d_hist [N,P,H] in x's dtype); attn_bias is then [.., L = P + S] and d_bias a contiguous fp32
+    [N, A, S, L].  A binary key_mask [N, L] is folded on the host into a [N,1,1,L] 0 / -10000 bias (this route has no mask-bit
+    variant; use the same fold in the forward).  Not with ctx / lse / dump / d_align / chunk_id / mask_bits."""
+    if hist is not None:
+        if ctx is not None or lse is not None or dump is not None or d_align is not None or chunk_id is not None or mask_bits is not None:
+            raise ValueError("qkv_attn_bwd: hist (prefix rows) does not combine with ctx / lse / dump / d_align / chunk_id / mask_bits")
+        if key_mask is not None:
+            if attn_bias is not None:
+                raise ValueError("qkv_attn_bwd: attn_bias replaces key_mask")
+            attn_bias = fold_key_mask(key_mask)
+        return _qkv_attn_prefix_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, num_heads, accumulate,
+                                    attn_dropout, dx_residual)
     if attn_bias is not None or head_mask is not None or d_bias is not None:
         if key_mask is not None or mask_bits is not None:
             raise ValueError("qkv_attn_bwd: attn_bias / head_mask replace key_mask / mask_bits")
@@ -1085,6 +1102,47 @@ def _qkv_attn_bias_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, 
                                          n, s, h, a, float(ap), seed, off, _ptr(ws), need, dt, _stream()),
            "modcr_qkv_attn_bias_bwd")
     return dx
+
+
+def fold_key_mask(key_mask):
+    """binary key mask [N, L] (1 = attend) -> the additive [N,1,1,L] fp32 bias 0 / -10000 of the reference's extended mask"""
+    if key_mask.dim() != 2:
+        raise ValueError("fold_key_mask: key_mask must be [N, L], got %s" % (tuple(key_mask.shape),))
+    return ((1.0 - key_mask.to(torch.float32)) * -10000.0).reshape(key_mask.shape[0], 1, 1, key_mask.shape[1])
+
+
+def qkv_attn_prefix_bwd_route(n, s, p, h, a, dtype=BF16):
+    """The core modcr_qkv_attn_prefix_bwd runs for this shape (nothing is launched): "mfma", "exact" or "refused"."""
+    return ATTN_BIAS_BWD_CORES[lib().modcr_qkv_attn_prefix_bwd_route(n, s, p, h, a, dtype)]
+
+
+def _qkv_attn_prefix_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, a, accumulate, attn_dropout, dx_residual):
+    """qkv_attn_bwd with hist: modcr_qkv_attn_prefix_bwd"""
+    dt = dt_of(x)
+    n, s, h = x.shape
+    if hist.dim() != 3 or hist.shape[0] != n or hist.shape[2] != h or hist.shape[1] < 1 or hist.dtype != x.dtype:
+        raise ValueError("qkv_attn_bwd: hist must be [N, P >= 1, H] in x's dtype, got %s %s" % (tuple(hist.shape), hist.dtype))
+    p = hist.shape[1]
+    l = p + s
+    if l > ATTN_BWD_MAX_KEYS:
+        raise ValueError("qkv_attn_bwd: P + S = %d keys exceeds the %d-key limit of the attention backward" % (l, ATTN_BWD_MAX_KEYS))
+    if attn_bias is None and head_mask is None:
+        raise ValueError("qkv_attn_bwd: hist needs attn_bias, key_mask or head_mask")
+    bias, (bsn, bsa, bsq) = (None, (0, 0, 0)) if attn_bias is None else _bias_strides(attn_bias, n, a, s, l)
+    hm, hsn = (None, 0) if head_mask is None else _head_mask_2d(head_mask, n, a)
+    if d_bias is not None and (bias is None or d_bias.dtype != torch.float32 or tuple(d_bias.shape) != (n, a, s, l) or not d_bias.is_contiguous()):
+        raise ValueError("qkv_attn_bwd: d_bias must be a contiguous fp32 [N, A, S, P + S] tensor, given together with attn_bias")
+    x, dctx, hist = _contig(x), _contig(dctx), _contig(hist)
+    dx, d_hist = torch.empty_like(x), torch.empty_like(hist)
+    need = lib().modcr_qkv_attn_prefix_bwd_workspace(n, s, p, h, dt)
+    ws = _workspace("attn_bwd", need, x.device)
+    ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
+    _check(lib().modcr_qkv_attn_prefix_bwd(_ptr(dctx), _ptr(x), _ptr(hist), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq,
+                                           _ptr(hm), hsn, _ptr(_contig(dx_residual, torch.float32)) if dx_residual is not None else None,
+                                           _ptr(dx), _ptr(d_hist), _ptr(dwqkv), _ptr(dbqkv), 1 if accumulate else 0, _ptr(d_bias),
+                                           n, s, p, h, a, float(ap), seed, off, _ptr(ws), need, dt, _stream()),
+           "modcr_qkv_attn_prefix_bwd")
+    return dx, d_hist
 
 
 def add(a, b, out_dtype=F32, out=None):

@@ -360,16 +360,17 @@ class BertLayerFn(_NotedFn):
 
 
 def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, params, key_mask=None, mask_bits=None, attn_bias=None,
-                        head_mask=None):
-    """forward of BertLayerFn / BertLayerBiasFn: both take nine arguments before the 16 parameters, so parameter i is input 9 + i"""
+                        head_mask=None, hist=None, first_param=9):
+    """forward of BertLayerFn / BertLayerBiasFn / BertLayerPrefixFn: parameter i is input first_param + i (the first two take nine
+    arguments before the 16 parameters, BertLayerPrefixFn ten)"""
     from . import hip_layers
-    s = x.shape[1]
+    s = x.shape[1] + (0 if hist is None else hist.shape[1])
     wants_grad = _caller_grad_mode()[-1] and (x.requires_grad or any(isinstance(p_, torch.Tensor) and p_.requires_grad for p_ in params) or
-                                              (attn_bias is not None and attn_bias.requires_grad))
+                                              (attn_bias is not None and attn_bias.requires_grad) or (hist is not None and hist.requires_grad))
     if s > mh.ATTN_TILE_KEYS and wants_grad:
         # the attention forward serves up to 512 keys, its backward (modcr_qkv_attn_bwd) 256: refuse before any launch
-        raise NotImplementedError("a trainable layer at S = %d exceeds the %d keys the attention backward takes; run it under "
-                                  "torch.no_grad() (eval) up to %d keys" % (s, mh.ATTN_TILE_KEYS, mh.ATTN_MAX_KEYS))
+        raise NotImplementedError("a trainable layer at %s = %d exceeds the %d keys the attention backward takes; run it under "
+                                  "torch.no_grad() (eval) up to %d keys" % ("S" if hist is None else "S + P", s, mh.ATTN_TILE_KEYS, mh.ATTN_MAX_KEYS))
     if head_mask is not None and head_mask.requires_grad and _caller_grad_mode()[-1]:
         raise NotImplementedError("head_mask is a constant of the trainable layer (head pruning): no gradient is formed for it; detach() it")
     align = packed.get("_align") if isinstance(packed, dict) else None       # (map buffer, T, gradient holder) of AlignMapFn
@@ -379,7 +380,8 @@ def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, par
                                               align_map=amap, align_t=at,
                                               side_post_dropout=bool(packed.get("_side_post", True)) if isinstance(packed, dict) else True,
                                               attn_bias=None if attn_bias is None else attn_bias.detach(),
-                                              head_mask=None if head_mask is None else head_mask.detach())
+                                              head_mask=None if head_mask is None else head_mask.detach(),
+                                              hist=None if hist is None else hist.detach())
     ctx.saved, ctx.packed = saved, packed
     ctx.holder = align[2] if align is not None else None
     ctx.params = params                  # (the Parameter objects: the gradient sink writes into their .grad views)
@@ -391,13 +393,13 @@ def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, par
     # sink counts the bucket down only when the LAST use has reported (FlatGrads.done) -- or autograd's hook does, which fires
     # after every node of the parameter has run.  Counting down on the first report would let the bucket's all-reduce start,
     # at N > 1, before the second contribution has been added.
-    _note_uses(ctx, [(9 + i, p_ if isinstance(p_, torch.nn.Parameter) else None) for i, p_ in enumerate(params)])
+    _note_uses(ctx, [(first_param + i, p_ if isinstance(p_, torch.nn.Parameter) else None) for i, p_ in enumerate(params)])
     return y
 
 
 def _bert_layer_backward(ctx, dy):
-    """backward of BertLayerFn / BertLayerBiasFn: (dx or None, the 16 parameter gradients -- None where the sink took them --,
-    the dense [N, A, S, S] bias gradient or None)"""
+    """backward of BertLayerFn / BertLayerBiasFn / BertLayerPrefixFn: (dx or None, the 16 parameter gradients -- None where the sink
+    took them --, the dense [N, A, S, L] bias gradient or None); a layer with a history state leaves its gradient in ctx.d_hist"""
     from . import hip_layers
     d_align = ctx.holder.get("d_align") if ctx.holder is not None else None
     sink, outs, sunk = grad_sink(), {}, {}
@@ -431,6 +433,7 @@ def _bert_layer_backward(ctx, dy):
     dx, g = hip_layers.layer_backward(ctx.packed, ctx.saved, dy.contiguous(), mfma=not EXACT, d_align=d_align, outs=outs,
                                       want_d_bias=ctx.need_bias)
     ctx.saved = None
+    ctx.d_hist = g.get("history_state")
     grads = [None if (n in sunk or not need) else g[n] for n, need in zip(BertLayerFn.NAMES, ctx.need)]
     for prm in sunk.values():
         sink.done(prm)
@@ -457,6 +460,35 @@ class BertLayerBiasFn(_NotedFn):
             shape, dtype = ctx.bias_shape
             d_bias = d_bias.sum_to_size(shape).to(dtype)
         return (dx, d_bias) + (None,) * 7 + grads
+
+
+class BertLayerPrefixFn(_NotedFn):
+    """BertLayerBiasFn with a history state (the reference's encoder_history_states[i], modeling_bert.py:36-44): hist [N,P,H] in the
+    storage dtype is prepended for K and V only and is a DIFFERENTIABLE input (prefix tuning), as are x, attn_bias (any float tensor
+    broadcastable to [N, A, S, P + S]) and the 16 parameters; head_mask is a constant.  attn_bias or head_mask may be None, not both.
+    S + P <= 256 under grad mode (modcr_qkv_attn_prefix_bwd).  Ten arguments before the parameters; same gradient-sink protocol."""
+
+    @staticmethod
+    def forward(ctx, x, hist, attn_bias, head_mask, chunk_id, num_heads, eps, p, attn_p, packed, *params):
+        if hist is None:
+            raise ValueError("BertLayerPrefixFn: no history state (that layer is BertLayerBiasFn / BertLayerFn)")
+        if attn_bias is None and head_mask is None:
+            raise ValueError("BertLayerPrefixFn: neither attn_bias nor head_mask")
+        if chunk_id is not None:
+            raise ValueError("BertLayerPrefixFn: no chunk-mean queries with a history state")
+        ctx.bias_shape = None if attn_bias is None else (tuple(attn_bias.shape), attn_bias.dtype)
+        ctx.need_hist = hist.requires_grad
+        return _bert_layer_forward(ctx, x, None, num_heads, eps, p, attn_p, packed, params, attn_bias=attn_bias, head_mask=head_mask,
+                                   hist=hist, first_param=10)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx, grads, d_bias = _bert_layer_backward(ctx, dy)
+        if d_bias is not None:
+            shape, dtype = ctx.bias_shape
+            d_bias = d_bias.sum_to_size(shape).to(dtype)
+        d_hist, ctx.d_hist = (ctx.d_hist if ctx.need_hist else None), None
+        return (dx, d_hist, d_bias) + (None,) * 7 + grads
 
 
 class ResidualAddFn(torch.autograd.Function):

@@ -183,7 +183,7 @@ def attn_dropout_supported(x, num_heads):
 
 
 def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None, chunk_id=None, p=0.0, attn_p=0.0,
-                        align_map=None, align_t=0, side_post_dropout=True, attn_bias=None, head_mask=None):
+                        align_map=None, align_t=0, side_post_dropout=True, attn_bias=None, head_mask=None, hist=None):
     """p: hidden_dropout_prob of BertSelfOutput / BertOutput in training mode (a_bert:369-373, :446-451);
     attn_p: attention_probs_dropout_prob (modeling_bert.py:69), applied inside the attention kernels;
     align_map [N,T,R] fp32 (+= head-summed text->region probabilities of this layer, v10:982), align_t = T;
@@ -191,8 +191,21 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
     re-enters under the same mask; False = the un-dropped probabilities;
     attn_bias / head_mask: the additive float mask and the head multiplier of mh.qkv_attn(attn_bias=, head_mask=), instead of
     key_mask / mask_bits.  Both are kept for the backward (modcr_qkv_attn_bias_bwd, S <= 256: it recomputes the row statistics, so
-    no lse / dump is written); no align map on this route."""
+    no lse / dump is written); no align map on this route.
+    hist [N,P,H] (storage dtype): the layer's history state, prepended for K and V only (modeling_bert.py:36-44), P + S <= 256 for
+    the backward (modcr_qkv_attn_prefix_bwd).  attn_bias is then [.., P + S]; a binary key_mask [N, P + S] is folded into a
+    0 / -10000 bias, so that forward and backward run one arithmetic.  No mask bits, chunk-mean queries or align map with it."""
     n, s, h = x.shape
+    pl = 0 if hist is None else hist.shape[1]
+    if hist is not None:
+        if mask_bits is not None or chunk_id is not None or align_map is not None:
+            raise ValueError("layer_forward_train: hist (history state) takes no mask_bits, chunk_id or align map")
+        if key_mask is not None:
+            if attn_bias is not None:
+                raise ValueError("layer_forward_train: attn_bias replaces key_mask")
+            attn_bias, key_mask = mh.fold_key_mask(key_mask), None
+        if attn_bias is None and head_mask is None:
+            raise ValueError("layer_forward_train: hist needs key_mask, attn_bias or head_mask")
     biased = attn_bias is not None or head_mask is not None
     if biased and (key_mask is not None or mask_bits is not None):
         raise ValueError("layer_forward_train: attn_bias / head_mask replace key_mask / mask_bits")
@@ -200,9 +213,9 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
         raise ValueError("layer_forward_train: no align map (and no align-map gradient) on the attn_bias / head_mask route")
     adrop = None
     if attn_p > 0.0:
-        if not attn_dropout_supported(x, num_heads):
-            raise NotImplementedError("attention-probability dropout in a trainable layer needs S <= 256 (S=%d, dtype=%s)" % (s, x.dtype))
-        seed, off = mh.DROPOUT.take(n * num_heads * s * s)
+        if not attn_dropout_supported(x, num_heads) or pl + s > 256:
+            raise NotImplementedError("attention-probability dropout in a trainable layer needs P + S <= 256 (S=%d, P=%d, dtype=%s)" % (s, pl, x.dtype))
+        seed, off = mh.DROPOUT.take(n * num_heads * s * (pl + s))
         adrop = (float(attn_p), seed, off)
     # row statistics of the softmax for the five-product attention backward (csrc/attn_bwd.hip), where the forward runs a tile kernel
     lse = torch.empty((n, num_heads, s), dtype=torch.float32, device=x.device) if not biased and mh.lse_supported(x, num_heads) else None
@@ -214,7 +227,7 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
     post = bool(side_post_dropout and adrop is not None and align_map is not None)
     if biased:
         ctx, _ = mh.qkv_attn(x, layer["wqkv"], layer["bqkv"], chunk_id=chunk_id, num_heads=num_heads, attn_dropout=adrop,
-                             attn_bias=attn_bias, head_mask=head_mask)
+                             attn_bias=attn_bias, head_mask=head_mask, hist=hist)
     else:
         ctx, _ = mh.qkv_attn(x, layer["wqkv"], layer["bqkv"], key_mask=key_mask, mask_bits=mask_bits, chunk_id=chunk_id,
                              num_heads=num_heads, attn_dropout=adrop, align_map=align_map, align_t=align_t, lse=lse, dump=dump,
@@ -233,7 +246,7 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
     saved = dict(x=x, ctx=ctx, pre1=pre1, a=a, inter=inter, u=u, pre2=pre2, num_heads=num_heads, eps=eps,
                  key_mask=key_mask, mask_bits=mask_bits, chunk_id=chunk_id, drop1=drop1, drop2=drop2, adrop=adrop,
                  align_t=align_t if align_map is not None else 0, lse=lse, dump=dump, side_post=post,
-                 attn_bias=attn_bias, head_mask=head_mask)
+                 attn_bias=attn_bias, head_mask=head_mask, hist=hist)
     return y.view(n, s, h), saved
 
 
@@ -259,7 +272,9 @@ def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None, want_d_
     the flat gradient buffer on its first use in an accumulation window) or ACCUMULATED into it (the four LayerNorm parameters: the
     kernels add) instead of into a fresh tensor; the returned dict holds the same tensor objects.
     want_d_bias (a layer that ran with attn_bias): the dict also holds "attn_bias", the fp32 [N, A, S, S] gradient of the DENSE bias
-    (dS of every sequence and head; the caller reduces it to the bias's own shape)."""
+    (dS of every sequence and head; the caller reduces it to the bias's own shape).
+    A layer that ran with hist: the dict also holds "history_state", the [N,P,H] gradient of the history state in the storage dtype,
+    and "attn_bias" is [N, A, S, P + S]."""
     outs = outs or {}
     x, ctx, a, inter = saved["x"], saved["ctx"], saved["a"], saved["inter"]
     n, s, h = x.shape
@@ -314,10 +329,14 @@ def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None, want_d_
     if saved.get("attn_bias") is not None or saved.get("head_mask") is not None:
         if want_d_bias and saved.get("attn_bias") is None:
             raise ValueError("layer_backward: want_d_bias for a layer that ran without attn_bias")
-        d_bias = torch.empty((n, saved["num_heads"], s, s), dtype=f32, device=dev) if want_d_bias else None
+        hist = saved.get("hist")
+        keys = s if hist is None else hist.shape[1] + s
+        d_bias = torch.empty((n, saved["num_heads"], s, keys), dtype=f32, device=dev) if want_d_bias else None
         dx = mh.qkv_attn_bwd(d_ctx.view(n, s, h), x, layer["wqkv"], layer["bqkv"], dwqkv, dbqkv, chunk_id=saved["chunk_id"],
                              num_heads=saved["num_heads"], attn_dropout=saved.get("adrop"), dx_residual=d_pre1.view(n, s, h),
-                             attn_bias=saved.get("attn_bias"), head_mask=saved.get("head_mask"), d_bias=d_bias)
+                             attn_bias=saved.get("attn_bias"), head_mask=saved.get("head_mask"), d_bias=d_bias, hist=hist)
+        if hist is not None:
+            dx, g["history_state"] = dx
         if want_d_bias:
             g["attn_bias"] = d_bias
     else:

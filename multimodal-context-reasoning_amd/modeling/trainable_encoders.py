@@ -103,17 +103,36 @@ def _run_layer_bias(model, i, layer, hidden, attn_bias, head_mask):
                                     packed, *params)
 
 
-def encoder_layers(model, hidden, attention_mask, head_mask=None):
-    """CaptionBertEncoder.forward(hidden_states, attention_mask, head_mask) with gradients: the layers of model.encoder over
-    hidden [N,S,H] (storage dtype) under the reference's 4-D ADDITIVE attention_mask (broadcastable to [N,A,S,S]) and
-    head_mask[i] per layer (None, or a sequence / tensor indexed by layer; an entry may be None).  A 0 / -10000 mask on a layer
-    without head mask runs _run_layer with the binary mask, as global_encoder does; anything else -- a soft bias, -5000, -inf, a
-    per-head mask, a head mask -- runs the bias form, and attention_mask is then a differentiable input."""
+def _run_layer_prefix(model, i, layer, hidden, hist, attn_bias, head_mask):
+    """_run_layer_bias with the layer's history state (hip_autograd.BertLayerPrefixFn)"""
+    cfg = model.config
+    params = _layer_params(layer)
+    p = cfg.hidden_dropout_prob if model.training else 0.0
+    ap = getattr(cfg, "attention_probs_dropout_prob", 0.0) if model.training else 0.0
+    packed = _packed(model, i, layer, params, hidden.device, hidden.dtype)
+    return ag.BertLayerPrefixFn.apply(hidden, hist, attn_bias, head_mask, None, cfg.num_attention_heads, cfg.layer_norm_eps, float(p),
+                                      float(ap), packed, *params)
+
+
+def encoder_layers(model, hidden, attention_mask, head_mask=None, encoder_history_states=None):
+    """CaptionBertEncoder.forward(hidden_states, attention_mask, head_mask, encoder_history_states) with gradients: the layers of
+    model.encoder over hidden [N,S,H] (storage dtype) under the reference's 4-D ADDITIVE attention_mask (broadcastable to
+    [N,A,S,S]) and head_mask[i] per layer (None, or a sequence / tensor indexed by layer; an entry may be None).  A 0 / -10000 mask
+    on a layer without head mask runs _run_layer with the binary mask, as global_encoder does; anything else -- a soft bias, -5000,
+    -inf, a per-head mask, a head mask -- runs the bias form, and attention_mask is then a differentiable input.
+    encoder_history_states: None, or one entry per layer, each None or a [N,P,H] tensor in the storage dtype that is prepended for
+    that layer's K and V (modeling_bert.py:36-44) and may require grad (prefix tuning); attention_mask is then broadcastable to
+    [N,A,S,P+S] and P + S <= 256 under grad mode.  Such a layer runs the prefix form (BertLayerPrefixFn) with the mask as it is;
+    layers without a history state keep their route."""
     from .modeling_bert import split_additive_mask
     n, s, _ = hidden.shape
     plain = None                                            # the split of the mask alone (one reduction and one host read)
     for i, layer in enumerate(model.encoder.layer):
         hm = None if head_mask is None else head_mask[i]
+        hist = None if encoder_history_states is None else encoder_history_states[i]
+        if hist is not None:
+            hidden = _run_layer_prefix(model, i, layer, hidden, hist, attention_mask, hm)
+            continue
         if hm is None:
             if plain is None:
                 plain = split_additive_mask(attention_mask, n, s, s)
