@@ -484,8 +484,9 @@ int modcr_qkv_attn_bias_bwd(const void* dctx, const void* x, const void* wqkv, c
  *   attn_bias / bias_stride_* / head_mask / head_mask_stride_n: as modcr_qkv_attn_bias_bwd, the key dimension being L.
  *   d_bias    fp32 contiguous [N, A, S, L] or NULL, as modcr_qkv_attn_bias_bwd's (one lane per element, no atomics).
  *   attn_p, seed, offset: the forward's dropout; the mask is that of counter row (n A + a) x 256 + query, key index over [hist ; x].
- * No chunk mean and no align-map gradient.  Cores (csrc/attn_prefix_bwd.hip): attn_prefix_bwd_mfma_kernel (bf16, L <= 192) or the
- * exact attn_prefix_bwd_f32_kernel (fp32; bf16 with 192 < L <= 256); modcr_qkv_attn_prefix_bwd_route says which without launching:
+ * No chunk mean and no align-map gradient.  Cores (csrc/attn_bias_bwd.hip, the PREFIX instantiations of modcr_qkv_attn_bias_bwd's):
+ * attn_bias_bwd_mfma_kernel (bf16, L <= 192) or the exact attn_bias_bwd_f32_kernel (fp32; bf16 with 192 < L <= 256);
+ * modcr_qkv_attn_prefix_bwd_route says which without launching:
  * 0 = refused, 1 = MFMA core, 2 = exact core.  Every argument is validated before the first launch: P = 0 or hist == NULL returns
  * MODCR_ERR_INVALID (that call belongs to modcr_qkv_attn_bias_bwd), P + S > 256 returns MODCR_ERR_UNSUPPORTED. */
 int64_t modcr_qkv_attn_prefix_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype);

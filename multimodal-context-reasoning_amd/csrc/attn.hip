@@ -2741,34 +2741,53 @@ extern "C" int modcr_qkv_attn_opt_bwd(const void* dctx, const void* x, const voi
                     N, S, H, A, attn_p, seed, offset, d_align, align_t, ctx, lse, qkv_dump, flags, workspace, workspace_bytes, dtype, stream);
 }
 
-// ---- backward of modcr_qkv_attn_bias_fwd (no prefix rows, no align-map gradient) --------------------------------------------------
-// The body is attn_bwd()'s, step for step, with the cores of attn_bias_bwd.hip in step 2.
-extern "C" int64_t modcr_qkv_attn_bias_bwd_workspace(int32_t N, int32_t S, int32_t H, int32_t dtype) {
-    return modcr_qkv_attn_bwd_workspace(N, S, H, dtype);
+// ---- backward of modcr_qkv_attn_bias_fwd: modcr_qkv_attn_bias_bwd (no prefix rows) and modcr_qkv_attn_prefix_bwd (hist [N, P, H], P >= 1) ----
+// One body, attn_bwd()'s step for step with the cores of attn_bias_bwd.hip in step 2: S queries against P + S <= 256 keys, no
+// align-map gradient.  With prefix rows (no chunk mean then) a second, K | V only set of GEMMs serves them: rows H..3H of wqkv / bqkv
+// are a contiguous [2H, H] sub-block (ldw = H).
+namespace {
+
+// The workspace: q | k | v and dq | dk | dv rows of the own rows (rows_x each), k | v and dk | dv rows of the prefix rows (rows_h
+// each; 0 without), then the GEMMs' sub-workspace (the larger of the two sets' needs)
+struct AttnBiasBwdWs {
+    int64_t rows_x, rows_h, sub;
+    int64_t bytes() const { return 2 * rows_x + 2 * rows_h + sub; }
+};
+AttnBiasBwdWs attn_bias_bwd_ws(int32_t N, int32_t S, int32_t P, int32_t H) {
+    AttnBiasBwdWs w;
+    w.rows_x = (((int64_t)N * S * 3 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
+    w.rows_h = (((int64_t)N * P * 2 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
+    w.sub = attn_bwd_sub_ws(N * S, H);
+    if (P > 0) {
+        const int64_t a = modcr_linear_bwd_input_workspace(N * P, 2 * H, H), b = modcr_linear_bwd_weight_workspace(N * P, 2 * H, H);
+        const int64_t h = ((a > b ? a : b) + 255) & ~(int64_t)255;
+        if (h > w.sub) w.sub = h;
+    }
+    return w;
 }
 
 // 0 = refused, 1 = attn_bias_bwd_mfma_kernel, 2 = attn_bias_bwd_f32_kernel
-extern "C" int modcr_qkv_attn_bias_bwd_route(int32_t N, int32_t S, int32_t H, int32_t A, int32_t dtype) {
-    if (N <= 0 || S <= 0 || S > 256 || A <= 0 || H != A * 64 || (dtype != MODCR_BF16 && dtype != MODCR_F32)) return 0;
-    return dtype == MODCR_BF16 && S <= AB::LP ? 1 : 2;
+int attn_bias_bwd_core(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype) {
+    if (N <= 0 || S <= 0 || P < 0 || (int64_t)P + S > 256 || A <= 0 || H != A * 64 || (dtype != MODCR_BF16 && dtype != MODCR_F32)) return 0;
+    return dtype == MODCR_BF16 && P + S <= AB::LP ? 1 : 2;
 }
 
-extern "C" int modcr_qkv_attn_bias_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* attn_bias,
-                                       int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q, const float* head_mask,
-                                       int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx,
-                                       float* dwqkv, float* dbqkv, int32_t accumulate, float* d_bias, int32_t N, int32_t S, int32_t H, int32_t A,
-                                       float attn_p, uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
-                                       modcr_stream_t stream) {
-    const char* who = "qkv_attn_bias_bwd";
-    MODCR_REQUIRE(dctx && x && wqkv && bqkv && dx && dwqkv && dbqkv, "%s: null pointer", who);
+// hist / d_hist / P: the prefix rows and their gradient (null, null, 0 from modcr_qkv_attn_bias_bwd); chunk_id / chunk_t: the chunk
+// mean of the queries (null, 0 from modcr_qkv_attn_prefix_bwd)
+int attn_bias_bwd(const char* who, const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* attn_bias,
+                  int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q, const float* head_mask, int64_t head_mask_stride_n,
+                  const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv,
+                  int32_t accumulate, float* d_bias, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p, uint64_t seed,
+                  uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
+    MODCR_REQUIRE(dctx && x && wqkv && bqkv && dx && (d_hist || !P) && dwqkv && dbqkv, "%s: null pointer", who);
     MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "%s: unknown dtype %d", who, dtype);
-    MODCR_REQUIRE(N > 0 && S > 0 && A > 0, "%s: bad shape (N=%d S=%d H=%d A=%d)", who, N, S, H, A);
+    MODCR_REQUIRE(N > 0 && S > 0 && A > 0, "%s: bad shape (N=%d S=%d P=%d H=%d A=%d)", who, N, S, P, H, A);
     MODCR_REQUIRE(H == A * 64, "%s: head size must be 64 (H=%d, A=%d)", who, H, A);
-    if (S > 256) {
-        modcr_set_error("%s: S=%d exceeds the 256-key limit of the attention backward", who, S);
+    if ((int64_t)P + S > 256) {
+        modcr_set_error("%s: P + S = %lld keys (P=%d) exceeds the 256-key limit of the attention backward", who, (long long)P + S, P);
         return MODCR_ERR_UNSUPPORTED;
     }
-    MODCR_REQUIRE(attn_bias || head_mask, "%s: neither bias nor head_mask (that call belongs to modcr_qkv_attn_opt_bwd)", who);
+    MODCR_REQUIRE(attn_bias || head_mask, "%s: neither bias nor head_mask%s", who, P ? "" : " (that call belongs to modcr_qkv_attn_opt_bwd)");
     MODCR_REQUIRE(attn_bias || !d_bias, "%s: d_bias without a bias", who);
     MODCR_REQUIRE(attn_p >= 0.f && attn_p < 1.f, "%s: attention dropout p=%g out of [0, 1)", who, attn_p);
     MODCR_REQUIRE(bias_stride_n >= 0 && bias_stride_a >= 0 && bias_stride_q >= 0 && head_mask_stride_n >= 0, "%s: negative stride", who);
@@ -2777,19 +2796,26 @@ extern "C" int modcr_qkv_attn_bias_bwd(const void* dctx, const void* x, const vo
     MODCR_REQUIRE(((uintptr_t)attn_bias & 3) == 0 && ((uintptr_t)head_mask & 3) == 0 && ((uintptr_t)d_bias & 3) == 0,
                   "%s: bias / head_mask / d_bias not 4-byte aligned", who);
     MODCR_REQUIRE(!chunk_id || (chunk_t > 0 && chunk_t <= S), "%s: chunk_t=%d out of range", who, chunk_t);
-    MODCR_REQUIRE(dtype != MODCR_BF16 || (modcr_aligned16(dctx) && modcr_aligned16(x) && modcr_aligned16(wqkv) && modcr_aligned16(dx)),
+    MODCR_REQUIRE(dtype != MODCR_BF16 || (modcr_aligned16(dctx) && modcr_aligned16(x) && modcr_aligned16(hist) && modcr_aligned16(wqkv) &&
+                                          modcr_aligned16(dx) && modcr_aligned16(d_hist)),
                   "%s(bf16): 16-byte alignment", who);
-    const int64_t need = modcr_qkv_attn_bias_bwd_workspace(N, S, H, dtype);
-    MODCR_REQUIRE(workspace && workspace_bytes >= need && modcr_aligned16(workspace), "%s: workspace %lld < %lld bytes (or unaligned)", who,
-                  (long long)workspace_bytes, (long long)need);
-    const int core = modcr_qkv_attn_bias_bwd_route(N, S, H, A, dtype);
-    const int M = N * S;
-    const int64_t rows = (((int64_t)M * 3 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
-    void* qkv = workspace;
-    void* dqkv = (char*)workspace + rows;
-    void* sub = dtype == MODCR_BF16 ? (void*)((char*)workspace + 2 * rows) : nullptr;
-    const int64_t sub_bytes = dtype == MODCR_BF16 ? attn_bwd_sub_ws(M, H) : 0;
-    // 1. recompute q | k | v rows (MFMA core: bf16, exact core: fp32), chunk-mean queries as the forward
+    const AttnBiasBwdWs ws = attn_bias_bwd_ws(N, S, P, H);
+    MODCR_REQUIRE(workspace && workspace_bytes >= ws.bytes() && modcr_aligned16(workspace), "%s: workspace %lld < %lld bytes (or unaligned)", who,
+                  (long long)workspace_bytes, (long long)ws.bytes());
+    const int core = attn_bias_bwd_core(N, S, P, H, A, dtype);
+    const int M = N * S, Mh = N * P;
+    char* w = (char*)workspace;
+    void* qkv = w;
+    void* dqkv = w + ws.rows_x;
+    void* kvh = P ? w + 2 * ws.rows_x : nullptr;
+    void* dkvh = P ? w + 2 * ws.rows_x + ws.rows_h : nullptr;
+    // bf16: the weight / input products run on the MFMA path (workspace); fp32 parity path: exact VALU kernels
+    void* sub = dtype == MODCR_BF16 ? (void*)(w + 2 * ws.rows_x + 2 * ws.rows_h) : nullptr;
+    const int64_t sub_bytes = dtype == MODCR_BF16 ? ws.sub : 0;
+    const size_t esz = dtype == MODCR_BF16 ? 2 : 4;
+    const void* wkv = (const char*)wqkv + (size_t)H * H * esz;                  // rows H..3H of wqkv: the K | V projection [2H, H]
+    // 1. recompute the rows (MFMA core: bf16, exact core: fp32): q | k | v of the own rows, chunk-mean queries as the forward; k | v of
+    //    the prefix rows
     const int32_t qdt = core == 1 ? MODCR_BF16 : MODCR_F32;
     int rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, qkv, 3 * H, M, 3 * H, H, MODCR_ACT_NONE, dtype, qdt, stream);
     if (rc != MODCR_OK) return rc;
@@ -2797,15 +2823,19 @@ extern "C" int modcr_qkv_attn_bias_bwd(const void* dctx, const void* x, const vo
         rc = modcr_chunk_mean_q_fwd(qkv, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, qdt, stream);
         if (rc != MODCR_OK) return rc;
     }
+    if (P) {
+        rc = modcr_linear_fwd(hist, H, wkv, H, bqkv + H, nullptr, 0, 0, kvh, 2 * H, Mh, 2 * H, H, MODCR_ACT_NONE, dtype, qdt, stream);
+        if (rc != MODCR_OK) return rc;
+    }
     // 2. attention core backward
     AttnBiasBwdArgs b;
-    b.qkv = qkv; b.dctx = dctx; b.dqkv = dqkv;
+    b.qkv = qkv; b.kvh = kvh; b.dctx = dctx; b.dqkv = dqkv; b.dkvh = dkvh;
     b.bias = attn_bias; b.bias_sn = bias_stride_n; b.bias_sa = bias_stride_a; b.bias_sq = bias_stride_q;
     b.head_mask = head_mask; b.head_mask_sn = head_mask_stride_n;
     b.d_bias = d_bias;
     const AttnDrop d = attn_drop(attn_p, seed, offset);     // (as the forward)
     b.drop_thr16 = d.thr16; b.drop_key = d.key; b.drop_keep = d.keep;
-    b.N = N; b.S = S; b.H = H; b.A = A;
+    b.N = N; b.S = S; b.P = P; b.H = H; b.A = A;
     rc = modcr_launch_attn_bias_bwd(b, core, dtype, (hipStream_t)stream);
     if (rc != MODCR_OK) return rc;
     // 3. the chunk mean is its own adjoint
@@ -2813,32 +2843,46 @@ extern "C" int modcr_qkv_attn_bias_bwd(const void* dctx, const void* x, const vo
         rc = modcr_chunk_mean_q_fwd(dqkv, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, qdt, stream);
         if (rc != MODCR_OK) return rc;
     }
-    // 4. dX = dqkv . Wqkv (+ dx_residual);  dWqkv (+)= dqkv^T . X;  dbqkv (+)= column sums
+    // 4. own rows: dX = dqkv . Wqkv (+ dx_residual);  dWqkv (+)= dqkv^T . X;  dbqkv (+)= column sums
     rc = modcr_linear_bwd_input_res(dqkv, 3 * H, qdt, wqkv, H, dx_residual, H, dx, H, M, 3 * H, H, dtype, dtype, sub, sub_bytes, stream);
     if (rc != MODCR_OK) return rc;
-    return modcr_linear_bwd_weight(dqkv, 3 * H, qdt, x, H, dwqkv, dbqkv, M, 3 * H, H, accumulate, dtype, sub, sub_bytes, stream);
+    rc = modcr_linear_bwd_weight(dqkv, 3 * H, qdt, x, H, dwqkv, dbqkv, M, 3 * H, H, accumulate, dtype, sub, sub_bytes, stream);
+    if (rc != MODCR_OK || !P) return rc;
+    // 5. prefix rows, K | V only: d_hist = d(k|v) . Wqkv[H:3H];  dWqkv[H:3H] += d(k|v)^T . hist;  dbqkv[H:3H] += column sums
+    rc = modcr_linear_bwd_input_res(dkvh, 2 * H, qdt, wkv, H, nullptr, 0, d_hist, H, Mh, 2 * H, H, dtype, dtype, sub, sub_bytes, stream);
+    if (rc != MODCR_OK) return rc;
+    return modcr_linear_bwd_weight(dkvh, 2 * H, qdt, hist, H, dwqkv + (size_t)H * H, dbqkv + H, Mh, 2 * H, H, 1, dtype, sub, sub_bytes, stream);
 }
 
-// ---- backward of modcr_qkv_attn_bias_fwd WITH prefix rows (hist [N, P, H], P >= 1, P + S <= 256; no chunk mean, no align-map gradient) ----
-// The body is modcr_qkv_attn_bias_bwd's, step for step, with the rectangular cores of attn_prefix_bwd.hip in step 2 and a second,
-// K | V only set of GEMMs for the prefix rows: rows H..3H of wqkv / bqkv are a contiguous [2H, H] sub-block (ldw = H).
-static int64_t attn_prefix_bwd_sub_ws(int32_t N, int32_t S, int32_t P, int32_t H) {
-    const int64_t a = modcr_linear_bwd_input_workspace(N * P, 2 * H, H), b = modcr_linear_bwd_weight_workspace(N * P, 2 * H, H);
-    const int64_t h = ((a > b ? a : b) + 255) & ~(int64_t)255, x = attn_bwd_sub_ws(N * S, H);
-    return h > x ? h : x;
+}  // namespace
+
+extern "C" int64_t modcr_qkv_attn_bias_bwd_workspace(int32_t N, int32_t S, int32_t H, int32_t dtype) {
+    (void)dtype;
+    return attn_bias_bwd_ws(N, S, 0, H).bytes();            // (= modcr_qkv_attn_bwd_workspace)
 }
+
+extern "C" int modcr_qkv_attn_bias_bwd_route(int32_t N, int32_t S, int32_t H, int32_t A, int32_t dtype) {
+    return attn_bias_bwd_core(N, S, 0, H, A, dtype);
+}
+
+extern "C" int modcr_qkv_attn_bias_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* attn_bias,
+                                       int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q, const float* head_mask,
+                                       int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx,
+                                       float* dwqkv, float* dbqkv, int32_t accumulate, float* d_bias, int32_t N, int32_t S, int32_t H, int32_t A,
+                                       float attn_p, uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                                       modcr_stream_t stream) {
+    return attn_bias_bwd("qkv_attn_bias_bwd", dctx, x, nullptr, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask,
+                         head_mask_stride_n, chunk_id, chunk_t, dx_residual, dx, nullptr, dwqkv, dbqkv, accumulate, d_bias, N, S, 0, H, A, attn_p,
+                         seed, offset, workspace, workspace_bytes, dtype, stream);
+}
+
 extern "C" int64_t modcr_qkv_attn_prefix_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
     (void)dtype;
-    if (N <= 0 || S <= 0 || P <= 0 || H <= 0) return 0;
-    const int64_t rows_x = (((int64_t)N * S * 3 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
-    const int64_t rows_h = (((int64_t)N * P * 2 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
-    return 2 * rows_x + 2 * rows_h + attn_prefix_bwd_sub_ws(N, S, P, H);
+    return N <= 0 || S <= 0 || P <= 0 || H <= 0 ? 0 : attn_bias_bwd_ws(N, S, P, H).bytes();
 }
 
-// 0 = refused, 1 = attn_prefix_bwd_mfma_kernel, 2 = attn_prefix_bwd_f32_kernel
 extern "C" int modcr_qkv_attn_prefix_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype) {
-    if (N <= 0 || S <= 0 || P <= 0 || (int64_t)P + S > 256 || A <= 0 || H != A * 64 || (dtype != MODCR_BF16 && dtype != MODCR_F32)) return 0;
-    return dtype == MODCR_BF16 && P + S <= AB::LP ? 1 : 2;
+    return P <= 0 ? 0 : attn_bias_bwd_core(N, S, P, H, A, dtype);
 }
 
 extern "C" int modcr_qkv_attn_prefix_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
@@ -2849,65 +2893,7 @@ extern "C" int modcr_qkv_attn_prefix_bwd(const void* dctx, const void* x, const 
                                          int32_t dtype, modcr_stream_t stream) {
     const char* who = "qkv_attn_prefix_bwd";
     MODCR_REQUIRE(P >= 1 && hist, "%s: no prefix rows (P=%d, hist %s): that call belongs to modcr_qkv_attn_bias_bwd", who, P, hist ? "given" : "null");
-    MODCR_REQUIRE(dctx && x && wqkv && bqkv && dx && d_hist && dwqkv && dbqkv, "%s: null pointer", who);
-    MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "%s: unknown dtype %d", who, dtype);
-    MODCR_REQUIRE(N > 0 && S > 0 && A > 0, "%s: bad shape (N=%d S=%d P=%d H=%d A=%d)", who, N, S, P, H, A);
-    MODCR_REQUIRE(H == A * 64, "%s: head size must be 64 (H=%d, A=%d)", who, H, A);
-    if ((int64_t)P + S > 256) {
-        modcr_set_error("%s: P + S = %lld keys exceeds the 256-key limit of the attention backward", who, (long long)P + S);
-        return MODCR_ERR_UNSUPPORTED;
-    }
-    MODCR_REQUIRE(attn_bias || head_mask, "%s: neither bias nor head_mask", who);
-    MODCR_REQUIRE(attn_bias || !d_bias, "%s: d_bias without a bias", who);
-    MODCR_REQUIRE(attn_p >= 0.f && attn_p < 1.f, "%s: attention dropout p=%g out of [0, 1)", who, attn_p);
-    MODCR_REQUIRE(bias_stride_n >= 0 && bias_stride_a >= 0 && bias_stride_q >= 0 && head_mask_stride_n >= 0, "%s: negative stride", who);
-    // (the cores address a (sequence, head) slice of the bias with 32-bit element offsets)
-    MODCR_REQUIRE(bias_stride_q <= (1 << 20), "%s: bias query stride %lld exceeds 2^20 elements", who, (long long)bias_stride_q);
-    MODCR_REQUIRE(((uintptr_t)attn_bias & 3) == 0 && ((uintptr_t)head_mask & 3) == 0 && ((uintptr_t)d_bias & 3) == 0,
-                  "%s: bias / head_mask / d_bias not 4-byte aligned", who);
-    MODCR_REQUIRE(dtype != MODCR_BF16 || (modcr_aligned16(dctx) && modcr_aligned16(x) && modcr_aligned16(hist) && modcr_aligned16(wqkv) &&
-                                          modcr_aligned16(dx) && modcr_aligned16(d_hist)),
-                  "%s(bf16): 16-byte alignment", who);
-    const int64_t need = modcr_qkv_attn_prefix_bwd_workspace(N, S, P, H, dtype);
-    MODCR_REQUIRE(workspace && workspace_bytes >= need && modcr_aligned16(workspace), "%s: workspace %lld < %lld bytes (or unaligned)", who,
-                  (long long)workspace_bytes, (long long)need);
-    const int core = modcr_qkv_attn_prefix_bwd_route(N, S, P, H, A, dtype);
-    const int M = N * S, Mh = N * P;
-    const int64_t rows_x = (((int64_t)M * 3 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
-    const int64_t rows_h = (((int64_t)Mh * 2 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
-    char* w = (char*)workspace;
-    void* qkv = w;
-    void* dqkv = w + rows_x;
-    void* kvh = w + 2 * rows_x;
-    void* dkvh = w + 2 * rows_x + rows_h;
-    void* sub = dtype == MODCR_BF16 ? (void*)(w + 2 * rows_x + 2 * rows_h) : nullptr;
-    const int64_t sub_bytes = dtype == MODCR_BF16 ? attn_prefix_bwd_sub_ws(N, S, P, H) : 0;
-    const size_t esz = dtype == MODCR_BF16 ? 2 : 4;
-    const void* wkv = (const char*)wqkv + (size_t)H * H * esz;                  // rows H..3H of wqkv: the K | V projection [2H, H]
-    // 1. recompute the rows (MFMA core: bf16, exact core: fp32): q | k | v of the own rows, k | v of the prefix rows
-    const int32_t qdt = core == 1 ? MODCR_BF16 : MODCR_F32;
-    int rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, qkv, 3 * H, M, 3 * H, H, MODCR_ACT_NONE, dtype, qdt, stream);
-    if (rc != MODCR_OK) return rc;
-    rc = modcr_linear_fwd(hist, H, wkv, H, bqkv + H, nullptr, 0, 0, kvh, 2 * H, Mh, 2 * H, H, MODCR_ACT_NONE, dtype, qdt, stream);
-    if (rc != MODCR_OK) return rc;
-    // 2. attention core backward
-    AttnPrefixBwdArgs b;
-    b.qkv = qkv; b.kvh = kvh; b.dctx = dctx; b.dqkv = dqkv; b.dkvh = dkvh;
-    b.bias = attn_bias; b.bias_sn = bias_stride_n; b.bias_sa = bias_stride_a; b.bias_sq = bias_stride_q;
-    b.head_mask = head_mask; b.head_mask_sn = head_mask_stride_n;
-    b.d_bias = d_bias;
-    const AttnDrop d = attn_drop(attn_p, seed, offset);     // (as the forward)
-    b.drop_thr16 = d.thr16; b.drop_key = d.key; b.drop_keep = d.keep;
-    b.N = N; b.S = S; b.P = P; b.H = H; b.A = A;
-    rc = modcr_launch_attn_prefix_bwd(b, core, dtype, (hipStream_t)stream);
-    if (rc != MODCR_OK) return rc;
-    // 3. own rows: dX = dqkv . Wqkv (+ dx_residual);  dWqkv (+)= dqkv^T . X;  dbqkv (+)= column sums
-    rc = modcr_linear_bwd_input_res(dqkv, 3 * H, qdt, wqkv, H, dx_residual, H, dx, H, M, 3 * H, H, dtype, dtype, sub, sub_bytes, stream);
-    if (rc != MODCR_OK) return rc;
-    rc = modcr_linear_bwd_weight(dqkv, 3 * H, qdt, x, H, dwqkv, dbqkv, M, 3 * H, H, accumulate, dtype, sub, sub_bytes, stream);
-    if (rc != MODCR_OK) return rc;
-    // 4. prefix rows, K | V only: d_hist = d(k|v) . Wqkv[H:3H];  dWqkv[H:3H] += d(k|v)^T . hist;  dbqkv[H:3H] += column sums
-    rc = modcr_linear_bwd_input_res(dkvh, 2 * H, qdt, wkv, H, nullptr, 0, d_hist, H, Mh, 2 * H, H, dtype, dtype, sub, sub_bytes, stream);
-    if (rc != MODCR_OK) return rc;
-    return modcr_linear_bwd_weight(dkvh, 2 * H, qdt, hist, H, dwqkv + (size_t)H * H, dbqkv + H, Mh, 2 * H, H, 1, dtype, sub, sub_bytes, stream);
+    return attn_bias_bwd(who, dctx, x, hist, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask, head_mask_stride_n,
+                         nullptr, 0, dx_residual, dx, d_hist, dwqkv, dbqkv, accumulate, d_bias, N, S, P, H, A, attn_p, seed, offset, workspace,
+                         workspace_bytes, dtype, stream);
 }

@@ -125,11 +125,15 @@ struct AttnBwdArgs {
 // attn_bwd.hip: launches attn_bwd5_kernel on `b` (bf16 rows, 0 < S <= 192, lse and ctx given, no align-map gradient)
 __attribute__((visibility("hidden"))) int modcr_launch_attn_bwd5(const AttnBwdArgs& b, hipStream_t stream);
 
-// attn_bias_bwd.hip: the attention core backward under an additive bias and / or a head mask (modcr_qkv_attn_bias_bwd), from the
-// recomputed q | k | v rows [N*S][3H] to the dq | dk | dv rows of the same layout and, when wanted, d_bias = dS [N, A, S, S] fp32.
+// attn_bias_bwd.hip: the attention core backward under an additive bias and / or a head mask, S queries against L = P + S keys
+// (modcr_qkv_attn_bias_bwd: P = 0; modcr_qkv_attn_prefix_bwd: P > 0 prefix keys).  The own rows' q | k | v projection qkv [N*S][3H]
+// and, with P > 0, the prefix rows' k | v projection kvh [N*P][2H] come in; dq | dk | dv of the own rows (dqkv, same layout) and
+// dk | dv of the prefix rows (dkvh, same layout) go out; d_bias = dS [N, A, S, L] fp32 when wanted.
 struct AttnBiasBwdArgs {
-    const void* qkv; const void* dctx; void* dqkv;         // core 1: bf16 rows in and out; core 2: fp32 rows, dctx in the storage dtype
-    // bias[n sn + a sa + q sq + j] fp32 (strides in elements, 0 = broadcast; NULL = no bias), head_mask[n hsn + a] (NULL = 1)
+    const void* qkv; const void* kvh; const void* dctx;    // core 1: bf16 rows in and out; core 2: fp32 rows, dctx in the storage dtype
+    void* dqkv; void* dkvh;                                 // kvh, dkvh: NULL exactly when P == 0
+    // bias[n sn + a sa + q sq + j] fp32, j over the L keys (strides in elements, 0 = broadcast; NULL = no bias), head_mask[n hsn + a]
+    // (NULL = 1)
     const float* bias; int64_t bias_sn, bias_sa, bias_sq;
     const float* head_mask; int64_t head_mask_sn;
     float* d_bias;                                          // or NULL
@@ -137,28 +141,10 @@ struct AttnBiasBwdArgs {
     uint32_t drop_thr16;
     uint64_t drop_key;
     float drop_keep;
-    int N, S, H, A;
-};
-// core: 1 = attn_bias_bwd_mfma_kernel (bf16, S <= 192), 2 = attn_bias_bwd_f32_kernel (S <= 256)
-__attribute__((visibility("hidden"))) int modcr_launch_attn_bias_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype, hipStream_t stream);
-
-// attn_prefix_bwd.hip: the same backward with P > 0 prefix keys (modcr_qkv_attn_prefix_bwd), S queries against L = P + S keys.
-// The own rows' q | k | v projection qkv [N*S][3H] and the prefix rows' k | v projection kvh [N*P][2H] come in, dq | dk | dv of the own
-// rows (dqkv, same layout) and dk | dv of the prefix rows (dkvh, same layout) go out; d_bias = dS [N, A, S, L] fp32 when wanted.
-struct AttnPrefixBwdArgs {
-    const void* qkv; const void* kvh; const void* dctx;    // core 1: bf16 rows in and out; core 2: fp32 rows, dctx in the storage dtype
-    void* dqkv; void* dkvh;
-    // bias[n sn + a sa + q sq + j] fp32, j over the L keys (strides in elements, 0 = broadcast; NULL = no bias), head_mask[n hsn + a]
-    const float* bias; int64_t bias_sn, bias_sa, bias_sq;
-    const float* head_mask; int64_t head_mask_sn;
-    float* d_bias;                                          // or NULL
-    uint32_t drop_thr16;                                    // the forward's attention-probability dropout, as AttnBiasBwdArgs
-    uint64_t drop_key;
-    float drop_keep;
     int N, S, P, H, A;
 };
-// core: 1 = attn_prefix_bwd_mfma_kernel (bf16, P + S <= 192), 2 = attn_prefix_bwd_f32_kernel (P + S <= 256)
-__attribute__((visibility("hidden"))) int modcr_launch_attn_prefix_bwd(const AttnPrefixBwdArgs& b, int core, int32_t dtype, hipStream_t stream);
+// core: 1 = attn_bias_bwd_mfma_kernel (bf16, P + S <= 192), 2 = attn_bias_bwd_f32_kernel (P + S <= 256); prefix rows where b.P > 0
+__attribute__((visibility("hidden"))) int modcr_launch_attn_bias_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype, hipStream_t stream);
 
 // attn_long.hip: the streaming attention core (P + S <= 512) over q | k | v rows the dispatcher projected: qx [N*S][3H] (queries,
 // chunk-mean applied), qh [N*P][3H] (prefix rows) -- bf16 or fp32 as `dtype`.  Binary masks (key_mask / bits: above 256 keys, no

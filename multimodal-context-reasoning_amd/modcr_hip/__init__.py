@@ -1029,8 +1029,8 @@ def qkv_attn_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, mask_bits=Non
             if attn_bias is not None:
                 raise ValueError("qkv_attn_bwd: attn_bias replaces key_mask")
             attn_bias = fold_key_mask(key_mask)
-        return _qkv_attn_prefix_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, num_heads, accumulate,
-                                    attn_dropout, dx_residual)
+        return _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, None, num_heads, accumulate,
+                                  attn_dropout, dx_residual)
     if attn_bias is not None or head_mask is not None or d_bias is not None:
         if key_mask is not None or mask_bits is not None:
             raise ValueError("qkv_attn_bwd: attn_bias / head_mask replace key_mask / mask_bits")
@@ -1038,7 +1038,7 @@ def qkv_attn_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, mask_bits=Non
             raise ValueError("qkv_attn_bwd: no ctx / lse / dump on the attn_bias / head_mask route (it recomputes the row statistics)")
         if d_align is not None:
             raise ValueError("qkv_attn_bwd: no align-map gradient (d_align) on the attn_bias / head_mask route")
-        return _qkv_attn_bias_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, num_heads, accumulate,
+        return _qkv_attn_bias_bwd(dctx, x, None, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, num_heads, accumulate,
                                   attn_dropout, dx_residual)
     dt = dt_of(x)
     x, dctx = _contig(x), _contig(dctx)
@@ -1077,28 +1077,49 @@ def qkv_attn_bias_bwd_route(n, s, h, a, dtype=BF16):
     return ATTN_BIAS_BWD_CORES[lib().modcr_qkv_attn_bias_bwd_route(n, s, h, a, dtype)]
 
 
-def _qkv_attn_bias_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, a, accumulate, attn_dropout, dx_residual):
-    """qkv_attn_bwd with attn_bias / head_mask: modcr_qkv_attn_bias_bwd"""
+def qkv_attn_prefix_bwd_route(n, s, p, h, a, dtype=BF16):
+    """The core modcr_qkv_attn_prefix_bwd runs for this shape (nothing is launched): "mfma", "exact" or "refused"."""
+    return ATTN_BIAS_BWD_CORES[lib().modcr_qkv_attn_prefix_bwd_route(n, s, p, h, a, dtype)]
+
+
+def _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, a, accumulate, attn_dropout, dx_residual):
+    """qkv_attn_bwd with attn_bias / head_mask: modcr_qkv_attn_bias_bwd -> dx, or with hist modcr_qkv_attn_prefix_bwd -> (dx, d_hist)"""
     dt = dt_of(x)
-    x, dctx = _contig(x), _contig(dctx)
     n, s, h = x.shape
-    if s > ATTN_BWD_MAX_KEYS:
-        raise ValueError("qkv_attn_bwd: S = %d exceeds the %d-key limit of the attention backward" % (s, ATTN_BWD_MAX_KEYS))
+    p = 0
+    if hist is not None:
+        if hist.dim() != 3 or hist.shape[0] != n or hist.shape[2] != h or hist.shape[1] < 1 or hist.dtype != x.dtype:
+            raise ValueError("qkv_attn_bwd: hist must be [N, P >= 1, H] in x's dtype, got %s %s" % (tuple(hist.shape), hist.dtype))
+        p = hist.shape[1]
+    l = p + s
+    if l > ATTN_BWD_MAX_KEYS:
+        raise ValueError(("qkv_attn_bwd: P + S = %d keys exceeds the %d-key limit of the attention backward" if p else
+                          "qkv_attn_bwd: S = %d exceeds the %d-key limit of the attention backward") % (l, ATTN_BWD_MAX_KEYS))
     if attn_bias is None and head_mask is None:
-        raise ValueError("qkv_attn_bwd: d_bias without attn_bias")
-    bias, (bsn, bsa, bsq) = (None, (0, 0, 0)) if attn_bias is None else _bias_strides(attn_bias, n, a, s, s)
+        raise ValueError("qkv_attn_bwd: hist needs attn_bias, key_mask or head_mask" if p else "qkv_attn_bwd: d_bias without attn_bias")
+    bias, (bsn, bsa, bsq) = (None, (0, 0, 0)) if attn_bias is None else _bias_strides(attn_bias, n, a, s, l)
     hm, hsn = (None, 0) if head_mask is None else _head_mask_2d(head_mask, n, a)
-    if d_bias is not None and (bias is None or d_bias.dtype != torch.float32 or tuple(d_bias.shape) != (n, a, s, s) or not d_bias.is_contiguous()):
-        raise ValueError("qkv_attn_bwd: d_bias must be a contiguous fp32 [N, A, S, S] tensor, given together with attn_bias")
+    if d_bias is not None and (bias is None or d_bias.dtype != torch.float32 or tuple(d_bias.shape) != (n, a, s, l) or not d_bias.is_contiguous()):
+        raise ValueError("qkv_attn_bwd: d_bias must be a contiguous fp32 [N, A, S, %s] tensor, given together with attn_bias" % ("P + S" if p else "S"))
+    x, dctx = _contig(x), _contig(dctx)
     dx = torch.empty_like(x)
+    res = _contig(dx_residual, torch.float32) if dx_residual is not None else None
+    ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
+    if p:
+        hist = _contig(hist)
+        d_hist = torch.empty_like(hist)
+        need = lib().modcr_qkv_attn_prefix_bwd_workspace(n, s, p, h, dt)
+        ws = _workspace("attn_bwd", need, x.device)
+        _check(lib().modcr_qkv_attn_prefix_bwd(_ptr(dctx), _ptr(x), _ptr(hist), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq,
+                                               _ptr(hm), hsn, _ptr(res), _ptr(dx), _ptr(d_hist), _ptr(dwqkv), _ptr(dbqkv), 1 if accumulate else 0,
+                                               _ptr(d_bias), n, s, p, h, a, float(ap), seed, off, _ptr(ws), need, dt, _stream()),
+               "modcr_qkv_attn_prefix_bwd")
+        return dx, d_hist
     need = lib().modcr_qkv_attn_bias_bwd_workspace(n, s, h, dt)
     ws = _workspace("attn_bwd", need, x.device)
     chunk_t = 0 if chunk_id is None else chunk_id.shape[1]
-    ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
     _check(lib().modcr_qkv_attn_bias_bwd(_ptr(dctx), _ptr(x), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq, _ptr(hm), hsn,
-                                         _ptr(chunk_id), chunk_t,
-                                         _ptr(_contig(dx_residual, torch.float32)) if dx_residual is not None else None,
-                                         _ptr(dx), _ptr(dwqkv), _ptr(dbqkv), 1 if accumulate else 0, _ptr(d_bias),
+                                         _ptr(chunk_id), chunk_t, _ptr(res), _ptr(dx), _ptr(dwqkv), _ptr(dbqkv), 1 if accumulate else 0, _ptr(d_bias),
                                          n, s, h, a, float(ap), seed, off, _ptr(ws), need, dt, _stream()),
            "modcr_qkv_attn_bias_bwd")
     return dx
@@ -1109,40 +1130,6 @@ def fold_key_mask(key_mask):
     if key_mask.dim() != 2:
         raise ValueError("fold_key_mask: key_mask must be [N, L], got %s" % (tuple(key_mask.shape),))
     return ((1.0 - key_mask.to(torch.float32)) * -10000.0).reshape(key_mask.shape[0], 1, 1, key_mask.shape[1])
-
-
-def qkv_attn_prefix_bwd_route(n, s, p, h, a, dtype=BF16):
-    """The core modcr_qkv_attn_prefix_bwd runs for this shape (nothing is launched): "mfma", "exact" or "refused"."""
-    return ATTN_BIAS_BWD_CORES[lib().modcr_qkv_attn_prefix_bwd_route(n, s, p, h, a, dtype)]
-
-
-def _qkv_attn_prefix_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, a, accumulate, attn_dropout, dx_residual):
-    """qkv_attn_bwd with hist: modcr_qkv_attn_prefix_bwd"""
-    dt = dt_of(x)
-    n, s, h = x.shape
-    if hist.dim() != 3 or hist.shape[0] != n or hist.shape[2] != h or hist.shape[1] < 1 or hist.dtype != x.dtype:
-        raise ValueError("qkv_attn_bwd: hist must be [N, P >= 1, H] in x's dtype, got %s %s" % (tuple(hist.shape), hist.dtype))
-    p = hist.shape[1]
-    l = p + s
-    if l > ATTN_BWD_MAX_KEYS:
-        raise ValueError("qkv_attn_bwd: P + S = %d keys exceeds the %d-key limit of the attention backward" % (l, ATTN_BWD_MAX_KEYS))
-    if attn_bias is None and head_mask is None:
-        raise ValueError("qkv_attn_bwd: hist needs attn_bias, key_mask or head_mask")
-    bias, (bsn, bsa, bsq) = (None, (0, 0, 0)) if attn_bias is None else _bias_strides(attn_bias, n, a, s, l)
-    hm, hsn = (None, 0) if head_mask is None else _head_mask_2d(head_mask, n, a)
-    if d_bias is not None and (bias is None or d_bias.dtype != torch.float32 or tuple(d_bias.shape) != (n, a, s, l) or not d_bias.is_contiguous()):
-        raise ValueError("qkv_attn_bwd: d_bias must be a contiguous fp32 [N, A, S, P + S] tensor, given together with attn_bias")
-    x, dctx, hist = _contig(x), _contig(dctx), _contig(hist)
-    dx, d_hist = torch.empty_like(x), torch.empty_like(hist)
-    need = lib().modcr_qkv_attn_prefix_bwd_workspace(n, s, p, h, dt)
-    ws = _workspace("attn_bwd", need, x.device)
-    ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
-    _check(lib().modcr_qkv_attn_prefix_bwd(_ptr(dctx), _ptr(x), _ptr(hist), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq,
-                                           _ptr(hm), hsn, _ptr(_contig(dx_residual, torch.float32)) if dx_residual is not None else None,
-                                           _ptr(dx), _ptr(d_hist), _ptr(dwqkv), _ptr(dbqkv), 1 if accumulate else 0, _ptr(d_bias),
-                                           n, s, p, h, a, float(ap), seed, off, _ptr(ws), need, dt, _stream()),
-           "modcr_qkv_attn_prefix_bwd")
-    return dx, d_hist
 
 
 def add(a, b, out_dtype=F32, out=None):

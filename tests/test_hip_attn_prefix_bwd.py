@@ -1,5 +1,5 @@
 """GPU tests of the attention backward with prefix rows / history states (modcr_qkv_attn_prefix_bwd: the cores of
-csrc/attn_prefix_bwd.hip behind modcr_hip.qkv_attn_bwd(hist=), hip_layers.layer_forward_train(hist=) / layer_backward,
+csrc/attn_bias_bwd.hip behind modcr_hip.qkv_attn_bwd(hist=), hip_layers.layer_forward_train(hist=) / layer_backward,
 hip_autograd.BertLayerPrefixFn and trainable_encoders.encoder_layers(encoder_history_states=)), P + S <= 256, bf16 and fp32.
 
 Checker: torch autograd in float64 on the CPU of

@@ -1,7 +1,7 @@
 """How much of the bf16 bounds of tests/test_hip_attn_prefix_bwd.py the number formats alone use (CPU, no GPU needed).
 
 The attention backward with prefix rows is restated in float64 with every quantity the bf16 route holds in bf16 rounded to bf16
-where the MFMA core of csrc/attn_prefix_bwd.hip rounds it: the recomputed q | k | v rows, the scaled queries, the probabilities
+where the MFMA core of csrc/attn_bias_bwd.hip rounds it: the recomputed q | k | v rows, the scaled queries, the probabilities
 P'' and the dS tile that enter the dV / dK / dQ products, the dq | dk | dv rows, and dx / d_hist as they leave their GEMMs (above
 192 keys the exact core keeps fp32 rows: only dx and d_hist are rounded).  Inputs are those of the tests' soft-bias case: the six
 shapes, the three bias forms, head mask (1, 0.5), p = 0.2.  Each line is the share of a bound this restatement uses against the

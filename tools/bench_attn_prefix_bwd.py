@@ -1,4 +1,4 @@
-"""Times the attention backward with prefix rows (modcr_qkv_attn_prefix_bwd: csrc/attn_prefix_bwd.hip) next to the only thing
+"""Times the attention backward with prefix rows (modcr_qkv_attn_prefix_bwd: csrc/attn_bias_bwd.hip) next to the only thing
 the library offered for the same gradients before it: modcr_qkv_attn_bias_bwd over the concatenated [hist ; x] rows, with zero
 dctx rows for the prefix (their queries then add nothing) and the bias over L = P + S query rows, dx[:, :P] being d_hist.
 
