@@ -459,7 +459,8 @@ int modcr_qkv_attn_opt_bwd(const void* dctx, const void* x, const void* wqkv, co
  *             broadcast bias's gradient is its sum over the broadcast dimensions: the caller's reduction).  Every element is
  *             written, by exactly one lane: no atomics, repeated calls are bit-identical.  A -inf entry has probability 0 and
  *             d_bias 0; a query row whose every key is -inf (the forward's P = 0 row) adds exactly nothing to dx, dwqkv,
- *             dbqkv and has a zero d_bias row.  No gradient for head_mask: it is a constant (head pruning).
+ *             dbqkv and has a zero d_bias row.  No gradient for head_mask here: it is a constant (head pruning);
+ *             modcr_qkv_attn_gate_bwd forms it.
  *   dctx, x, wqkv, bqkv, chunk_id, dx_residual, dx, dwqkv, dbqkv, accumulate: as modcr_qkv_attn_dropout_bwd.
  * The core recomputes the row statistics from the recomputed q | k | v rows (the bias forward writes no lse / dump):
  * attn_bias_bwd_mfma_kernel (bf16, S <= 192) or the exact attn_bias_bwd_f32_kernel (fp32; bf16 with 192 < S <= 256), both in
@@ -497,6 +498,33 @@ int modcr_qkv_attn_prefix_bwd(const void* dctx, const void* x, const void* hist,
                               float* dwqkv, float* dbqkv, int32_t accumulate, float* d_bias, int32_t N, int32_t S, int32_t P,
                               int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, void* workspace,
                               int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
+/* modcr_qkv_attn_bias_bwd and modcr_qkv_attn_prefix_bwd in one entry (P >= 0), WITH the gradient of head_mask (head importance,
+ * learned head gates).  The same host body, workspace layout, route choice, limits and error codes as those two; their arguments,
+ * in modcr_qkv_attn_prefix_bwd's order, plus chunk_id / chunk_t (behind head_mask_stride_n, as modcr_qkv_attn_bias_bwd's) and
+ * d_head_mask (behind d_bias):
+ *   P, hist, d_hist: P >= 0; hist and d_hist are NULL exactly when P == 0.  chunk_id (chunk-mean queries) only with P == 0.
+ *   d_head_mask  fp32 contiguous [N, A] or NULL, written:
+ *                    d_hm[n, a] = sum_i dctx_i . (P'.V)_i = sum_i sum_j P_ij (m_ij / (1 - p)) (dctx_i . v_j)
+ *                over the S queries and the L = P + S keys of head a -- the derivative with respect to the multiplier ITSELF, so it
+ *                is formed without head_mask: at head_mask[n, a] = 0 every other gradient of the head is exactly 0 and this one is
+ *                not.  A head_mask broadcast over N receives the sum over n (the caller's reduction, as for d_bias).  One workgroup
+ *                per (n, a), one lane writes the element, the summation order is fixed: no atomics, repeated calls are
+ *                bit-identical.  A query row whose every key is -inf adds 0.  Nothing else the call writes depends on whether
+ *                d_head_mask is given.
+ *   head_mask    may be NULL together with d_head_mask != NULL: the gradient at a mask of ones (head importance).  At least one of
+ *                attn_bias, head_mask, d_head_mask is given.
+ * With d_head_mask == NULL the call is that of the other two entries.  Cores: the DHM instantiations of attn_bias_bwd_mfma_kernel /
+ * attn_bias_bwd_f32_kernel (csrc/attn_bias_bwd.hip); modcr_qkv_attn_gate_bwd_route: 0 = refused, 1 = MFMA core, 2 = exact core.
+ * Every argument is validated before the first launch; P + S > 256 returns MODCR_ERR_UNSUPPORTED. */
+int64_t modcr_qkv_attn_gate_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype);
+int modcr_qkv_attn_gate_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype);
+int modcr_qkv_attn_gate_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                            const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                            const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
+                            const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv, int32_t accumulate,
+                            float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
+                            uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                            modcr_stream_t stream);
 
 /* ---- backward of the encoder layer's GEMM blocks (autograd of BertSelfOutput / BertIntermediate / BertOutput,
  * a_bert:362-373, :425-437, :440-451).  Gradients of parameters are fp32; dgamma / dbeta are ACCUMULATED (caller

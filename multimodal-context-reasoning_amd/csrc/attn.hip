@@ -2741,7 +2741,8 @@ extern "C" int modcr_qkv_attn_opt_bwd(const void* dctx, const void* x, const voi
                     N, S, H, A, attn_p, seed, offset, d_align, align_t, ctx, lse, qkv_dump, flags, workspace, workspace_bytes, dtype, stream);
 }
 
-// ---- backward of modcr_qkv_attn_bias_fwd: modcr_qkv_attn_bias_bwd (no prefix rows) and modcr_qkv_attn_prefix_bwd (hist [N, P, H], P >= 1) ----
+// ---- backward of modcr_qkv_attn_bias_fwd: modcr_qkv_attn_bias_bwd (no prefix rows), modcr_qkv_attn_prefix_bwd (hist [N, P, H], P >= 1)
+// and modcr_qkv_attn_gate_bwd (either, + the gradient of head_mask) ----
 // One body, attn_bwd()'s step for step with the cores of attn_bias_bwd.hip in step 2: S queries against P + S <= 256 keys, no
 // align-map gradient.  With prefix rows (no chunk mean then) a second, K | V only set of GEMMs serves them: rows H..3H of wqkv / bqkv
 // are a contiguous [2H, H] sub-block (ldw = H).
@@ -2773,12 +2774,12 @@ int attn_bias_bwd_core(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, in
 }
 
 // hist / d_hist / P: the prefix rows and their gradient (null, null, 0 from modcr_qkv_attn_bias_bwd); chunk_id / chunk_t: the chunk
-// mean of the queries (null, 0 from modcr_qkv_attn_prefix_bwd)
+// mean of the queries (null, 0 from modcr_qkv_attn_prefix_bwd); d_head_mask: fp32 [N, A] (null from both; modcr_qkv_attn_gate_bwd's)
 int attn_bias_bwd(const char* who, const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* attn_bias,
                   int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q, const float* head_mask, int64_t head_mask_stride_n,
                   const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv,
-                  int32_t accumulate, float* d_bias, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p, uint64_t seed,
-                  uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
+                  int32_t accumulate, float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
+                  uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
     MODCR_REQUIRE(dctx && x && wqkv && bqkv && dx && (d_hist || !P) && dwqkv && dbqkv, "%s: null pointer", who);
     MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "%s: unknown dtype %d", who, dtype);
     MODCR_REQUIRE(N > 0 && S > 0 && A > 0, "%s: bad shape (N=%d S=%d P=%d H=%d A=%d)", who, N, S, P, H, A);
@@ -2787,14 +2788,17 @@ int attn_bias_bwd(const char* who, const void* dctx, const void* x, const void* 
         modcr_set_error("%s: P + S = %lld keys (P=%d) exceeds the 256-key limit of the attention backward", who, (long long)P + S, P);
         return MODCR_ERR_UNSUPPORTED;
     }
-    MODCR_REQUIRE(attn_bias || head_mask, "%s: neither bias nor head_mask%s", who, P ? "" : " (that call belongs to modcr_qkv_attn_opt_bwd)");
+    // (with d_head_mask a missing head_mask is a mask of ones: the head-importance call)
+    MODCR_REQUIRE(attn_bias || head_mask || d_head_mask, "%s: neither bias nor head_mask%s", who,
+                  P ? "" : " (that call belongs to modcr_qkv_attn_opt_bwd)");
     MODCR_REQUIRE(attn_bias || !d_bias, "%s: d_bias without a bias", who);
     MODCR_REQUIRE(attn_p >= 0.f && attn_p < 1.f, "%s: attention dropout p=%g out of [0, 1)", who, attn_p);
     MODCR_REQUIRE(bias_stride_n >= 0 && bias_stride_a >= 0 && bias_stride_q >= 0 && head_mask_stride_n >= 0, "%s: negative stride", who);
     // (the cores address a (sequence, head) slice of the bias with 32-bit element offsets)
     MODCR_REQUIRE(bias_stride_q <= (1 << 20), "%s: bias query stride %lld exceeds 2^20 elements", who, (long long)bias_stride_q);
-    MODCR_REQUIRE(((uintptr_t)attn_bias & 3) == 0 && ((uintptr_t)head_mask & 3) == 0 && ((uintptr_t)d_bias & 3) == 0,
-                  "%s: bias / head_mask / d_bias not 4-byte aligned", who);
+    MODCR_REQUIRE(((uintptr_t)attn_bias & 3) == 0 && ((uintptr_t)head_mask & 3) == 0 && ((uintptr_t)d_bias & 3) == 0 &&
+                      ((uintptr_t)d_head_mask & 3) == 0,
+                  "%s: bias / head_mask / d_bias%s not 4-byte aligned", who, d_head_mask ? " / d_head_mask" : "");
     MODCR_REQUIRE(!chunk_id || (chunk_t > 0 && chunk_t <= S), "%s: chunk_t=%d out of range", who, chunk_t);
     MODCR_REQUIRE(dtype != MODCR_BF16 || (modcr_aligned16(dctx) && modcr_aligned16(x) && modcr_aligned16(hist) && modcr_aligned16(wqkv) &&
                                           modcr_aligned16(dx) && modcr_aligned16(d_hist)),
@@ -2832,7 +2836,7 @@ int attn_bias_bwd(const char* who, const void* dctx, const void* x, const void* 
     b.qkv = qkv; b.kvh = kvh; b.dctx = dctx; b.dqkv = dqkv; b.dkvh = dkvh;
     b.bias = attn_bias; b.bias_sn = bias_stride_n; b.bias_sa = bias_stride_a; b.bias_sq = bias_stride_q;
     b.head_mask = head_mask; b.head_mask_sn = head_mask_stride_n;
-    b.d_bias = d_bias;
+    b.d_bias = d_bias; b.d_head_mask = d_head_mask;
     const AttnDrop d = attn_drop(attn_p, seed, offset);     // (as the forward)
     b.drop_thr16 = d.thr16; b.drop_key = d.key; b.drop_keep = d.keep;
     b.N = N; b.S = S; b.P = P; b.H = H; b.A = A;
@@ -2872,8 +2876,8 @@ extern "C" int modcr_qkv_attn_bias_bwd(const void* dctx, const void* x, const vo
                                        float attn_p, uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
                                        modcr_stream_t stream) {
     return attn_bias_bwd("qkv_attn_bias_bwd", dctx, x, nullptr, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask,
-                         head_mask_stride_n, chunk_id, chunk_t, dx_residual, dx, nullptr, dwqkv, dbqkv, accumulate, d_bias, N, S, 0, H, A, attn_p,
-                         seed, offset, workspace, workspace_bytes, dtype, stream);
+                         head_mask_stride_n, chunk_id, chunk_t, dx_residual, dx, nullptr, dwqkv, dbqkv, accumulate, d_bias, nullptr, N, S, 0, H, A,
+                         attn_p, seed, offset, workspace, workspace_bytes, dtype, stream);
 }
 
 extern "C" int64_t modcr_qkv_attn_prefix_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
@@ -2894,6 +2898,34 @@ extern "C" int modcr_qkv_attn_prefix_bwd(const void* dctx, const void* x, const 
     const char* who = "qkv_attn_prefix_bwd";
     MODCR_REQUIRE(P >= 1 && hist, "%s: no prefix rows (P=%d, hist %s): that call belongs to modcr_qkv_attn_bias_bwd", who, P, hist ? "given" : "null");
     return attn_bias_bwd(who, dctx, x, hist, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask, head_mask_stride_n,
-                         nullptr, 0, dx_residual, dx, d_hist, dwqkv, dbqkv, accumulate, d_bias, N, S, P, H, A, attn_p, seed, offset, workspace,
-                         workspace_bytes, dtype, stream);
+                         nullptr, 0, dx_residual, dx, d_hist, dwqkv, dbqkv, accumulate, d_bias, nullptr, N, S, P, H, A, attn_p, seed, offset,
+                         workspace, workspace_bytes, dtype, stream);
+}
+
+// ---- modcr_qkv_attn_gate_bwd: the two entries above in one (P >= 0), with the gradient of head_mask ----
+extern "C" int64_t modcr_qkv_attn_gate_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
+    (void)dtype;
+    return N <= 0 || S <= 0 || P < 0 || H <= 0 ? 0 : attn_bias_bwd_ws(N, S, P, H).bytes();
+}
+
+extern "C" int modcr_qkv_attn_gate_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype) {
+    return attn_bias_bwd_core(N, S, P, H, A, dtype);
+}
+
+extern "C" int modcr_qkv_attn_gate_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                                       const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                                       const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
+                                       const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv, int32_t accumulate,
+                                       float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
+                                       uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                                       modcr_stream_t stream) {
+    const char* who = "qkv_attn_gate_bwd";
+    MODCR_REQUIRE(P >= 0, "%s: bad shape (P=%d)", who, P);
+    MODCR_REQUIRE((hist != nullptr) == (P > 0) && (d_hist != nullptr) == (P > 0),
+                  "%s: hist and d_hist are given exactly with prefix rows (P=%d, hist %s, d_hist %s)", who, P, hist ? "given" : "null",
+                  d_hist ? "given" : "null");
+    MODCR_REQUIRE(!chunk_id || P == 0, "%s: no chunk-mean queries with prefix rows (P=%d)", who, P);
+    return attn_bias_bwd(who, dctx, x, hist, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask, head_mask_stride_n,
+                         chunk_id, chunk_t, dx_residual, dx, d_hist, dwqkv, dbqkv, accumulate, d_bias, d_head_mask, N, S, P, H, A, attn_p, seed,
+                         offset, workspace, workspace_bytes, dtype, stream);
 }

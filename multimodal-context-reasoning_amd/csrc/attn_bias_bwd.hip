@@ -6,7 +6,8 @@
 //     dV = P''^T.dctx     dP = hm (m / (1 - p)) o (dctx.V^T)     dS = P o (dP - rowsum(dP o P))
 //     dQ = dS.K / 8  [S rows]     dK = dS^T.Q / 8  [L rows]     d_bias = dS  [N, A, S, L]
 // from the recomputed rows: the own rows' q | k | v projection [N*S][3H] and, with P > 0, the prefix rows' k | v projection
-// [N*P][2H].  modcr_qkv_attn_bias_bwd calls with P = 0, modcr_qkv_attn_prefix_bwd with P > 0; PREFIX = false makes P the
+// [N*P][2H].  modcr_qkv_attn_bias_bwd calls with P = 0, modcr_qkv_attn_prefix_bwd with P > 0, modcr_qkv_attn_gate_bwd with either and
+// with d_head_mask (DHM: d_hm[n, a] = sum_i dctx_i . (P'.V)_i, the derivative with respect to hm itself); PREFIX = false makes P the
 // compile-time constant 0, and every select between the two row buffers and every skip of an empty block falls away.  Both cores
 // recompute the row statistics (the bias forward writes none) and follow the older binary cores of attn.hip step for step --
 // attn_bias_bwd_mfma_kernel is attn_bwd_mfma_kernel (bf16 rows, L <= 192, two sub-passes, accumulators as operands),
@@ -50,8 +51,9 @@ __device__ __forceinline__ bf16x8 abb_tr8(const unsigned char* img, int tok0, in
     return o;
 }
 
-// PREFIX: prefix rows are given (else P = 0); BIAS: a bias is given (else the head mask alone); DBIAS: dS leaves as d_bias.
-template <bool PREFIX, bool BIAS, bool DBIAS>
+// PREFIX: prefix rows are given (else P = 0); BIAS: a bias is given (else the head mask alone); DBIAS: dS leaves as d_bias;
+// DHM: the gradient of the head's multiplier leaves as d_head_mask[n A + a].
+template <bool PREFIX, bool BIAS, bool DBIAS, bool DHM>
 __global__ __launch_bounds__(384, 3) void attn_bias_bwd_mfma_kernel(AttnBiasBwdArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int LP = ABB::LP;
@@ -252,6 +254,22 @@ __global__ __launch_bounds__(384, 3) void attn_bias_bwd_mfma_kernel(AttnBiasBwdA
         }
     }
     __syncthreads();
+    if constexpr (DHM) {
+        // d_hm = sum_i dctx_i . (P'.V)_i = sum_i sum_j P_ij (m_ij / (1 - p)) (dctx_i . v_j): the sum over the S real query rows of the
+        // delta sub-pass Q left in sDl, which carries no hm (hm enters at the stores only), so hm = 0 keeps its gradient.  A row whose
+        // every key is -inf left P = 0 and delta = 0; rows beyond S are not read.  One wave, a fixed order (three rows per lane in
+        // ascending order, then the butterfly), one store: two launches are bit-identical.
+        if (wave == 0) {
+            float g = 0.f;
+#pragma unroll
+            for (int r = 0; r < LP / 64; ++r) {
+                const int i = r * 64 + lane;
+                if (i < S) g += sDl[i];
+            }
+            g = wave_sum(g);
+            if (lane == 0) p.d_head_mask[n * p.A + a] = g;
+        }
+    }
     // ---- images of sub-pass K: Qs rows, dO rows (S of them) -------------------------------------------------------
     for (int it = tid; it < LP * 8; it += ABB::NT) {
         const int t = it >> 3, c = it & 7;
@@ -349,7 +367,7 @@ __global__ __launch_bounds__(384, 3) void attn_bias_bwd_mfma_kernel(AttnBiasBwdA
 // Pass A (K, V of the L keys in LDS; one query per wave-iteration, S of them): p_ij, dp_ij, delta_i, ds_ij (-> d_bias row i), dQ_i;
 // (max, 1 / sum, delta) of every query row stay in LDS.  Pass B (Q, dO of the S queries in LDS; one key per wave-iteration, L of
 // them): p and ds rebuilt from them, dV_j and dK_j to the prefix or the own rows.
-template <bool PREFIX, typename TD>
+template <bool PREFIX, typename TD, bool DHM>
 __global__ __launch_bounds__(256) void attn_bias_bwd_f32_kernel(AttnBiasBwdArgs p) {
     extern __shared__ float sm[];
     const int S = p.S, P = PREFIX ? p.P : 0, L = S + P, H = p.H;
@@ -383,6 +401,19 @@ __global__ __launch_bounds__(256) void attn_bias_bwd_f32_kernel(AttnBiasBwdArgs 
         attn_drop_words((uint32_t)((n * p.A + a) * 256 + i), j >> 2, p.drop_key, hx, hy);
         return attn_keep_field(hx, hy, j & 3, dthr) ? keepv : 0.f;
     };
+    // DHM: the same weight's factor WITHOUT hm, keep / (1 - p), next to it (one hash for both); keepv stays folded as it is --
+    // (hm keep) x and hm (keep x) round differently
+    const float keep1 = dthr ? p.drop_keep : 1.0f;
+    auto dmask2 = [&](int i, int j, float& m1) {
+        m1 = keep1;
+        if (!dthr) return keepv;
+        uint32_t hx, hy;
+        attn_drop_words((uint32_t)((n * p.A + a) * 256 + i), j >> 2, p.drop_key, hx, hy);
+        const bool kept = attn_keep_field(hx, hy, j & 3, dthr);
+        if (!kept) m1 = 0.f;
+        return kept ? keepv : 0.f;
+    };
+    float ghm = 0.f;                         // DHM: this lane's share of d_hm, over its keys of every query row of the wave
     // ---- pass A ------------------------------------------------------------------------------------------
     for (int idx = tid; idx < L * 64; idx += 256) {
         const int j = idx >> 6, d = idx & 63;
@@ -395,16 +426,23 @@ __global__ __launch_bounds__(256) void attn_bias_bwd_f32_kernel(AttnBiasBwdArgs 
         wq[lane] = qkv[(int64_t)i * 3 * H + lane];
         wd[lane] = to_f32(dctx[(int64_t)i * H + lane]);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        float sv[4], dp[4], mx = -INFINITY;
+        float sv[4], dp[4], dp1[4], mx = -INFINITY;         // dp1 (DHM): dp without hm
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int j = lane + 64 * c;
-            sv[c] = -INFINITY; dp[c] = 0.f;
+            sv[c] = -INFINITY; dp[c] = 0.f; dp1[c] = 0.f;
             if (j < L) {
                 float s = 0.f, t = 0.f;
                 for (int d = 0; d < 64; ++d) { s = fmaf(wq[d], sA[j * 65 + d], s); t = fmaf(wd[d], sB[j * 65 + d], t); }
                 s = s / 8.0f + bias_at(i, j);
-                sv[c] = s; dp[c] = t * dmask(i, j);
+                sv[c] = s;
+                if constexpr (DHM) {
+                    float m1;
+                    dp[c] = t * dmask2(i, j, m1);
+                    dp1[c] = t * m1;
+                } else {
+                    dp[c] = t * dmask(i, j);
+                }
                 mx = fmaxf(mx, s);
             }
         }
@@ -419,6 +457,10 @@ __global__ __launch_bounds__(256) void attn_bias_bwd_f32_kernel(AttnBiasBwdArgs 
 #pragma unroll
         for (int c = 0; c < 4; ++c) if (lane + 64 * c < L) { sv[c] *= inv; dl += sv[c] * dp[c]; }
         dl = wave_sum(dl);
+        if constexpr (DHM) {                // p_ij (kept ? 1 / (1 - p) : 0) (dctx_i . v_j); a row of -inf keys has p = 0
+#pragma unroll
+            for (int c = 0; c < 4; ++c) if (lane + 64 * c < L) ghm += sv[c] * dp1[c];
+        }
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             if (lane + 64 * c < L) {
@@ -433,7 +475,20 @@ __global__ __launch_bounds__(256) void attn_bias_bwd_f32_kernel(AttnBiasBwdArgs 
         dqkv[(int64_t)i * 3 * H + lane] = g / 8.0f;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     }
+    if constexpr (DHM) {
+        // the waves' sums through the head of their own row buffers (free until pass B fills them, behind the second barrier
+        // below), added in wave order by one lane
+        ghm = wave_sum(ghm);
+        if (lane == 0) wq[0] = ghm;
+    }
     __syncthreads();
+    if constexpr (DHM) {
+        if (tid == 0) {
+            float g = 0.f;
+            for (int w = 0; w < 4; ++w) g += sW[(size_t)w * (128 + 2 * L)];
+            p.d_head_mask[n * p.A + a] = g;
+        }
+    }
     // ---- pass B ------------------------------------------------------------------------------------------
     for (int idx = tid; idx < S * 64; idx += 256) {
         const int i = idx >> 6, d = idx & 63;
@@ -481,38 +536,38 @@ int abb_configure(K kernel, int bytes, bool& configured) {
     return MODCR_OK;
 }
 
-template <bool PREFIX, bool BIAS, bool DBIAS>
+template <bool PREFIX, bool BIAS, bool DBIAS, bool DHM>
 int launch_mfma(const AttnBiasBwdArgs& b, hipStream_t st) {
     static bool configured_dev[MODCR_MAX_DEV] = {};
-    const int rc = abb_configure(&attn_bias_bwd_mfma_kernel<PREFIX, BIAS, DBIAS>, ABB::SMEM, configured_dev[modcr_device_index()]);
+    const int rc = abb_configure(&attn_bias_bwd_mfma_kernel<PREFIX, BIAS, DBIAS, DHM>, ABB::SMEM, configured_dev[modcr_device_index()]);
     if (rc != MODCR_OK) return rc;
-    hipLaunchKernelGGL((attn_bias_bwd_mfma_kernel<PREFIX, BIAS, DBIAS>), dim3(b.N * b.A), dim3(ABB::NT), ABB::SMEM, st, b);
+    hipLaunchKernelGGL((attn_bias_bwd_mfma_kernel<PREFIX, BIAS, DBIAS, DHM>), dim3(b.N * b.A), dim3(ABB::NT), ABB::SMEM, st, b);
     return modcr_check_launch("attn_bias_bwd_mfma");
 }
 
-template <bool PREFIX, typename TD>
+template <bool PREFIX, typename TD, bool DHM>
 int launch_f32(const AttnBiasBwdArgs& b, hipStream_t st) {
     static bool configured_dev[MODCR_MAX_DEV] = {};
-    const int rc = abb_configure(&attn_bias_bwd_f32_kernel<PREFIX, TD>, 160 * 1024, configured_dev[modcr_device_index()]);
+    const int rc = abb_configure(&attn_bias_bwd_f32_kernel<PREFIX, TD, DHM>, 160 * 1024, configured_dev[modcr_device_index()]);
     if (rc != MODCR_OK) return rc;
     const size_t S = (size_t)b.S, L = (size_t)b.S + (size_t)b.P;
     const size_t smem = (2 * L * 65 + 3 * S + 4 * (128 + 2 * L)) * sizeof(float);         // 146 KB at S = L = 256
-    hipLaunchKernelGGL((attn_bias_bwd_f32_kernel<PREFIX, TD>), dim3(b.N * b.A), dim3(256), smem, st, b);
+    hipLaunchKernelGGL((attn_bias_bwd_f32_kernel<PREFIX, TD, DHM>), dim3(b.N * b.A), dim3(256), smem, st, b);
     return modcr_check_launch("attn_bias_bwd_f32");
 }
 
-template <bool PREFIX>
+template <bool PREFIX, bool DHM>
 int launch(const AttnBiasBwdArgs& b, int core, int32_t dtype, hipStream_t st) {
-    if (core != 1) return dtype == MODCR_BF16 ? launch_f32<PREFIX, bf16>(b, st) : launch_f32<PREFIX, float>(b, st);
-    if (!b.bias) return launch_mfma<PREFIX, false, false>(b, st);
-    return b.d_bias ? launch_mfma<PREFIX, true, true>(b, st) : launch_mfma<PREFIX, true, false>(b, st);
+    if (core != 1) return dtype == MODCR_BF16 ? launch_f32<PREFIX, bf16, DHM>(b, st) : launch_f32<PREFIX, float, DHM>(b, st);
+    if (!b.bias) return launch_mfma<PREFIX, false, false, DHM>(b, st);
+    return b.d_bias ? launch_mfma<PREFIX, true, true, DHM>(b, st) : launch_mfma<PREFIX, true, false, DHM>(b, st);
 }
 
 }  // namespace
 
 int modcr_launch_attn_bias_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype, hipStream_t stream) {
     const bool prefix = b.P > 0;
-    MODCR_REQUIRE(b.qkv && b.dctx && b.dqkv && (b.kvh != nullptr) == prefix && (b.dkvh != nullptr) == prefix && (b.bias || b.head_mask) &&
+    MODCR_REQUIRE(b.qkv && b.dctx && b.dqkv && (b.kvh != nullptr) == prefix && (b.dkvh != nullptr) == prefix && (b.bias || b.head_mask || b.d_head_mask) &&
                       (b.bias || !b.d_bias),
                   "attn_bias_bwd: null pointer");
     MODCR_REQUIRE(b.N > 0 && b.A > 0 && b.H == b.A * 64 && b.S > 0 && b.P >= 0 && (int64_t)b.S + b.P <= (core == 1 ? ABB::LP : 256),
@@ -521,5 +576,6 @@ int modcr_launch_attn_bias_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype
         MODCR_REQUIRE(dtype == MODCR_BF16 && modcr_aligned16(b.qkv) && modcr_aligned16(b.kvh) && modcr_aligned16(b.dctx) && modcr_aligned16(b.dqkv) &&
                           modcr_aligned16(b.dkvh),
                       "attn_bias_bwd: the MFMA core takes 16-byte aligned bf16 rows");
-    return prefix ? launch<true>(b, core, dtype, stream) : launch<false>(b, core, dtype, stream);
+    if (b.d_head_mask) return prefix ? launch<true, true>(b, core, dtype, stream) : launch<false, true>(b, core, dtype, stream);
+    return prefix ? launch<true, false>(b, core, dtype, stream) : launch<false, false>(b, core, dtype, stream);
 }

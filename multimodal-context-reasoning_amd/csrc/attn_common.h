@@ -142,6 +142,9 @@ struct AttnBiasBwdArgs {
     uint64_t drop_key;
     float drop_keep;
     int N, S, P, H, A;
+    // fp32 [N, A] or NULL: the gradient of the head's multiplier, d_hm[n, a] = sum_i dctx_i . (P'.V)_i (the DHM instantiations; one
+    // lane writes each element).  head_mask == NULL then stands for a mask of ones.  Last, so that every other field keeps its offset.
+    float* d_head_mask;
 };
 // core: 1 = attn_bias_bwd_mfma_kernel (bf16, P + S <= 192), 2 = attn_bias_bwd_f32_kernel (P + S <= 256); prefix rows where b.P > 0
 __attribute__((visibility("hidden"))) int modcr_launch_attn_bias_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype, hipStream_t stream);

@@ -104,6 +104,10 @@ SIGNATURES = {
     "modcr_qkv_attn_prefix_bwd_route": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "modcr_qkv_attn_prefix_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
                                          _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
+    "modcr_qkv_attn_gate_bwd_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_gate_bwd_route": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_gate_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
+                                       _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
     "modcr_linear_residual_ln_bwd_workspace": (_i64, [_i32, _i32, _i32]),
     "modcr_linear_residual_ln_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
                                             _vp, _i64, _i32, _vp]),
@@ -1009,7 +1013,7 @@ def adamw_step(p, g, m, v, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay,
 
 def qkv_attn_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, mask_bits=None, chunk_id=None, num_heads=None,
                  accumulate=False, attn_dropout=None, d_align=None, align_t=0, dx_residual=None, ctx=None, lse=None, dump=None,
-                 side_post_dropout=False, attn_bias=None, head_mask=None, d_bias=None, hist=None):
+                 side_post_dropout=False, attn_bias=None, head_mask=None, d_bias=None, hist=None, d_head_mask=None):
     """Backward of qkv_attn: returns dx [N,S,H] in x's dtype; dwqkv [3H,H] / dbqkv [3H] fp32 are
     written (or added into when accumulate).  attn_dropout = the (p, seed, offset) the forward ran with; d_align [N,T,R] =
     gradient of the align map the forward accumulated (align_t = T); dx_residual (fp32, x's shape) is added to dx in the
@@ -1021,7 +1025,10 @@ def qkv_attn_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, mask_bits=Non
     hist [N,P,H]: the prefix rows of a forward that ran qkv_attn(hist=, attn_bias= / head_mask=) (modcr_qkv_attn_prefix_bwd,
     P + S <= 256).  Returns (dx, d_hist [N,P,H] in x's dtype); attn_bias is then [.., L = P + S] and d_bias a contiguous fp32
     [N, A, S, L].  A binary key_mask [N, L] is folded on the host into a [N,1,1,L] 0 / -10000 bias (this route has no mask-bit
-    variant; use the same fold in the forward).  Not with ctx / lse / dump / d_align / chunk_id / mask_bits."""
+    variant; use the same fold in the forward).  Not with ctx / lse / dump / d_align / chunk_id / mask_bits.
+    d_head_mask: a contiguous fp32 [N, A] tensor that receives the gradient of the head's multiplier, sum_i dctx_i . (P'.V)_i per
+    sequence and head (sum_to_size it to the mask's own shape); the call then runs modcr_qkv_attn_gate_bwd, with or without hist, and
+    every other result is what it is without d_head_mask.  head_mask=None with d_head_mask stands for a mask of ones."""
     if hist is not None:
         if ctx is not None or lse is not None or dump is not None or d_align is not None or chunk_id is not None or mask_bits is not None:
             raise ValueError("qkv_attn_bwd: hist (prefix rows) does not combine with ctx / lse / dump / d_align / chunk_id / mask_bits")
@@ -1030,8 +1037,8 @@ def qkv_attn_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, mask_bits=Non
                 raise ValueError("qkv_attn_bwd: attn_bias replaces key_mask")
             attn_bias = fold_key_mask(key_mask)
         return _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, None, num_heads, accumulate,
-                                  attn_dropout, dx_residual)
-    if attn_bias is not None or head_mask is not None or d_bias is not None:
+                                  attn_dropout, dx_residual, d_head_mask)
+    if attn_bias is not None or head_mask is not None or d_bias is not None or d_head_mask is not None:
         if key_mask is not None or mask_bits is not None:
             raise ValueError("qkv_attn_bwd: attn_bias / head_mask replace key_mask / mask_bits")
         if ctx is not None or lse is not None or dump is not None:
@@ -1039,7 +1046,7 @@ def qkv_attn_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, mask_bits=Non
         if d_align is not None:
             raise ValueError("qkv_attn_bwd: no align-map gradient (d_align) on the attn_bias / head_mask route")
         return _qkv_attn_bias_bwd(dctx, x, None, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, num_heads, accumulate,
-                                  attn_dropout, dx_residual)
+                                  attn_dropout, dx_residual, d_head_mask)
     dt = dt_of(x)
     x, dctx = _contig(x), _contig(dctx)
     if (ctx is None) != (lse is None):
@@ -1082,8 +1089,15 @@ def qkv_attn_prefix_bwd_route(n, s, p, h, a, dtype=BF16):
     return ATTN_BIAS_BWD_CORES[lib().modcr_qkv_attn_prefix_bwd_route(n, s, p, h, a, dtype)]
 
 
-def _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, a, accumulate, attn_dropout, dx_residual):
-    """qkv_attn_bwd with attn_bias / head_mask: modcr_qkv_attn_bias_bwd -> dx, or with hist modcr_qkv_attn_prefix_bwd -> (dx, d_hist)"""
+def qkv_attn_gate_bwd_route(n, s, p, h, a, dtype=BF16):
+    """The core modcr_qkv_attn_gate_bwd runs for this shape, p >= 0 prefix rows (nothing is launched): "mfma", "exact" or "refused"."""
+    return ATTN_BIAS_BWD_CORES[lib().modcr_qkv_attn_gate_bwd_route(n, s, p, h, a, dtype)]
+
+
+def _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, a, accumulate, attn_dropout, dx_residual,
+                       d_head_mask=None):
+    """qkv_attn_bwd with attn_bias / head_mask: modcr_qkv_attn_bias_bwd -> dx, or with hist modcr_qkv_attn_prefix_bwd -> (dx, d_hist);
+    with d_head_mask modcr_qkv_attn_gate_bwd for both"""
     dt = dt_of(x)
     n, s, h = x.shape
     p = 0
@@ -1095,16 +1109,32 @@ def _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_
     if l > ATTN_BWD_MAX_KEYS:
         raise ValueError(("qkv_attn_bwd: P + S = %d keys exceeds the %d-key limit of the attention backward" if p else
                           "qkv_attn_bwd: S = %d exceeds the %d-key limit of the attention backward") % (l, ATTN_BWD_MAX_KEYS))
-    if attn_bias is None and head_mask is None:
+    if attn_bias is None and head_mask is None and d_head_mask is None:
         raise ValueError("qkv_attn_bwd: hist needs attn_bias, key_mask or head_mask" if p else "qkv_attn_bwd: d_bias without attn_bias")
     bias, (bsn, bsa, bsq) = (None, (0, 0, 0)) if attn_bias is None else _bias_strides(attn_bias, n, a, s, l)
     hm, hsn = (None, 0) if head_mask is None else _head_mask_2d(head_mask, n, a)
     if d_bias is not None and (bias is None or d_bias.dtype != torch.float32 or tuple(d_bias.shape) != (n, a, s, l) or not d_bias.is_contiguous()):
         raise ValueError("qkv_attn_bwd: d_bias must be a contiguous fp32 [N, A, S, %s] tensor, given together with attn_bias" % ("P + S" if p else "S"))
+    if d_head_mask is not None and (d_head_mask.dtype != torch.float32 or tuple(d_head_mask.shape) != (n, a) or not d_head_mask.is_contiguous() or
+                                    d_head_mask.device != x.device):
+        raise ValueError("qkv_attn_bwd: d_head_mask must be a contiguous fp32 [N, A] = [%d, %d] tensor on x's device, got %s %s" %
+                         (n, a, tuple(d_head_mask.shape), d_head_mask.dtype))
     x, dctx = _contig(x), _contig(dctx)
     dx = torch.empty_like(x)
     res = _contig(dx_residual, torch.float32) if dx_residual is not None else None
     ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
+    if d_head_mask is not None:
+        hist = _contig(hist) if p else None
+        d_hist = torch.empty_like(hist) if p else None
+        need = lib().modcr_qkv_attn_gate_bwd_workspace(n, s, p, h, dt)
+        ws = _workspace("attn_bwd", need, x.device)
+        chunk_t = 0 if chunk_id is None else chunk_id.shape[1]
+        _check(lib().modcr_qkv_attn_gate_bwd(_ptr(dctx), _ptr(x), _ptr(hist), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq,
+                                             _ptr(hm), hsn, _ptr(chunk_id), chunk_t, _ptr(res), _ptr(dx), _ptr(d_hist), _ptr(dwqkv), _ptr(dbqkv),
+                                             1 if accumulate else 0, _ptr(d_bias), _ptr(d_head_mask), n, s, p, h, a, float(ap), seed, off,
+                                             _ptr(ws), need, dt, _stream()),
+               "modcr_qkv_attn_gate_bwd")
+        return (dx, d_hist) if p else dx
     if p:
         hist = _contig(hist)
         d_hist = torch.empty_like(hist)

@@ -360,18 +360,21 @@ class BertLayerFn(_NotedFn):
 
 
 def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, params, key_mask=None, mask_bits=None, attn_bias=None,
-                        head_mask=None, hist=None, first_param=9):
-    """forward of BertLayerFn / BertLayerBiasFn / BertLayerPrefixFn: parameter i is input first_param + i (the first two take nine
-    arguments before the 16 parameters, BertLayerPrefixFn ten)"""
+                        head_mask=None, hist=None, first_param=9, head_mask_grad=False):
+    """forward of BertLayerFn / BertLayerBiasFn / BertLayerPrefixFn / BertLayerGateFn: parameter i is input first_param + i (the first
+    two take nine arguments before the 16 parameters, the other two ten); head_mask_grad: the class forms the gradient of head_mask
+    (BertLayerGateFn alone)"""
     from . import hip_layers
     s = x.shape[1] + (0 if hist is None else hist.shape[1])
+    need_hm = head_mask_grad and head_mask is not None and head_mask.requires_grad
     wants_grad = _caller_grad_mode()[-1] and (x.requires_grad or any(isinstance(p_, torch.Tensor) and p_.requires_grad for p_ in params) or
-                                              (attn_bias is not None and attn_bias.requires_grad) or (hist is not None and hist.requires_grad))
+                                              (attn_bias is not None and attn_bias.requires_grad) or (hist is not None and hist.requires_grad) or
+                                              need_hm)
     if s > mh.ATTN_TILE_KEYS and wants_grad:
         # the attention forward serves up to 512 keys, its backward (modcr_qkv_attn_bwd) 256: refuse before any launch
         raise NotImplementedError("a trainable layer at %s = %d exceeds the %d keys the attention backward takes; run it under "
                                   "torch.no_grad() (eval) up to %d keys" % ("S" if hist is None else "S + P", s, mh.ATTN_TILE_KEYS, mh.ATTN_MAX_KEYS))
-    if head_mask is not None and head_mask.requires_grad and _caller_grad_mode()[-1]:
+    if not head_mask_grad and head_mask is not None and head_mask.requires_grad and _caller_grad_mode()[-1]:
         raise NotImplementedError("head_mask is a constant of the trainable layer (head pruning): no gradient is formed for it; detach() it")
     align = packed.get("_align") if isinstance(packed, dict) else None       # (map buffer, T, gradient holder) of AlignMapFn
     amap, at = (align[0], align[1]) if align is not None else (None, 0)
@@ -388,6 +391,7 @@ def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, par
     ctx.need = [p_.requires_grad for p_ in params]
     ctx.need_x = x.requires_grad
     ctx.need_bias = attn_bias is not None and attn_bias.requires_grad
+    ctx.need_hm = need_hm
     # gradient sink: this node is ONE use of each of its parameters.  A layer applied twice in a graph (global_enc with trainable
     # encoders: the image-only pass and the full pass) has two: the node whose backward runs first still writes in place, but the
     # sink counts the bucket down only when the LAST use has reported (FlatGrads.done) -- or autograd's hook does, which fires
@@ -399,7 +403,8 @@ def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, par
 
 def _bert_layer_backward(ctx, dy):
     """backward of BertLayerFn / BertLayerBiasFn / BertLayerPrefixFn: (dx or None, the 16 parameter gradients -- None where the sink
-    took them --, the dense [N, A, S, L] bias gradient or None); a layer with a history state leaves its gradient in ctx.d_hist"""
+    took them --, the dense [N, A, S, L] bias gradient or None); a layer with a history state leaves its gradient in ctx.d_hist,
+    BertLayerGateFn's head-mask gradient [N, A] in ctx.d_hm"""
     from . import hip_layers
     d_align = ctx.holder.get("d_align") if ctx.holder is not None else None
     sink, outs, sunk = grad_sink(), {}, {}
@@ -431,9 +436,10 @@ def _bert_layer_backward(ctx, dy):
                         for nm in nms:
                             sunk[nm] = pmap[nm][0]
     dx, g = hip_layers.layer_backward(ctx.packed, ctx.saved, dy.contiguous(), mfma=not EXACT, d_align=d_align, outs=outs,
-                                      want_d_bias=ctx.need_bias)
+                                      want_d_bias=ctx.need_bias, want_d_head_mask=ctx.need_hm)
     ctx.saved = None
     ctx.d_hist = g.get("history_state")
+    ctx.d_hm = g.get("head_mask")
     grads = [None if (n in sunk or not need) else g[n] for n, need in zip(BertLayerFn.NAMES, ctx.need)]
     for prm in sunk.values():
         sink.done(prm)
@@ -489,6 +495,40 @@ class BertLayerPrefixFn(_NotedFn):
             d_bias = d_bias.sum_to_size(shape).to(dtype)
         d_hist, ctx.d_hist = (ctx.d_hist if ctx.need_hist else None), None
         return (dx, d_hist, d_bias) + (None,) * 7 + grads
+
+
+class BertLayerGateFn(_NotedFn):
+    """BertLayerPrefixFn's argument order with head_mask ([A], [N, A], anything broadcastable to [N, A, 1, 1]) as a DIFFERENTIABLE
+    input too (head importance, learned head gates): its gradient is the [N, A] sum_i dctx_i . (P'.V)_i of modcr_qkv_attn_gate_bwd
+    summed to the mask's own shape and cast to its dtype.  hist and attn_bias may be None, head_mask may not; chunk_id only without
+    hist.  S + P <= 256 under grad mode.  Ten arguments before the parameters; same gradient-sink protocol."""
+
+    @staticmethod
+    def forward(ctx, x, hist, attn_bias, head_mask, chunk_id, num_heads, eps, p, attn_p, packed, *params):
+        if head_mask is None:
+            raise ValueError("BertLayerGateFn: no head_mask (that layer is BertLayerBiasFn / BertLayerPrefixFn / BertLayerFn)")
+        if hist is not None and chunk_id is not None:
+            raise ValueError("BertLayerGateFn: no chunk-mean queries with a history state")
+        ctx.bias_shape = None if attn_bias is None else (tuple(attn_bias.shape), attn_bias.dtype)
+        ctx.hm_shape = (tuple(head_mask.shape), head_mask.dtype)
+        ctx.need_hist = hist is not None and hist.requires_grad
+        return _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, params, attn_bias=attn_bias, head_mask=head_mask,
+                                   hist=hist, first_param=10, head_mask_grad=True)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx, grads, d_bias = _bert_layer_backward(ctx, dy)
+        if d_bias is not None:
+            shape, dtype = ctx.bias_shape
+            d_bias = d_bias.sum_to_size(shape).to(dtype)
+        d_hist, ctx.d_hist = (ctx.d_hist if ctx.need_hist else None), None
+        d_hm, ctx.d_hm = ctx.d_hm, None
+        if d_hm is not None:
+            # [N, A] -> the mask's shape: a mask of fewer than two dimensions ([A], a scalar) is summed over N, a mask with trailing
+            # singleton dimensions ([N, A, 1, 1], [1, A, 1, 1]) takes them from a view
+            shape, dtype = ctx.hm_shape
+            d_hm = d_hm.reshape(d_hm.shape + (1,) * max(0, len(shape) - 2)).sum_to_size(shape).to(dtype)
+        return (dx, d_hist, d_bias, d_hm) + (None,) * 6 + grads
 
 
 class ResidualAddFn(torch.autograd.Function):

@@ -264,7 +264,7 @@ def _sub_ln_bwd(dy, pre, a_in, w, gamma, eps, dgamma, dbeta, drop, mfma, dw_out=
     return d_pre, da, dw, db
 
 
-def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None, want_d_bias=False):
+def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None, want_d_bias=False, want_d_head_mask=False):
     """dy [N,S,H] -> (dx [N,S,H] in x's dtype, {HF parameter name: fp32 gradient}).  Four C-ABI composites:
     modcr_ffn_down_residual_ln_bwd, modcr_ffn_up_gelu_bwd, modcr_proj_residual_ln_bwd, modcr_qkv_attn_bwd
     (the two residual-gradient sums ride in the epilogues of the dX GEMMs).  `mfma` is implied by the storage dtype (bf16 = MFMA route).
@@ -274,7 +274,9 @@ def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None, want_d_
     want_d_bias (a layer that ran with attn_bias): the dict also holds "attn_bias", the fp32 [N, A, S, S] gradient of the DENSE bias
     (dS of every sequence and head; the caller reduces it to the bias's own shape).
     A layer that ran with hist: the dict also holds "history_state", the [N,P,H] gradient of the history state in the storage dtype,
-    and "attn_bias" is [N, A, S, P + S]."""
+    and "attn_bias" is [N, A, S, P + S].
+    want_d_head_mask (a layer that ran with head_mask): the dict also holds "head_mask", the fp32 [N, A] gradient of the head's
+    multiplier per sequence and head (modcr_qkv_attn_gate_bwd; the caller reduces it to the mask's own shape)."""
     outs = outs or {}
     x, ctx, a, inter = saved["x"], saved["ctx"], saved["a"], saved["inter"]
     n, s, h = x.shape
@@ -332,13 +334,19 @@ def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None, want_d_
         hist = saved.get("hist")
         keys = s if hist is None else hist.shape[1] + s
         d_bias = torch.empty((n, saved["num_heads"], s, keys), dtype=f32, device=dev) if want_d_bias else None
+        if want_d_head_mask and saved.get("head_mask") is None:
+            raise ValueError("layer_backward: want_d_head_mask for a layer that ran without head_mask")
+        d_hm = torch.empty((n, saved["num_heads"]), dtype=f32, device=dev) if want_d_head_mask else None
         dx = mh.qkv_attn_bwd(d_ctx.view(n, s, h), x, layer["wqkv"], layer["bqkv"], dwqkv, dbqkv, chunk_id=saved["chunk_id"],
                              num_heads=saved["num_heads"], attn_dropout=saved.get("adrop"), dx_residual=d_pre1.view(n, s, h),
-                             attn_bias=saved.get("attn_bias"), head_mask=saved.get("head_mask"), d_bias=d_bias, hist=hist)
+                             attn_bias=saved.get("attn_bias"), head_mask=saved.get("head_mask"), d_bias=d_bias, hist=hist,
+                             d_head_mask=d_hm)
         if hist is not None:
             dx, g["history_state"] = dx
         if want_d_bias:
             g["attn_bias"] = d_bias
+        if want_d_head_mask:
+            g["head_mask"] = d_hm
     else:
         dx = mh.qkv_attn_bwd(d_ctx.view(n, s, h), x, layer["wqkv"], layer["bqkv"], dwqkv, dbqkv,
                              key_mask=saved["key_mask"], mask_bits=saved["mask_bits"], chunk_id=saved["chunk_id"],

@@ -114,6 +114,17 @@ def _run_layer_prefix(model, i, layer, hidden, hist, attn_bias, head_mask):
                                       float(ap), packed, *params)
 
 
+def _run_layer_gate(model, i, layer, hidden, hist, attn_bias, head_mask):
+    """_run_layer_bias / _run_layer_prefix (hist may be None) with head_mask a differentiable input (hip_autograd.BertLayerGateFn)"""
+    cfg = model.config
+    params = _layer_params(layer)
+    p = cfg.hidden_dropout_prob if model.training else 0.0
+    ap = getattr(cfg, "attention_probs_dropout_prob", 0.0) if model.training else 0.0
+    packed = _packed(model, i, layer, params, hidden.device, hidden.dtype)
+    return ag.BertLayerGateFn.apply(hidden, hist, attn_bias, head_mask, None, cfg.num_attention_heads, cfg.layer_norm_eps, float(p),
+                                    float(ap), packed, *params)
+
+
 def encoder_layers(model, hidden, attention_mask, head_mask=None, encoder_history_states=None):
     """CaptionBertEncoder.forward(hidden_states, attention_mask, head_mask, encoder_history_states) with gradients: the layers of
     model.encoder over hidden [N,S,H] (storage dtype) under the reference's 4-D ADDITIVE attention_mask (broadcastable to
@@ -123,13 +134,18 @@ def encoder_layers(model, hidden, attention_mask, head_mask=None, encoder_histor
     encoder_history_states: None, or one entry per layer, each None or a [N,P,H] tensor in the storage dtype that is prepended for
     that layer's K and V (modeling_bert.py:36-44) and may require grad (prefix tuning); attention_mask is then broadcastable to
     [N,A,S,P+S] and P + S <= 256 under grad mode.  Such a layer runs the prefix form (BertLayerPrefixFn) with the mask as it is;
-    layers without a history state keep their route."""
+    layers without a history state keep their route.
+    A layer whose head_mask[i] requires grad (under grad mode) runs BertLayerGateFn, with or without a history state, and the mask
+    receives its gradient (head importance: head_importance below); every other layer runs as without this."""
     from .modeling_bert import split_additive_mask
     n, s, _ = hidden.shape
     plain = None                                            # the split of the mask alone (one reduction and one host read)
     for i, layer in enumerate(model.encoder.layer):
         hm = None if head_mask is None else head_mask[i]
         hist = None if encoder_history_states is None else encoder_history_states[i]
+        if hm is not None and hm.requires_grad and torch.is_grad_enabled():
+            hidden = _run_layer_gate(model, i, layer, hidden, hist, attention_mask, hm)
+            continue
         if hist is not None:
             hidden = _run_layer_prefix(model, i, layer, hidden, hist, attention_mask, hm)
             continue
@@ -144,6 +160,27 @@ def encoder_layers(model, hidden, attention_mask, head_mask=None, encoder_histor
         else:
             hidden = _run_layer(model, i, layer, hidden, **args)
     return hidden
+
+
+def head_importance(model, hidden, attention_mask, loss_fn, encoder_history_states=None):
+    """Head-importance scores (Michel et al. 2019; HF run_bertology.py): |d loss / d head_mask| at a head mask of ones, fp32
+    [layers, A], for loss = loss_fn(encoder_layers(model, hidden, attention_mask, head_mask, encoder_history_states)) -- one forward
+    and one backward on the caller's batch (average the result over batches for E|.|).  The parameters are frozen inside the call,
+    so no parameter gradient is formed or touched, and their requires_grad is restored afterwards."""
+    cfg = model.config
+    hm = torch.ones(len(model.encoder.layer), cfg.num_attention_heads, dtype=torch.float32, device=hidden.device, requires_grad=True)
+    params = list(model.encoder.parameters())
+    flags = [p_.requires_grad for p_ in params]
+    try:
+        for p_ in params:
+            p_.requires_grad_(False)
+        with torch.enable_grad():
+            loss = loss_fn(encoder_layers(model, hidden.detach(), attention_mask, head_mask=hm, encoder_history_states=encoder_history_states))
+            grad, = torch.autograd.grad(loss, hm)
+    finally:
+        for p_, f in zip(params, flags):
+            p_.requires_grad_(f)
+    return grad.detach().abs()
 
 
 def global_encoder(model, input_ids, token_type_ids, attention_mask, position_ids, img_feats):
