@@ -441,8 +441,17 @@ __global__ __launch_bounds__(256) void align_attn_fwd_kernel(const float* q, con
         const int hh = tid >> 5, l32 = tid & 31;
         if (hh < heads) {
             float mx = -INFINITY;
-            if (key_bias)       // additive key mask (ClsLayer2's word_mask, v10:823): same for every head
-                for (int j = l32; j < L; j += 32) sS[j * heads + hh] += key_bias[(int64_t)n * L + j];
+            if (key_bias) {     // additive key mask (ClsLayer2's word_mask, v10:823): same for every head
+                // taken relative to its largest entry (the softmax does not see the shift): a sequence whose keys are ALL at
+                // -10000 then keeps the low bits of its scores, which score + (-10000) drops below ulp(10000) = 2^-10
+                const float* kbn = key_bias + (int64_t)n * L;
+                float bm = -INFINITY;
+                for (int j = l32; j < L; j += 32) bm = fmaxf(bm, kbn[j]);
+#pragma unroll
+                for (int o = 16; o > 0; o >>= 1) bm = fmaxf(bm, __shfl_xor(bm, o, 64));
+                if (bm == -INFINITY) bm = 0.f;
+                for (int j = l32; j < L; j += 32) sS[j * heads + hh] += kbn[j] - bm;
+            }
             for (int j = l32; j < L; j += 32) mx = fmaxf(mx, sS[j * heads + hh]);
 #pragma unroll
             for (int o = 16; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));

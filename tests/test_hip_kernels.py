@@ -443,6 +443,7 @@ def test_embedding_dropout_rides_on_the_passes_that_write_the_rows(mh, dtype):
 @pytest.mark.parametrize("n,l,e,heads", [(5, 57, 768, 8), (3, 237, 768, 8), (2, 9, 128, 2),
                                          (2, 579, 1024, 8), (2, 1100, 768, 8), (3, 700, 1024, 1)])     # keys in several LDS blocks (VCR: L = 3 * 193)
 def test_align_attn_fwd_bwd(mh, dtype, n, l, e, heads):
+    """binding-level check; element-wise against float64, route by route: tests/test_hip_head_attn.py"""
     rs = np.random.RandomState(9)
     d = e // heads
     scale = d ** -0.5
@@ -1197,7 +1198,8 @@ def test_align_attn_weight_dropout(mh, dtype):
 def test_cls_xattn_reassociated_form(mh, e, rows, p):
     """modcr_cls_xattn_fwd / _bwd (csrc/clsattn.hip): ctx[h] = sum_j p'[h][j] x_j, ssum[h] = sum_j p'[h][j] with
     p = softmax_j(qt[h] . x_j) over row blocks read in place (strided views of larger buffers), and d qt -- against
-    autograd on the same formula with the SAME dropout mask (read back from the counter-based generator)."""
+    autograd on the same formula with the SAME dropout mask (read back from the counter-based generator).
+    Element-wise against float64, every instantiation and the host mask: tests/test_hip_head_attn.py"""
     rs = np.random.RandomState(23 + e + len(rows))
     n, heads = 5, 8
     l = sum(rows)

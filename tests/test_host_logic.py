@@ -749,3 +749,76 @@ def test_rowops_case_tables_cover_every_route():
     assert set(T.FUSED_ROUTES) == {("f32", r, o) for r in (None, "bf16", "f32") for o in ("bf16", "f32")} | \
         {("f16", None, "bf16"), ("f16", "bf16", "bf16")}
     assert set(T.FUSED_H) >= {256, 772, 1024}
+
+
+def test_head_attn_case_tables_cover_every_class():
+    """tests/test_hip_head_attn.py states in each case's id the route its shape lands on (align_attn_lds and the cls_xattn switch,
+    restated there); a later edit to a table must not silently lose a kernel instantiation, a geometry class, a blocking class, a
+    dtype, a key_bias kind, a stride form, the aliased call or a dropout counter edge."""
+    import test_hip_head_attn as T
+    A = T.ALIGN_CASES
+    # the restatement at the figures the C code documents (E = 768, 8 heads)
+    assert T.align_max_l(768, 8, 1) == 4416 and T.align_max_l(768, 8, 2) == 2208
+    assert T.align_route(4416, 768, 8, 1)[0] == 16 and T.align_route(2208, 768, 8, 2)[0] == 16
+    assert T.align_route(4417, 768, 8, 1) is None and T.align_route(2209, 768, 8, 2) is None
+    assert T.align_last_unblocked(768, 8, 1) == 354 and T.align_last_unblocked(768, 8, 2) == 329
+    assert T.align_geom(520, 5) == (65, 3, 13, 61)
+    assert T.cls_max_l(768, 1) == 4352 and T.cls_max_l(768, 2) == 2176
+    assert {(c.e, c.heads) for c in A} >= set(T.ALIGN_EH) and len(T.ALIGN_EH) == 10
+    assert {T.align_geom(c.e, c.heads)[0] for c in A} == {1, 8, 16, 65, 96, 128, 256}
+    geom = [T.align_geom(c.e, c.heads) + (c.l,) for c in A]
+    assert any(ks == 1 for _, ks, _, _, _ in geom) and any(idle > 0 for _, _, _, idle, _ in geom) and any(ks > l for _, ks, _, _, l in geom)
+    for e, heads in T.ALIGN_EH:
+        ks = T.align_geom(e, heads)[1]
+        ls = {c.l for c in A if (c.e, c.heads) == (e, heads)}
+        assert ls >= {1, 2, 3, 4 * ks, 4 * ks + 1} | ({ks - 1} if ks > 1 else set()), (e, heads)
+        for t in (1, 2):
+            l0, lmax = T.align_last_unblocked(e, heads, t), T.align_max_l(e, heads, t)
+            blocks = {T.align_route(l, e, heads, t)[1] for l in ls if T.align_route(l, e, heads, t)}
+            assert {l0, l0 + 1} <= ls and 2 in blocks and max(blocks) >= 3, (e, heads, t)
+            assert T.align_route(l0, e, heads, t)[:2] == (l0, 1) and T.align_route(l0 + 1, e, heads, t)[1] == 2
+            assert {lmax, lmax + 1} <= ls and T.align_route(lmax + 1, e, heads, t) is None, (e, heads, t)
+        # only the backward walks the keys in blocks
+        assert any(T.align_route(l, e, heads, 1)[1] == 1 and (T.align_route(l, e, heads, 2) or (0, 1))[1] > 1
+                   for l in ls if T.align_route(l, e, heads, 1)), (e, heads)
+    for pick in (lambda c: c.dt, lambda c: c.bias, lambda c: (c.kpad, c.dpad), lambda c: c.p, lambda c: c.noprobs):
+        got = {pick(c) for c in A}
+        want = {pick(T.acase(8, 1, 1, dt=dt, bias=b, kpad=kp, dpad=dp, p=p, noprobs=nop)) for dt in ("f32", "bf16") for b in T.BIAS_KINDS
+                for kp in (0, 8) for dp in (0, 8) for p in (0.0, 0.1, 0.5) for nop in (False, True)}
+        assert got == want, got
+    for dt in ("f32", "bf16"):
+        mine = [c for c in A if c.dt == dt]
+        assert {c.bias for c in mine} == set(T.BIAS_KINDS) and {(c.kpad, c.dpad) for c in mine} == {(0, 0), (0, 8), (8, 0), (8, 8)}
+        assert {(c.p, c.off) for c in mine if c.p} >= {(p, o) for p in (0.1, 0.5) for o in T.ALIGN_OFF}
+        # the ClsLayer2 call
+        assert {c.p for c in mine if c.alias and c.scale1 and c.heads == 1 and c.bias == "ragged"} == {0.0, 0.1}
+        assert any(c.noprobs for c in mine)
+    assert T.drop_offset("0", 8, 57) == 0 and T.drop_offset("mod3", 8, 57) % 4 == 3
+    for c in A + [T.acase(768, 8, 237)]:                            # "cross": counter 2^32 falls strictly inside sequence 0
+        if c.heads * c.l > 1:
+            assert 0 < 2 ** 32 - T.drop_offset("cross", c.heads, c.l) < c.heads * c.l
+    ids = [T.align_id(c) for c in A]
+    assert len(set(ids)) == len(ids)
+
+    C = T.CLS_CASES
+    inst = {T.cls_route(c.e, sum(c.rows))[0] for c in C}
+    assert inst == {(1, 4, False), (2, 4, False), (3, 4, False), (3, 4, True), (4, 2, False), (4, 2, True)}, inst
+    want_e = {(1, 4, False): {4, 128, 256}, (2, 4, False): {260, 512}, (3, 4, False): {516, 764}, (3, 4, True): {768},
+              (4, 2, False): {772, 1020}, (4, 2, True): {1024}}
+    for k, es in want_e.items():
+        assert {c.e for c in C if T.cls_route(c.e, 1)[0] == k} >= es, k
+    for e in T.CLS_E:
+        mine = [c for c in C if c.e == e]
+        u4 = 4 * T.cls_route(e, 1)[0][1]
+        assert {sum(c.rows) for c in mine} >= {1, 2, 3, u4 - 1, u4, u4 + 1, 300}, e
+        assert {len(c.rows) for c in mine} == {1, 2, 3} and any(1 in c.rows and len(c.rows) > 1 for c in mine)
+    assert {c.ldpad for c in C} == {0, 4} and any(c.stride0 is not None for c in C)
+    assert {(c.p, c.off) for c in C if c.p} >= {(p, o) for p in (0.1, 0.5) for o in T.ALIGN_OFF} and any(c.p == 0 for c in C)
+    for e in T.CLS_MAX_E:
+        ls = {sum(c.rows) for c in C if c.e == e and c.n == 1}
+        assert ls >= {T.cls_max_l(e, 1), T.cls_max_l(e, 1) + 1, T.cls_max_l(e, 2), T.cls_max_l(e, 2) + 1}
+        assert T.cls_route(e, T.cls_max_l(e, 1))[1] == 160 * 1024 and T.cls_route(e, T.cls_max_l(e, 1) + 1)[1] is None
+        assert T.cls_route(e, T.cls_max_l(e, 2))[2] == 160 * 1024 and T.cls_route(e, T.cls_max_l(e, 2) + 1)[2] is None
+    assert 768 in T.CLS_MAX_E
+    ids = [T.cls_id(c) for c in C]
+    assert len(set(ids)) == len(ids)
