@@ -525,6 +525,30 @@ int modcr_qkv_attn_gate_bwd(const void* dctx, const void* x, const void* hist, c
                             float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
                             uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
                             modcr_stream_t stream);
+/* modcr_qkv_attn_gate_bwd with the key limit 512 instead of 256 (opt-in: training a batch padded past 256 keys).  The arguments are
+ * modcr_qkv_attn_gate_bwd's, in its order.
+ *   P + S <= 256: the call IS modcr_qkv_attn_gate_bwd -- same body, same bits, same codes, dropout included; _workspace and _route
+ *             answer what the gate entry answers.
+ *   256 < P + S <= 512: the same host body (recomputed q | k | v rows, chunk mean and its adjoint, dx, dwqkv, dbqkv, d_hist) around
+ *             the streaming cores of csrc/attn_long_bwd.hip, which keep 64-row tiles in LDS instead of a head's whole key row: a
+ *             query kernel (row statistics, then dS / d_bias / dQ per 64-query block) and a key kernel (dK | dV per 64-key block).
+ *             d_bias, d_head_mask, -inf entries, all -inf rows and head_mask = 0 behave as documented for the entries above; every
+ *             output element is written by exactly one lane, no atomics, repeated calls are bit-identical.  No attention-probability
+ *             dropout there: attn_p > 0 returns MODCR_ERR_UNSUPPORTED (the dropout counter of a head ends at 256 queries).
+ *             The workspace is the gate entry's layout followed by the per-row statistics, fp32 [N A][3][S rounded up to 64].
+ *   P + S > 512 returns MODCR_ERR_UNSUPPORTED.
+ * modcr_qkv_attn_long_bwd_route: 0 = refused, 1 = MFMA core, 2 = exact core (both as modcr_qkv_attn_gate_bwd_route), 3 = streaming
+ * bf16 kernels, 4 = streaming exact fp32 kernels.  Every argument is validated before the first launch; a refused call writes
+ * nothing. */
+int64_t modcr_qkv_attn_long_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype);
+int modcr_qkv_attn_long_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype);
+int modcr_qkv_attn_long_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                            const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                            const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
+                            const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv, int32_t accumulate,
+                            float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
+                            uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                            modcr_stream_t stream);
 
 /* ---- backward of the encoder layer's GEMM blocks (autograd of BertSelfOutput / BertIntermediate / BertOutput,
  * a_bert:362-373, :425-437, :440-451).  Gradients of parameters are fp32; dgamma / dbeta are ACCUMULATED (caller

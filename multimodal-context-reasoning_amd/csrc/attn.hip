@@ -2746,16 +2746,20 @@ extern "C" int modcr_qkv_attn_opt_bwd(const void* dctx, const void* x, const voi
 // One body, attn_bwd()'s step for step with the cores of attn_bias_bwd.hip in step 2: S queries against P + S <= 256 keys, no
 // align-map gradient.  With prefix rows (no chunk mean then) a second, K | V only set of GEMMs serves them: rows H..3H of wqkv / bqkv
 // are a contiguous [2H, H] sub-block (ldw = H).
+// modcr_qkv_attn_long_bwd is the same body with the key limit 512 (max_keys): at P + S <= 256 nothing differs; above, step 2 runs the
+// streaming cores of attn_long_bwd.hip (no dropout there) and the workspace grows by their per-row statistics.
 namespace {
 
 // The workspace: q | k | v and dq | dk | dv rows of the own rows (rows_x each), k | v and dk | dv rows of the prefix rows (rows_h
 // each; 0 without), then the GEMMs' sub-workspace (the larger of the two sets' needs)
+// ... and, above 256 keys only (the streaming cores), their per-row statistics fp32 [N A][3][S rounded up to 64] at the end
 struct AttnBiasBwdWs {
-    int64_t rows_x, rows_h, sub;
-    int64_t bytes() const { return 2 * rows_x + 2 * rows_h + sub; }
+    int64_t rows_x, rows_h, sub, stats;
+    int64_t bytes() const { return 2 * rows_x + 2 * rows_h + sub + stats; }
 };
-AttnBiasBwdWs attn_bias_bwd_ws(int32_t N, int32_t S, int32_t P, int32_t H) {
+AttnBiasBwdWs attn_bias_bwd_ws(int32_t N, int32_t S, int32_t P, int32_t H, int max_keys = 256) {
     AttnBiasBwdWs w;
+    w.stats = (int64_t)P + S <= 256 || max_keys <= 256 ? 0 : (((int64_t)N * (H / 64) * 3 * ((S + 63) & ~63) * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
     w.rows_x = (((int64_t)N * S * 3 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
     w.rows_h = (((int64_t)N * P * 2 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
     w.sub = attn_bwd_sub_ws(N * S, H);
@@ -2767,25 +2771,33 @@ AttnBiasBwdWs attn_bias_bwd_ws(int32_t N, int32_t S, int32_t P, int32_t H) {
     return w;
 }
 
-// 0 = refused, 1 = attn_bias_bwd_mfma_kernel, 2 = attn_bias_bwd_f32_kernel
-int attn_bias_bwd_core(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype) {
-    if (N <= 0 || S <= 0 || P < 0 || (int64_t)P + S > 256 || A <= 0 || H != A * 64 || (dtype != MODCR_BF16 && dtype != MODCR_F32)) return 0;
+// 0 = refused, 1 = attn_bias_bwd_mfma_kernel, 2 = attn_bias_bwd_f32_kernel; with max_keys = 512 (modcr_qkv_attn_long_bwd) above 256
+// keys: 3 = the streaming bf16 kernels of attn_long_bwd.hip, 4 = its exact fp32 kernels
+int attn_bias_bwd_core(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype, int max_keys = 256) {
+    if (N <= 0 || S <= 0 || P < 0 || (int64_t)P + S > max_keys || A <= 0 || H != A * 64 || (dtype != MODCR_BF16 && dtype != MODCR_F32)) return 0;
+    if (P + S > 256) return dtype == MODCR_BF16 ? 3 : 4;
     return dtype == MODCR_BF16 && P + S <= AB::LP ? 1 : 2;
 }
 
 // hist / d_hist / P: the prefix rows and their gradient (null, null, 0 from modcr_qkv_attn_bias_bwd); chunk_id / chunk_t: the chunk
-// mean of the queries (null, 0 from modcr_qkv_attn_prefix_bwd); d_head_mask: fp32 [N, A] (null from both; modcr_qkv_attn_gate_bwd's)
+// mean of the queries (null, 0 from modcr_qkv_attn_prefix_bwd); d_head_mask: fp32 [N, A] (null from both; modcr_qkv_attn_gate_bwd's);
+// max_keys: 256, or 512 from modcr_qkv_attn_long_bwd
 int attn_bias_bwd(const char* who, const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* attn_bias,
                   int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q, const float* head_mask, int64_t head_mask_stride_n,
                   const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv,
                   int32_t accumulate, float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
-                  uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
+                  uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream,
+                  int max_keys = 256) {
     MODCR_REQUIRE(dctx && x && wqkv && bqkv && dx && (d_hist || !P) && dwqkv && dbqkv, "%s: null pointer", who);
     MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "%s: unknown dtype %d", who, dtype);
     MODCR_REQUIRE(N > 0 && S > 0 && A > 0, "%s: bad shape (N=%d S=%d P=%d H=%d A=%d)", who, N, S, P, H, A);
     MODCR_REQUIRE(H == A * 64, "%s: head size must be 64 (H=%d, A=%d)", who, H, A);
-    if ((int64_t)P + S > 256) {
-        modcr_set_error("%s: P + S = %lld keys (P=%d) exceeds the 256-key limit of the attention backward", who, (long long)P + S, P);
+    if ((int64_t)P + S > max_keys) {
+        modcr_set_error("%s: P + S = %lld keys (P=%d) exceeds the %d-key limit of the attention backward", who, (long long)P + S, P, max_keys);
+        return MODCR_ERR_UNSUPPORTED;
+    }
+    if ((int64_t)P + S > 256 && attn_p > 0.f) {
+        modcr_set_error("%s: attention-probability dropout (p=%g) is not implemented above 256 keys (P+S=%d)", who, attn_p, P + S);
         return MODCR_ERR_UNSUPPORTED;
     }
     // (with d_head_mask a missing head_mask is a mask of ones: the head-importance call)
@@ -2803,10 +2815,12 @@ int attn_bias_bwd(const char* who, const void* dctx, const void* x, const void* 
     MODCR_REQUIRE(dtype != MODCR_BF16 || (modcr_aligned16(dctx) && modcr_aligned16(x) && modcr_aligned16(hist) && modcr_aligned16(wqkv) &&
                                           modcr_aligned16(dx) && modcr_aligned16(d_hist)),
                   "%s(bf16): 16-byte alignment", who);
-    const AttnBiasBwdWs ws = attn_bias_bwd_ws(N, S, P, H);
+    const AttnBiasBwdWs ws = attn_bias_bwd_ws(N, S, P, H, max_keys);
     MODCR_REQUIRE(workspace && workspace_bytes >= ws.bytes() && modcr_aligned16(workspace), "%s: workspace %lld < %lld bytes (or unaligned)", who,
                   (long long)workspace_bytes, (long long)ws.bytes());
-    const int core = attn_bias_bwd_core(N, S, P, H, A, dtype);
+    const int core = attn_bias_bwd_core(N, S, P, H, A, dtype, max_keys);
+    // (the streaming kernels' grid is (block, head, sequence))
+    MODCR_REQUIRE(core < 3 || (N <= 65535 && A <= 65535), "%s: grid of N=%d sequences x A=%d heads too large", who, N, A);
     const int M = N * S, Mh = N * P;
     char* w = (char*)workspace;
     void* qkv = w;
@@ -2820,7 +2834,7 @@ int attn_bias_bwd(const char* who, const void* dctx, const void* x, const void* 
     const void* wkv = (const char*)wqkv + (size_t)H * H * esz;                  // rows H..3H of wqkv: the K | V projection [2H, H]
     // 1. recompute the rows (MFMA core: bf16, exact core: fp32): q | k | v of the own rows, chunk-mean queries as the forward; k | v of
     //    the prefix rows
-    const int32_t qdt = core == 1 ? MODCR_BF16 : MODCR_F32;
+    const int32_t qdt = core == 1 || core == 3 ? MODCR_BF16 : MODCR_F32;
     int rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, qkv, 3 * H, M, 3 * H, H, MODCR_ACT_NONE, dtype, qdt, stream);
     if (rc != MODCR_OK) return rc;
     if (chunk_id) {
@@ -2840,7 +2854,8 @@ int attn_bias_bwd(const char* who, const void* dctx, const void* x, const void* 
     const AttnDrop d = attn_drop(attn_p, seed, offset);     // (as the forward)
     b.drop_thr16 = d.thr16; b.drop_key = d.key; b.drop_keep = d.keep;
     b.N = N; b.S = S; b.P = P; b.H = H; b.A = A;
-    rc = modcr_launch_attn_bias_bwd(b, core, dtype, (hipStream_t)stream);
+    b.stats = core >= 3 ? (float*)(w + 2 * ws.rows_x + 2 * ws.rows_h + ws.sub) : nullptr;
+    rc = core >= 3 ? modcr_launch_attn_long_bwd(b, core, dtype, (hipStream_t)stream) : modcr_launch_attn_bias_bwd(b, core, dtype, (hipStream_t)stream);
     if (rc != MODCR_OK) return rc;
     // 3. the chunk mean is its own adjoint
     if (chunk_id) {
@@ -2903,6 +2918,17 @@ extern "C" int modcr_qkv_attn_prefix_bwd(const void* dctx, const void* x, const 
 }
 
 // ---- modcr_qkv_attn_gate_bwd: the two entries above in one (P >= 0), with the gradient of head_mask ----
+// what the gate entry and modcr_qkv_attn_long_bwd check before the shared body: P >= 0, hist / d_hist exactly with prefix rows, no chunk mean
+// with them
+static int attn_gate_precheck(const char* who, const void* hist, const void* d_hist, const int32_t* chunk_id, int32_t P) {
+    MODCR_REQUIRE(P >= 0, "%s: bad shape (P=%d)", who, P);
+    MODCR_REQUIRE((hist != nullptr) == (P > 0) && (d_hist != nullptr) == (P > 0),
+                  "%s: hist and d_hist are given exactly with prefix rows (P=%d, hist %s, d_hist %s)", who, P, hist ? "given" : "null",
+                  d_hist ? "given" : "null");
+    MODCR_REQUIRE(!chunk_id || P == 0, "%s: no chunk-mean queries with prefix rows (P=%d)", who, P);
+    return MODCR_OK;
+}
+
 extern "C" int64_t modcr_qkv_attn_gate_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
     (void)dtype;
     return N <= 0 || S <= 0 || P < 0 || H <= 0 ? 0 : attn_bias_bwd_ws(N, S, P, H).bytes();
@@ -2920,12 +2946,38 @@ extern "C" int modcr_qkv_attn_gate_bwd(const void* dctx, const void* x, const vo
                                        uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
                                        modcr_stream_t stream) {
     const char* who = "qkv_attn_gate_bwd";
-    MODCR_REQUIRE(P >= 0, "%s: bad shape (P=%d)", who, P);
-    MODCR_REQUIRE((hist != nullptr) == (P > 0) && (d_hist != nullptr) == (P > 0),
-                  "%s: hist and d_hist are given exactly with prefix rows (P=%d, hist %s, d_hist %s)", who, P, hist ? "given" : "null",
-                  d_hist ? "given" : "null");
-    MODCR_REQUIRE(!chunk_id || P == 0, "%s: no chunk-mean queries with prefix rows (P=%d)", who, P);
+    const int rc = attn_gate_precheck(who, hist, d_hist, chunk_id, P);
+    if (rc != MODCR_OK) return rc;
     return attn_bias_bwd(who, dctx, x, hist, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask, head_mask_stride_n,
                          chunk_id, chunk_t, dx_residual, dx, d_hist, dwqkv, dbqkv, accumulate, d_bias, d_head_mask, N, S, P, H, A, attn_p, seed,
                          offset, workspace, workspace_bytes, dtype, stream);
+}
+
+// ---- modcr_qkv_attn_long_bwd: modcr_qkv_attn_gate_bwd with the key limit 512 (opt-in; the streaming cores above 256 keys) ----
+extern "C" int64_t modcr_qkv_attn_long_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
+    (void)dtype;
+    return N <= 0 || S <= 0 || P < 0 || H <= 0 || (int64_t)P + S > 512 ? 0 : attn_bias_bwd_ws(N, S, P, H, 512).bytes();
+}
+
+extern "C" int modcr_qkv_attn_long_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype) {
+    return attn_bias_bwd_core(N, S, P, H, A, dtype, 512);
+}
+
+extern "C" int modcr_qkv_attn_long_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                                       const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                                       const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
+                                       const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv, int32_t accumulate,
+                                       float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
+                                       uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                                       modcr_stream_t stream) {
+    if ((int64_t)P + S <= 256)
+        return modcr_qkv_attn_gate_bwd(dctx, x, hist, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask,
+                                       head_mask_stride_n, chunk_id, chunk_t, dx_residual, dx, d_hist, dwqkv, dbqkv, accumulate, d_bias, d_head_mask,
+                                       N, S, P, H, A, attn_p, seed, offset, workspace, workspace_bytes, dtype, stream);
+    const char* who = "qkv_attn_long_bwd";
+    const int rc = attn_gate_precheck(who, hist, d_hist, chunk_id, P);
+    if (rc != MODCR_OK) return rc;
+    return attn_bias_bwd(who, dctx, x, hist, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask, head_mask_stride_n,
+                         chunk_id, chunk_t, dx_residual, dx, d_hist, dwqkv, dbqkv, accumulate, d_bias, d_head_mask, N, S, P, H, A, attn_p, seed,
+                         offset, workspace, workspace_bytes, dtype, stream, 512);
 }

@@ -36,21 +36,6 @@ struct ABB {
     static constexpr int SMEM = IMG + 3 * LP * 4;           // + row max, 1 / row sum, delta
 };
 
-typedef __attribute__((address_space(3))) bf16x4* lds_tr_b;
-
-// Transposed fragment of a row image (as attn_bwd_mfma_kernel's): feature 16 db + l15, tokens tok0 + 4 l4 + {0..3} and
-// tok0 + 16 + 4 l4 + {0..3}
-__device__ __forceinline__ bf16x8 abb_tr8(const unsigned char* img, int tok0, int db, int l15, int l4) {
-    const int r = tok0 + 4 * l4 + (l15 >> 2);
-    const int ch = db * 2 + ((l15 & 3) >> 1), within = (l15 & 1) * 8;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_tr_b)(img + swz128(r, ch) + within));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_tr_b)(img + swz128(r + 16, ch) + within));
-    bf16x8 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o[e] = lo[e]; o[4 + e] = hi[e]; }
-    return o;
-}
-
 // PREFIX: prefix rows are given (else P = 0); BIAS: a bias is given (else the head mask alone); DBIAS: dS leaves as d_bias;
 // DHM: the gradient of the head's multiplier leaves as d_head_mask[n A + a].
 template <bool PREFIX, bool BIAS, bool DBIAS, bool DHM>

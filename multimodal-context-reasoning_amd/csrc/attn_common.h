@@ -89,6 +89,22 @@ __device__ __forceinline__ bf16x8 attn_drop8_rt(bf16x8 pb, uint32_t base, int kt
 __device__ __forceinline__ int swz128(int row, int chunk) { return (row << 7) + (((chunk ^ (row >> 1)) & 7) << 4); }
 __device__ __forceinline__ int swz64(int row, int chunk) { return (row << 6) + (((chunk ^ (row >> 2)) & 3) << 4); }
 
+typedef __attribute__((address_space(3))) bf16x4* lds_tr_b;
+
+// Transposed fragment of a swz128 row image (attn_bias_bwd.hip, attn_long_bwd.hip; as attn_bwd_mfma_kernel's): feature
+// 16 db + l15, tokens tok0 + 4 l4 + {0..3} and tok0 + 16 + 4 l4 + {0..3}.  The gather crosses lanes: call it with every lane of
+// the wave active.
+__device__ __forceinline__ bf16x8 abb_tr8(const unsigned char* img, int tok0, int db, int l15, int l4) {
+    const int r = tok0 + 4 * l4 + (l15 >> 2);
+    const int ch = db * 2 + ((l15 & 3) >> 1), within = (l15 & 1) * 8;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_tr_b)(img + swz128(r, ch) + within));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_tr_b)(img + swz128(r + 16, ch) + within));
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { o[e] = lo[e]; o[4 + e] = hi[e]; }
+    return o;
+}
+
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -145,9 +161,15 @@ struct AttnBiasBwdArgs {
     // fp32 [N, A] or NULL: the gradient of the head's multiplier, d_hm[n, a] = sum_i dctx_i . (P'.V)_i (the DHM instantiations; one
     // lane writes each element).  head_mask == NULL then stands for a mask of ones.  Last, so that every other field keeps its offset.
     float* d_head_mask;
+    // attn_long_bwd.hip only: the per-row statistics fp32 [N A][3][SP] (row max, 1 / row sum, D; SP = S rounded up to 64), 16-byte
+    // aligned, written by its query kernel and read by its key kernel.  The whole-row cores never look at it.
+    float* stats;
 };
 // core: 1 = attn_bias_bwd_mfma_kernel (bf16, P + S <= 192), 2 = attn_bias_bwd_f32_kernel (P + S <= 256); prefix rows where b.P > 0
 __attribute__((visibility("hidden"))) int modcr_launch_attn_bias_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype, hipStream_t stream);
+// attn_long_bwd.hip: the streaming cores for P + S <= 512 keys, no dropout; core: 3 = the bf16 MFMA kernels, 4 = the exact fp32 kernels
+// (fp32 dtype only: its dctx is fp32); b.stats given
+__attribute__((visibility("hidden"))) int modcr_launch_attn_long_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype, hipStream_t stream);
 
 // attn_long.hip: the streaming attention core (P + S <= 512) over q | k | v rows the dispatcher projected: qx [N*S][3H] (queries,
 // chunk-mean applied), qh [N*P][3H] (prefix rows) -- bf16 or fp32 as `dtype`.  Binary masks (key_mask / bits: above 256 keys, no

@@ -106,7 +106,11 @@ SIGNATURES = {
                                          _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
     "modcr_qkv_attn_gate_bwd_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "modcr_qkv_attn_gate_bwd_route": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_long_bwd_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_long_bwd_route": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "modcr_qkv_attn_gate_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
+                                       _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
+    "modcr_qkv_attn_long_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
                                        _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
     "modcr_linear_residual_ln_bwd_workspace": (_i64, [_i32, _i32, _i32]),
     "modcr_linear_residual_ln_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
@@ -1094,31 +1098,39 @@ def qkv_attn_gate_bwd_route(n, s, p, h, a, dtype=BF16):
     return ATTN_BIAS_BWD_CORES[lib().modcr_qkv_attn_gate_bwd_route(n, s, p, h, a, dtype)]
 
 
+def _attn_bias_bwd_operands(who, x, hist, attn_bias, head_mask, d_bias, d_head_mask, a, max_keys):
+    """the checks the bias / prefix / gate backward and qkv_attn_long_bwd share, before any tensor is touched:
+    -> (P, fp32 bias or None, its three element strides, [1 or N, A] head mask or None, its sequence stride)"""
+    n, s, h = x.shape
+    p = 0
+    if hist is not None:
+        if hist.dim() != 3 or hist.shape[0] != n or hist.shape[2] != h or hist.shape[1] < 1 or hist.dtype != x.dtype:
+            raise ValueError("%s: hist must be [N, P >= 1, H] in x's dtype, got %s %s" % (who, tuple(hist.shape), hist.dtype))
+        p = hist.shape[1]
+    l = p + s
+    if l > max_keys:
+        raise ValueError(("%s: P + S = %d keys exceeds the %d-key limit of the attention backward" if p else
+                          "%s: S = %d exceeds the %d-key limit of the attention backward") % (who, l, max_keys))
+    if attn_bias is None and head_mask is None and d_head_mask is None:
+        raise ValueError("%s: hist needs attn_bias, key_mask or head_mask" % who if p else "%s: d_bias without attn_bias" % who)
+    bias, strides = (None, (0, 0, 0)) if attn_bias is None else _bias_strides(attn_bias, n, a, s, l)
+    hm, hsn = (None, 0) if head_mask is None else _head_mask_2d(head_mask, n, a)
+    if d_bias is not None and (bias is None or d_bias.dtype != torch.float32 or tuple(d_bias.shape) != (n, a, s, l) or not d_bias.is_contiguous()):
+        raise ValueError("%s: d_bias must be a contiguous fp32 [N, A, S, %s] tensor, given together with attn_bias" % (who, "P + S" if p else "S"))
+    if d_head_mask is not None and (d_head_mask.dtype != torch.float32 or tuple(d_head_mask.shape) != (n, a) or not d_head_mask.is_contiguous() or
+                                    d_head_mask.device != x.device):
+        raise ValueError("%s: d_head_mask must be a contiguous fp32 [N, A] = [%d, %d] tensor on x's device, got %s %s" %
+                         (who, n, a, tuple(d_head_mask.shape), d_head_mask.dtype))
+    return p, bias, strides, hm, hsn
+
+
 def _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, a, accumulate, attn_dropout, dx_residual,
                        d_head_mask=None):
     """qkv_attn_bwd with attn_bias / head_mask: modcr_qkv_attn_bias_bwd -> dx, or with hist modcr_qkv_attn_prefix_bwd -> (dx, d_hist);
     with d_head_mask modcr_qkv_attn_gate_bwd for both"""
     dt = dt_of(x)
     n, s, h = x.shape
-    p = 0
-    if hist is not None:
-        if hist.dim() != 3 or hist.shape[0] != n or hist.shape[2] != h or hist.shape[1] < 1 or hist.dtype != x.dtype:
-            raise ValueError("qkv_attn_bwd: hist must be [N, P >= 1, H] in x's dtype, got %s %s" % (tuple(hist.shape), hist.dtype))
-        p = hist.shape[1]
-    l = p + s
-    if l > ATTN_BWD_MAX_KEYS:
-        raise ValueError(("qkv_attn_bwd: P + S = %d keys exceeds the %d-key limit of the attention backward" if p else
-                          "qkv_attn_bwd: S = %d exceeds the %d-key limit of the attention backward") % (l, ATTN_BWD_MAX_KEYS))
-    if attn_bias is None and head_mask is None and d_head_mask is None:
-        raise ValueError("qkv_attn_bwd: hist needs attn_bias, key_mask or head_mask" if p else "qkv_attn_bwd: d_bias without attn_bias")
-    bias, (bsn, bsa, bsq) = (None, (0, 0, 0)) if attn_bias is None else _bias_strides(attn_bias, n, a, s, l)
-    hm, hsn = (None, 0) if head_mask is None else _head_mask_2d(head_mask, n, a)
-    if d_bias is not None and (bias is None or d_bias.dtype != torch.float32 or tuple(d_bias.shape) != (n, a, s, l) or not d_bias.is_contiguous()):
-        raise ValueError("qkv_attn_bwd: d_bias must be a contiguous fp32 [N, A, S, %s] tensor, given together with attn_bias" % ("P + S" if p else "S"))
-    if d_head_mask is not None and (d_head_mask.dtype != torch.float32 or tuple(d_head_mask.shape) != (n, a) or not d_head_mask.is_contiguous() or
-                                    d_head_mask.device != x.device):
-        raise ValueError("qkv_attn_bwd: d_head_mask must be a contiguous fp32 [N, A] = [%d, %d] tensor on x's device, got %s %s" %
-                         (n, a, tuple(d_head_mask.shape), d_head_mask.dtype))
+    p, bias, (bsn, bsa, bsq), hm, hsn = _attn_bias_bwd_operands("qkv_attn_bwd", x, hist, attn_bias, head_mask, d_bias, d_head_mask, a, ATTN_BWD_MAX_KEYS)
     x, dctx = _contig(x), _contig(dctx)
     dx = torch.empty_like(x)
     res = _contig(dx_residual, torch.float32) if dx_residual is not None else None
@@ -1153,6 +1165,57 @@ def _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_
                                          n, s, h, a, float(ap), seed, off, _ptr(ws), need, dt, _stream()),
            "modcr_qkv_attn_bias_bwd")
     return dx
+
+
+ATTN_BWD_LONG_MAX_KEYS = 512
+ATTN_LONG_BWD_CORES = {0: "refused", 1: "mfma", 2: "exact", 3: "stream", 4: "stream-exact"}
+
+
+def qkv_attn_long_bwd_route(n, s, p, h, a, dtype=BF16):
+    """The core modcr_qkv_attn_long_bwd runs for this shape, p >= 0 prefix rows (nothing is launched): "mfma" / "exact" (P + S <= 256,
+    modcr_qkv_attn_gate_bwd's), "stream" / "stream-exact" (256 < P + S <= 512, csrc/attn_long_bwd.hip) or "refused"."""
+    return ATTN_LONG_BWD_CORES[lib().modcr_qkv_attn_long_bwd_route(n, s, p, h, a, dtype)]
+
+
+def qkv_attn_long_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, chunk_id=None, num_heads=None, accumulate=False, attn_dropout=None,
+                      dx_residual=None, attn_bias=None, head_mask=None, d_bias=None, hist=None, d_head_mask=None):
+    """qkv_attn_bwd's attn_bias / head_mask / hist route with the key limit 512 instead of 256 (modcr_qkv_attn_long_bwd): the backward
+    of a forward that ran qkv_attn(attn_bias=, head_mask=, hist=) at P + S <= 512 keys.  Returns dx, or (dx, d_hist) with hist.  At
+    P + S <= 256 the call is modcr_qkv_attn_gate_bwd's, bit for bit; above, the streaming cores run and attention dropout is refused.
+    A binary key_mask [N, L] is folded into a [N,1,1,L] 0 / -10000 bias (fold the forward the same way); chunk_id only without hist."""
+    if hist is not None and chunk_id is not None:
+        raise ValueError("qkv_attn_long_bwd: hist (prefix rows) does not combine with chunk_id")
+    if key_mask is not None:
+        if attn_bias is not None:
+            raise ValueError("qkv_attn_long_bwd: attn_bias replaces key_mask")
+        attn_bias = fold_key_mask(key_mask)
+    return _qkv_attn_long_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, num_heads, accumulate,
+                              attn_dropout, dx_residual, d_head_mask)
+
+
+def _qkv_attn_long_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, a, accumulate, attn_dropout, dx_residual,
+                       d_head_mask):
+    who = "qkv_attn_long_bwd"
+    dt = dt_of(x)
+    n, s, h = x.shape
+    p, bias, (bsn, bsa, bsq), hm, hsn = _attn_bias_bwd_operands(who, x, hist, attn_bias, head_mask, d_bias, d_head_mask, a, ATTN_BWD_LONG_MAX_KEYS)
+    ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
+    if p + s > ATTN_BWD_MAX_KEYS and ap > 0:
+        raise ValueError("%s: attention-probability dropout (p=%g) is not implemented above %d keys (P + S = %d)" % (who, ap, ATTN_BWD_MAX_KEYS, p + s))
+    x, dctx = _contig(x), _contig(dctx)
+    dx = torch.empty_like(x)
+    res = _contig(dx_residual, torch.float32) if dx_residual is not None else None
+    hist = _contig(hist) if p else None
+    d_hist = torch.empty_like(hist) if p else None
+    need = lib().modcr_qkv_attn_long_bwd_workspace(n, s, p, h, dt)
+    ws = _workspace("attn_bwd", need, x.device)
+    chunk_t = 0 if chunk_id is None else chunk_id.shape[1]
+    _check(lib().modcr_qkv_attn_long_bwd(_ptr(dctx), _ptr(x), _ptr(hist), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq,
+                                         _ptr(hm), hsn, _ptr(chunk_id), chunk_t, _ptr(res), _ptr(dx), _ptr(d_hist), _ptr(dwqkv), _ptr(dbqkv),
+                                         1 if accumulate else 0, _ptr(d_bias), _ptr(d_head_mask), n, s, p, h, a, float(ap), seed, off,
+                                         _ptr(ws), need, dt, _stream()),
+           "modcr_qkv_attn_long_bwd")
+    return (dx, d_hist) if p else dx
 
 
 def fold_key_mask(key_mask):

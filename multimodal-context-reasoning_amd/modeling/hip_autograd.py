@@ -21,6 +21,15 @@ def set_exact(flag):
     EXACT = bool(flag)
 
 
+LONG_BACKWARD = False      # True = trainable layers above 256 keys run the streaming attention backward (up to 512 keys, no
+                           # attention-probability dropout there); opt-in, set by the run scripts' --modcr_long_backward
+
+
+def set_long_backward(flag):
+    global LONG_BACKWARD
+    LONG_BACKWARD = bool(flag)
+
+
 def _w_for(x, w):
     """weights in the activation's storage dtype (bf16 copy for the MFMA path)"""
     return mh.convert(w, mh.BF16) if x.dtype == torch.bfloat16 else w
@@ -370,13 +379,29 @@ def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, par
     wants_grad = _caller_grad_mode()[-1] and (x.requires_grad or any(isinstance(p_, torch.Tensor) and p_.requires_grad for p_ in params) or
                                               (attn_bias is not None and attn_bias.requires_grad) or (hist is not None and hist.requires_grad) or
                                               need_hm)
+    align = packed.get("_align") if isinstance(packed, dict) else None       # (map buffer, T, gradient holder) of AlignMapFn
+    long_bwd = False
     if s > mh.ATTN_TILE_KEYS and wants_grad:
         # the attention forward serves up to 512 keys, its backward (modcr_qkv_attn_bwd) 256: refuse before any launch
-        raise NotImplementedError("a trainable layer at %s = %d exceeds the %d keys the attention backward takes; run it under "
-                                  "torch.no_grad() (eval) up to %d keys" % ("S" if hist is None else "S + P", s, mh.ATTN_TILE_KEYS, mh.ATTN_MAX_KEYS))
+        if not LONG_BACKWARD:
+            raise NotImplementedError("a trainable layer at %s = %d exceeds the %d keys the attention backward takes; run it under "
+                                      "torch.no_grad() (eval) up to %d keys" % ("S" if hist is None else "S + P", s, mh.ATTN_TILE_KEYS, mh.ATTN_MAX_KEYS))
+        # set_long_backward(True): the streaming backward (modcr_qkv_attn_long_bwd) up to 512 keys, without what it does not carry
+        what = "S" if hist is None else "S + P"
+        if s > mh.ATTN_BWD_LONG_MAX_KEYS:
+            raise NotImplementedError("a trainable layer at %s = %d exceeds the %d keys the streaming attention backward takes" %
+                                      (what, s, mh.ATTN_BWD_LONG_MAX_KEYS))
+        if attn_p > 0.0:
+            raise NotImplementedError("attention-probability dropout (p=%g) in a trainable layer needs %s <= %d (%s = %d): set "
+                                      "attention_probs_dropout_prob = 0 to train above %d keys" %
+                                      (attn_p, what, mh.ATTN_TILE_KEYS, what, s, mh.ATTN_TILE_KEYS))
+        if mask_bits is not None or align is not None:
+            raise NotImplementedError("the streaming attention backward (%s = %d > %d keys) takes no %s: the dense phase masks and the "
+                                      "align-map gradient stay at %d keys" %
+                                      (what, s, mh.ATTN_TILE_KEYS, "mask_bits" if mask_bits is not None else "align map", mh.ATTN_TILE_KEYS))
+        long_bwd = True
     if not head_mask_grad and head_mask is not None and head_mask.requires_grad and _caller_grad_mode()[-1]:
         raise NotImplementedError("head_mask is a constant of the trainable layer (head pruning): no gradient is formed for it; detach() it")
-    align = packed.get("_align") if isinstance(packed, dict) else None       # (map buffer, T, gradient holder) of AlignMapFn
     amap, at = (align[0], align[1]) if align is not None else (None, 0)
     y, saved = hip_layers.layer_forward_train(packed, x.detach(), num_heads, eps, key_mask=key_mask,
                                               mask_bits=mask_bits, chunk_id=chunk_id, p=p, attn_p=attn_p,
@@ -384,7 +409,7 @@ def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, par
                                               side_post_dropout=bool(packed.get("_side_post", True)) if isinstance(packed, dict) else True,
                                               attn_bias=None if attn_bias is None else attn_bias.detach(),
                                               head_mask=None if head_mask is None else head_mask.detach(),
-                                              hist=None if hist is None else hist.detach())
+                                              hist=None if hist is None else hist.detach(), long_backward=long_bwd)
     ctx.saved, ctx.packed = saved, packed
     ctx.holder = align[2] if align is not None else None
     ctx.params = params                  # (the Parameter objects: the gradient sink writes into their .grad views)
@@ -472,7 +497,8 @@ class BertLayerPrefixFn(_NotedFn):
     """BertLayerBiasFn with a history state (the reference's encoder_history_states[i], modeling_bert.py:36-44): hist [N,P,H] in the
     storage dtype is prepended for K and V only and is a DIFFERENTIABLE input (prefix tuning), as are x, attn_bias (any float tensor
     broadcastable to [N, A, S, P + S]) and the 16 parameters; head_mask is a constant.  attn_bias or head_mask may be None, not both.
-    S + P <= 256 under grad mode (modcr_qkv_attn_prefix_bwd).  Ten arguments before the parameters; same gradient-sink protocol."""
+    S + P <= 256 under grad mode (modcr_qkv_attn_prefix_bwd); up to 512 without attention dropout after set_long_backward(True)
+    (modcr_qkv_attn_long_bwd).  Ten arguments before the parameters; same gradient-sink protocol."""
 
     @staticmethod
     def forward(ctx, x, hist, attn_bias, head_mask, chunk_id, num_heads, eps, p, attn_p, packed, *params):
@@ -501,7 +527,8 @@ class BertLayerGateFn(_NotedFn):
     """BertLayerPrefixFn's argument order with head_mask ([A], [N, A], anything broadcastable to [N, A, 1, 1]) as a DIFFERENTIABLE
     input too (head importance, learned head gates): its gradient is the [N, A] sum_i dctx_i . (P'.V)_i of modcr_qkv_attn_gate_bwd
     summed to the mask's own shape and cast to its dtype.  hist and attn_bias may be None, head_mask may not; chunk_id only without
-    hist.  S + P <= 256 under grad mode.  Ten arguments before the parameters; same gradient-sink protocol."""
+    hist.  S + P <= 256 under grad mode (up to 512 without attention dropout after set_long_backward(True)).  Ten arguments before the
+    parameters; same gradient-sink protocol."""
 
     @staticmethod
     def forward(ctx, x, hist, attn_bias, head_mask, chunk_id, num_heads, eps, p, attn_p, packed, *params):

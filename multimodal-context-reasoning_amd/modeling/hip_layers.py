@@ -183,7 +183,7 @@ def attn_dropout_supported(x, num_heads):
 
 
 def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None, chunk_id=None, p=0.0, attn_p=0.0,
-                        align_map=None, align_t=0, side_post_dropout=True, attn_bias=None, head_mask=None, hist=None):
+                        align_map=None, align_t=0, side_post_dropout=True, attn_bias=None, head_mask=None, hist=None, long_backward=False):
     """p: hidden_dropout_prob of BertSelfOutput / BertOutput in training mode (a_bert:369-373, :446-451);
     attn_p: attention_probs_dropout_prob (modeling_bert.py:69), applied inside the attention kernels;
     align_map [N,T,R] fp32 (+= head-summed text->region probabilities of this layer, v10:982), align_t = T;
@@ -194,9 +194,26 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
     no lse / dump is written); no align map on this route.
     hist [N,P,H] (storage dtype): the layer's history state, prepended for K and V only (modeling_bert.py:36-44), P + S <= 256 for
     the backward (modcr_qkv_attn_prefix_bwd).  attn_bias is then [.., P + S]; a binary key_mask [N, P + S] is folded into a
-    0 / -10000 bias, so that forward and backward run one arithmetic.  No mask bits, chunk-mean queries or align map with it."""
+    0 / -10000 bias, so that forward and backward run one arithmetic.  No mask bits, chunk-mean queries or align map with it.
+    long_backward: above 256 keys (256 < P + S <= 512) the forward takes the biased route -- a binary key_mask is folded into a
+    0 / -10000 bias, with or without hist, chunk_id allowed without hist; no lse / dump -- and layer_backward runs the streaming
+    attention backward (mh.qkv_attn_long_bwd).  No attention dropout, mask bits or align map there.  At P + S <= 256 it changes
+    nothing."""
     n, s, h = x.shape
     pl = 0 if hist is None else hist.shape[1]
+    long_backward = bool(long_backward) and pl + s > mh.ATTN_BWD_MAX_KEYS
+    if long_backward:
+        if attn_p > 0.0:
+            raise NotImplementedError("attention-probability dropout in a trainable layer needs P + S <= 256 (S=%d, P=%d): set "
+                                      "attention_probs_dropout_prob = 0 to train above 256 keys" % (s, pl))
+        if mask_bits is not None or align_map is not None:
+            raise NotImplementedError("layer_forward_train: no mask_bits and no align map above 256 keys (long_backward)")
+        if key_mask is not None:
+            if attn_bias is not None:
+                raise ValueError("layer_forward_train: attn_bias replaces key_mask")
+            attn_bias, key_mask = mh.fold_key_mask(key_mask), None
+        if attn_bias is None and head_mask is None:      # no mask at all: the biased route under a zero bias
+            attn_bias = torch.zeros((1, 1, 1, pl + s), dtype=torch.float32, device=x.device)
     if hist is not None:
         if mask_bits is not None or chunk_id is not None or align_map is not None:
             raise ValueError("layer_forward_train: hist (history state) takes no mask_bits, chunk_id or align map")
@@ -246,7 +263,7 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
     saved = dict(x=x, ctx=ctx, pre1=pre1, a=a, inter=inter, u=u, pre2=pre2, num_heads=num_heads, eps=eps,
                  key_mask=key_mask, mask_bits=mask_bits, chunk_id=chunk_id, drop1=drop1, drop2=drop2, adrop=adrop,
                  align_t=align_t if align_map is not None else 0, lse=lse, dump=dump, side_post=post,
-                 attn_bias=attn_bias, head_mask=head_mask, hist=hist)
+                 attn_bias=attn_bias, head_mask=head_mask, hist=hist, long_backward=long_backward)
     return y.view(n, s, h), saved
 
 
@@ -337,10 +354,12 @@ def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None, want_d_
         if want_d_head_mask and saved.get("head_mask") is None:
             raise ValueError("layer_backward: want_d_head_mask for a layer that ran without head_mask")
         d_hm = torch.empty((n, saved["num_heads"]), dtype=f32, device=dev) if want_d_head_mask else None
-        dx = mh.qkv_attn_bwd(d_ctx.view(n, s, h), x, layer["wqkv"], layer["bqkv"], dwqkv, dbqkv, chunk_id=saved["chunk_id"],
-                             num_heads=saved["num_heads"], attn_dropout=saved.get("adrop"), dx_residual=d_pre1.view(n, s, h),
-                             attn_bias=saved.get("attn_bias"), head_mask=saved.get("head_mask"), d_bias=d_bias, hist=hist,
-                             d_head_mask=d_hm)
+        # (a layer that ran with long_backward above 256 keys: the streaming backward, modcr_qkv_attn_long_bwd)
+        attn_bwd = mh.qkv_attn_long_bwd if saved.get("long_backward") else mh.qkv_attn_bwd
+        dx = attn_bwd(d_ctx.view(n, s, h), x, layer["wqkv"], layer["bqkv"], dwqkv, dbqkv, chunk_id=saved["chunk_id"],
+                      num_heads=saved["num_heads"], attn_dropout=saved.get("adrop"), dx_residual=d_pre1.view(n, s, h),
+                      attn_bias=saved.get("attn_bias"), head_mask=saved.get("head_mask"), d_bias=d_bias, hist=hist,
+                      d_head_mask=d_hm)
         if hist is not None:
             dx, g["history_state"] = dx
         if want_d_bias:

@@ -256,6 +256,10 @@ def get_args(argv=None):
     p.add_argument("--modcr_backward_memory", default="keep", choices=["keep", "recompute", "auto"],
                    help="(this build) what trainable layers keep for their backward: keep = Q|K|V images + bf16 GELU input per layer (fastest, "
                         "~1 GB per layer at 128 examples); recompute = neither (the attention / FFN backward recompute them); auto = by free memory")
+    p.add_argument("--modcr_long_backward", action="store_true",
+                   help="(this build) train batches padded past 256 keys: trainable layers at 256 < S + P <= 512 keys run the streaming "
+                        "attention backward (no attention-probability dropout there: set --attention_probs_dropout_prob 0); default off = "
+                        "such a batch is refused under grad mode")
     p.add_argument("--roberta_body", default="standin", choices=["standin", "large"],
                    help="large = the 24-layer prefix RoBERTa-large on the HIP kernels, trainable (run_PMR_ModCR.py:772-781; "
                         "random init: local_transformers/roberta-large is not in the reference tree)")
@@ -366,6 +370,9 @@ def main(argv=None):
                                                   groups=groups)
     if args.modcr_backward_memory != "keep":
         logger.info("modcr_backward_memory=%s -> %s", args.modcr_backward_memory, chosen)
+    if args.modcr_long_backward:
+        from modeling import hip_autograd
+        hip_autograd.set_long_backward(True)
     mh.DROPOUT.manual_seed(args.seed + 7919 * getattr(args, "rank", 0))   # different masks per rank (different data anyway)
     if args.do_test or (args.do_eval and not args.do_train):
         if os.path.isfile(args.eval_model_dir):

@@ -37,6 +37,9 @@ def freeze_roberta_body(model):
     return frozen
 
 
+get_args = pmr.get_args        # one parser for both entry points: every "(this build)" switch, --modcr_long_backward among them
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     defaults = ["--per_gpu_train_batch_size", "8", "--gradient_accumulation_steps", "4", "--valid_steps", "3500",

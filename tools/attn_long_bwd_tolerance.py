@@ -1,0 +1,118 @@
+"""How much of the bf16 bounds of tests/test_hip_attn_long_bwd.py the number formats alone use (CPU, no GPU needed).
+
+The attention backward from 257 to 512 keys is restated in float64 with every quantity the bf16 route holds in bf16 rounded to bf16
+where the streaming MFMA core of csrc/attn_long_bwd.hip (and, for ctx, the streaming forward of csrc/attn_long.hip) rounds it: the
+recomputed q | k | v rows, the probabilities that enter the context and dV products, the dS tile that enters the dQ and dK products,
+the dq | dk | dv rows, and ctx, dx, d_hist as they leave.  Above 256 keys the q rows are NOT scaled and rounded a second time (the
+accumulator takes log2e / 8), so that rounding of the cores below 257 keys is absent here.  The row statistics (max, 1 / sum, D) and
+d_head_mask stay fp32 on the device and are not rounded.  Inputs are those of the tests' soft-bias case: the seven shapes, the three
+bias forms, head mask (1, 0.5), no dropout.  Each line is the share of a bound this restatement uses against the float64 reference;
+if one exceeded half a bound, the INPUT would have to change, not the bound.
+
+    python tools/attn_long_bwd_tolerance.py [--out profiles/attn_long_bwd_tolerance_report.txt]
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p_ in (ROOT, os.path.join(ROOT, "multimodal-context-reasoning_amd"), os.path.join(ROOT, "tests")):
+    if p_ not in sys.path:
+        sys.path.insert(0, p_)
+
+import test_hip_attn_long_bwd as T  # noqa: E402
+import test_hip_attn_prefix_bwd as PF  # noqa: E402
+
+
+def r16(t):
+    return t.float().to(torch.bfloat16).double()
+
+
+def rounded_restatement(shape, bias, hm):
+    """(ctx, dx, d_hist or None, dWqkv, dbqkv, dS, d_hm) of the bf16 route's arithmetic in float64 with its roundings"""
+    n, s, p, h, a = shape
+    c = T.case(shape)
+    w, b, x = (t.double() for t in c[:3])
+    hist = c[3].double() if p else torch.zeros(n, 0, h, dtype=torch.float64)
+    dctx = c[-1].double()
+    F = torch.nn.functional
+    qkv = r16(F.linear(x, w, b))                                            # own rows q | k | v
+    kvh = r16(F.linear(hist, w[h:], b[h:]))                                 # prefix rows k | v
+    sp = lambda t: t.reshape(n, t.shape[1], a, 64).transpose(1, 2)
+    q = sp(qkv[..., :h])
+    k = sp(torch.cat([kvh[..., :h], qkv[..., h:2 * h]], 1))
+    v = sp(torch.cat([kvh[..., h:], qkv[..., 2 * h:]], 1))
+    do = sp(dctx)
+    P = torch.softmax(q @ k.transpose(-1, -2) / 8.0 + bias.double(), -1)
+    hmv = hm.double().reshape(n, a, 1, 1)
+    back = lambda t: t.transpose(1, 2).reshape(n, t.shape[2], h)
+    ctx = r16(back(r16(P) @ v * hmv))
+    dp = do @ v.transpose(-1, -2)
+    dl = (r16(P) @ v * do).sum(-1, keepdim=True)                            # D = dctx . (P.V), P as the context product takes it
+    ds = P * (dp - dl)
+    dq = r16(back(r16(ds) @ k * hmv * 0.125))
+    dk = r16(back(r16(ds).transpose(-1, -2) @ q * hmv * 0.125))
+    dv = r16(back(r16(P).transpose(-1, -2) @ do * hmv))
+    dqkv = torch.cat([dq, dk[:, p:], dv[:, p:]], -1)                         # [N, S, 3H]
+    dkvh = torch.cat([dk[:, :p], dv[:, :p]], -1)                             # [N, P, 2H]
+    dx = r16(dqkv @ w)
+    dh = r16(dkvh @ w[h:]) if p else None
+    dw = dqkv.reshape(-1, 3 * h).t() @ x.reshape(-1, h)
+    dw[h:] += dkvh.reshape(-1, 2 * h).t() @ hist.reshape(-1, h)
+    db = dqkv.reshape(-1, 3 * h).sum(0)
+    db[h:] += dkvh.reshape(-1, 2 * h).sum(0)
+    return ctx, dx, dh, dw, db, ds * hmv, dl.sum((-1, -2))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attn_long_bwd_tolerance_report.txt"))
+    args = ap.parse_args()
+    lines = ["bf16-rounded restatement of the attention backward from 257 to 512 keys against float64 (CPU): share of each bound of",
+             "tests/test_hip_attn_long_bwd.py used by the number formats alone.  Soft-bias case: head mask (1, 0.5), no dropout.",
+             "max|err| / max(1, max|ref|) against 2e-2; relative L2 against 2e-2; key-bias slice against 2e-2 x scale x sqrt(N S) / 4.", ""]
+    worst = {}
+    names = ("ctx", "dx", "d_hist", "dwqkv", "dbqkv", "d_bias", "d_head_mask")
+    for shape in T.SHAPES:
+        n, s, p, h, a = shape
+        for form in T.FORMS:
+            bias = PF.bias_of(form, n, s, p, a, s + p)
+            ref = T.soft_reference(shape, form)
+            got = rounded_restatement(shape, bias, T.head_mask(n, a))
+            row = []
+            for nm, g, r in zip(names, got, ref):
+                if r is None:
+                    continue
+                g, r = g.clone(), r.clone()
+                if nm == "dbqkv":
+                    g[h:2 * h] = 0
+                    r[h:2 * h] = 0
+                use = float((g - r).abs().max()) / max(1.0, float(r.abs().max())) / 2e-2
+                row.append("%s %4.1f %%" % (nm, 100 * use))
+                worst[nm] = max(worst.get(nm, (0.0, None)), (use, (shape, form)))
+                if nm in ("dx", "d_hist", "dwqkv"):
+                    rel = float((g - r).norm() / r.norm()) / 2e-2
+                    row.append("%s L2 %4.1f %%" % (nm, 100 * rel))
+                    worst[nm + " rel L2"] = max(worst.get(nm + " rel L2", (0.0, None)), (rel, (shape, form)))
+            kb = float(got[4][h:2 * h].abs().max()) / (2e-2 * max(1.0, float(ref[4].abs().max())) * (n * s) ** 0.5 * 0.25)
+            row.append("key-bias %4.1f %%" % (100 * kb))
+            worst["key-bias slice"] = max(worst.get("key-bias slice", (0.0, None)), (kb, (shape, form)))
+            lines.append("%-24s %-10s %s" % (shape, form, "  ".join(row)))
+    lines.append("")
+    lines.append("worst use of each bound:")
+    for nm, (use, where) in worst.items():
+        err = use * 2e-2
+        lines.append("  %-16s %5.1f %%  (%.2e against 2e-2%s)  at %s %s" % (nm, 100 * use, err, "" if nm != "key-bias slice" else " x its scale", where[0], where[1]))
+    top = max(u for u, _ in worst.values())
+    lines.append("")
+    lines.append("largest share: %.1f %% -- %s" % (100 * top, "below half of every bound: inputs and bounds stand" if top < 0.5 else "ABOVE HALF A BOUND: change the input"))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    with open(args.out, "w") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()
