@@ -79,17 +79,6 @@ struct AttnArgs {
     const int32_t* row_start = nullptr;
 };
 
-// attention-probability dropout as the host hands it to a kernel: the 64-bit key of (seed, offset), thr16 = round(p * 2^16) (0 = off)
-// and 1 / (1 - p); thr2 = the packed threshold of the bf16 tile kernels
-struct AttnDrop {
-    uint64_t key; uint32_t thr16; float keep;
-    uint32_t thr2() const { return thr16 ? attn_thrm1_2(thr16) : 0; }
-};
-inline AttnDrop attn_drop(float attn_p, uint64_t seed, uint64_t offset) {
-    if (!(attn_p > 0.f)) return {0, 0, 1.f};
-    return {seed + offset * 0x9E3779B97F4A7C15ull, attn_thr16(attn_p), 1.0f / (1.0f - attn_p)};
-}
-
 constexpr int VT_PAD = 8;  // bytes of padding per V^T row: stride/4 = 2*odd -> conflict-free b64 reads
 
 // HPW = heads per workgroup.  A 6-wave workgroup (S <= 192) lands 2,2,1,1 on the four SIMDs and a
@@ -1718,483 +1707,6 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(AttnF32Args p) {
     }
 }
 
-
-
-// ---- attention core backward on the matrix pipe (bf16 path, S <= 192): one workgroup of 6 waves per (n, head) -------
-// Same inputs / outputs as attn_bwd_f32_kernel below (recomputed fp32 q|k|v rows, dctx -> fp32 dq|dk|dv rows).
-// Wave w owns tokens 32 w .. 32 w + 31 twice:
-//   sub-pass Q (its QUERIES; K rows, V rows and K^T in LDS): S^T = K.Qs^T for all 192 keys stays in registers
-//     (Qs = Q log2e / 8, mask = accumulator init) -> exact row max / sum -> P^T; delta = rowsum(P o dP) with
-//     dP^T = V.dO^T; then dS^T = P^T o (dP^T - delta), whose bf16 pairs are the B operand of dQ^T += K^T.dS^T
-//     (accumulator as operand, keys permuted identically on the K^T fragment reads).  Row statistics go to LDS.
-//   sub-pass K (its KEYS; Qs rows, dO rows, Qs^T, dO^T in LDS): per 32-query tile S = Qs.K^T and dP = dO.V^T with
-//     the query in the registers, P and dS rebuilt from the row statistics, dV^T += dO^T.P, dK^T += Qs^T.dS.
-// Padding: dO rows beyond S are zero (their P, dS contribute nothing), keys beyond S carry a -inf mask.
-struct AB {
-    static constexpr int LP = 192, NT = 384;
-    static constexpr int ROWS = LP * 128;                   // [token][64] bf16, 128-byte rows, swz128
-    // The transposed operands (K^T; Qs^T, dO^T) are NOT kept as images: ds_read_b64_tr_b16 reads them out of the row images
-    // (a lane receives four consecutive tokens of one feature = half an MFMA operand).  Round 1 built [d][token] copies with
-    // eight 2-byte LDS stores per 16-byte piece and needed 108 KB per workgroup (one workgroup of six waves per CU);
-    // 57 KB now, two workgroups per CU.
-    static constexpr int IMG = 2 * ROWS;                    // sub-pass Q: K | V    sub-pass K: Qs | dO
-    static constexpr int SMEM = IMG + 4 * LP * 4 + LP * 6 * 4;
-};
-
-// DALIGN: the align map's gradient rides in (seq_enc layers 9-11 of the trainable-encoder variant only).  A template parameter:
-// as a run-time branch its per-block address arithmetic was hoisted to the top of the kernel and spilled (85 scratch stores
-// before the first MFMA) in every call.
-template <typename TD, bool DALIGN>
-__global__ __launch_bounds__(384, 3) void attn_bwd_mfma_kernel(AttnBwdArgs p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int LP = AB::LP;
-    unsigned char* img0 = smem;                             // rows image 0 (K | Qs)
-    unsigned char* img1 = smem + AB::ROWS;                  // rows image 1 (V | dO)
-    float* sM = reinterpret_cast<float*>(smem + AB::IMG);
-    float* sInv = sM + LP;
-    float* sDl = sInv + LP;
-    float* sMask = sDl + LP;
-    uint32_t* sBits = reinterpret_cast<uint32_t*>(sMask + LP);
-    const int S = p.S, H = p.H;
-    const int n = blockIdx.x / p.A, a = blockIdx.x % p.A;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l15_ = lane & 15, l4_ = lane >> 4;
-    const int LW = (S + 31) >> 5;
-    const bf16* qkv = p.qkvb + (int64_t)n * S * 3 * H + a * 64;
-    const TD* dctx = reinterpret_cast<const TD*>(p.dctx) + (int64_t)n * S * H + a * 64;
-    float* dqkv = p.dqkv + (int64_t)n * S * 3 * H + a * 64;
-    constexpr float QS = 0.125f * LOG2E;
-
-    // 8 consecutive features of token t (zeros beyond S) from the bf16 q|k|v rows (k, v: as they are -- the values the forward's
-    // images held; q: scaled by log2e / 8 and rounded again) or from dctx
-    auto row8 = [&](int t, int part, int c, float scale) {
-        bf16x8 o;
-        if (t < S) {
-            o = *reinterpret_cast<const bf16x8*>(qkv + (int64_t)t * 3 * H + part * H + c * 8);
-            if (scale != 1.0f) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (bf16)((float)o[e] * scale);
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (bf16)0.f;
-        }
-        return o;
-    };
-    auto do8 = [&](int t, int c) {
-        bf16x8 o;
-        if (t < S) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (bf16)to_f32(dctx[(int64_t)t * H + c * 8 + e]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (bf16)0.f;
-        }
-        return o;
-    };
-    auto put_rows = [&](unsigned char* img, int t, int c, const bf16x8& v) { *reinterpret_cast<bf16x8*>(img + swz128(t, c)) = v; };
-    // Transposed fragment of a row image: feature 16 db + l15, tokens tok0 + 4 l4 + {0..3} and tok0 + 16 + 4 l4 + {0..3} (the key
-    // order of the accumulator-as-operand products).  Within a 16-lane group lane i addresses token row (i >> 2), 8-byte piece
-    // (i & 3) of the 16-feature span and receives feature i (tools: transpose64_kernel, the TN GEMM); swz128 is applied per lane.
-    typedef __attribute__((address_space(3))) bf16x4* lds_tr;
-    auto tr8 = [&](const unsigned char* img, int tok0, int db, int l15, int l4) {
-        const int r = tok0 + 4 * l4 + (l15 >> 2);
-        const int ch = db * 2 + ((l15 & 3) >> 1), within = (l15 & 1) * 8;
-        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_tr)(img + swz128(r, ch) + within));
-        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_tr)(img + swz128(r + 16, ch) + within));
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { o[e] = lo[e]; o[4 + e] = hi[e]; }
-        return o;
-    };
-
-    // ---- tables and the images of sub-pass Q ---------------------------------------------------------------
-    for (int j = tid; j < LP; j += AB::NT) {
-        float m;
-        if (j >= S) m = -INFINITY;
-        else if (p.bits) m = 0.f;
-        else m = (1.0f - p.key_mask[(int64_t)n * S + j]) * (MODCR_NEG * LOG2E);
-        sMask[j] = m;
-    }
-    if (p.bits)
-        for (int j = tid; j < LP * 6; j += AB::NT) {
-            const int q = j / 6, w = j % 6;
-            sBits[j] = (q < S && w < LW) ? p.bits[((int64_t)n * S + q) * LW + w] : 0xffffffffu;
-        }
-    for (int it = tid; it < LP * 8; it += AB::NT) {
-        const int t = it >> 3, c = it & 7;
-        put_rows(img0, t, c, row8(t, 1, c, 1.0f));
-        put_rows(img1, t, c, row8(t, 2, c, 1.0f));
-    }
-    __syncthreads();
-
-    const int t0 = wave * 32;                               // this wave's tokens
-    if (MODCR_DBG(p.debug & 1)) return;
-    // ---- sub-pass Q ------------------------------------------------------------------------------------------
-    // One 16-query block at a time (its 16 x 192 scores = 48 registers): with both blocks of the wave's 32 queries unrolled
-    // side by side the kernel took 256 registers + 42 spilled, one workgroup per CU; the K / V / K^T fragments are read twice.
-    if (!MODCR_DBG(p.debug & 2)) {
-#pragma unroll 1
-        for (int qb = 0; qb < 2; ++qb) {
-            // per-iteration opaque copies of the lane indices: the fragment addresses below are loop invariant, and hoisted out
-            // of this loop their ~100 registers were spilled ahead of the first MFMA
-            int l15 = l15_, l4 = l4_;
-            asm volatile("" : "+v"(l15), "+v"(l4));
-            const int qrow = t0 + qb * 16 + l15;
-            bf16x8 fq[2], fdo[2];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                fq[ks] = row8(qrow, 0, ks * 4 + l4, QS);            // zeros beyond S, as the Qs image of sub-pass K (same row statistics)
-                fdo[ks] = do8(qrow, ks * 4 + l4);
-            }
-            f32x4 sc[6][2];
-#pragma unroll
-            for (int kt = 0; kt < 6; ++kt)
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb) {
-                    const int krow = kt * 32 + kb * 16;
-                    const bf16x8 fk0 = *reinterpret_cast<const bf16x8*>(img0 + swz128(krow + l15, l4));
-                    const bf16x8 fk1 = *reinterpret_cast<const bf16x8*>(img0 + swz128(krow + l15, 4 + l4));
-                    f32x4 c = *reinterpret_cast<const f32x4*>(sMask + krow + 4 * l4);
-                    if (p.bits) {
-                        const uint32_t word = sBits[qrow * 6 + kt];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (!((word >> (kb * 16 + 4 * l4 + e)) & 1u)) c[e] += MODCR_NEG * LOG2E;
-                    }
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk0, fq[0], c, 0, 0, 0);
-                    sc[kt][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk1, fq[1], c, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);      // no hoisting of the next blocks' fragment reads: registers
-                }
-            {
-                float m = -INFINITY;
-#pragma unroll
-                for (int kt = 0; kt < 6; ++kt)
-#pragma unroll
-                    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) m = fmaxf(m, sc[kt][kb][e]);
-                m = fmaxf(m, __shfl_xor(m, 16, 64));
-                m = fmaxf(m, __shfl_xor(m, 32, 64));
-                float l = 0.f;
-#pragma unroll
-                for (int kt = 0; kt < 6; ++kt)
-#pragma unroll
-                    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { const float ex = __builtin_amdgcn_exp2f(sc[kt][kb][e] - m); sc[kt][kb][e] = ex; l += ex; }
-                l += __shfl_xor(l, 16, 64);
-                l += __shfl_xor(l, 32, 64);
-                const float inv = 1.0f / l;
-#pragma unroll
-                for (int kt = 0; kt < 6; ++kt)
-#pragma unroll
-                    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) sc[kt][kb][e] *= inv;
-                if (l4 == 0) { sM[qrow] = m; sInv[qrow] = inv; }
-            }
-            // forward dropout on the probabilities: O = (P o m) V with m = keep / (1 - p), so dP = m o (dO V^T) below
-            const uint32_t dthr = p.drop_thr16;
-            const uint32_t dbase = attn_drop_base((uint32_t)((n * p.A + a) * 256 + qrow), (uint32_t)l4, p.drop_key);
-            auto dp_masked = [&](int kt, int kb) {
-                const int krow = kt * 32 + kb * 16;
-                const bf16x8 fv0 = *reinterpret_cast<const bf16x8*>(img1 + swz128(krow + l15, l4));
-                const bf16x8 fv1 = *reinterpret_cast<const bf16x8*>(img1 + swz128(krow + l15, 4 + l4));
-                f32x4 dp = {0.f, 0.f, 0.f, 0.f};
-                dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv0, fdo[0], dp, 0, 0, 0);
-                dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv1, fdo[1], dp, 0, 0, 0);
-                float mk4[4] = {1.f, 1.f, 1.f, 1.f};
-                if (dthr) {
-                    uint32_t hx, hy;
-                    hx = attn_drop_word(dbase, (2 * kt + kb) * 2, p.drop_key);
-                    hy = attn_drop_word(dbase, (2 * kt + kb) * 2 + 1, p.drop_key);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { mk4[e] = attn_keep_field(hx, hy, e, dthr) ? p.drop_keep : 0.f; dp[e] *= mk4[e]; }
-                }
-                if constexpr (DALIGN) {         // the align map's gradient, text query x region key: on the un-dropped probabilities,
-                                                // or (side_post_drop: the map summed P o m / (1 - p)) under the same mask
-                    const int T = p.align_t, key0 = kt * 32 + kb * 16 + 4 * l4;
-                    if (qrow < T && key0 + 3 >= T) {
-                        const float* da = p.d_align + ((int64_t)n * T + qrow) * (S - T) - T;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (key0 + e >= T && key0 + e < S) dp[e] += p.side_post_drop ? mk4[e] * da[key0 + e] : da[key0 + e];
-                    }
-                }
-                return dp;
-            };
-            float dl = 0.f;
-#pragma unroll
-            for (int kt = 0; kt < 6; ++kt)
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb) {
-                    const f32x4 dp = dp_masked(kt, kb);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) dl += sc[kt][kb][e] * dp[e];
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            dl += __shfl_xor(dl, 16, 64);
-            dl += __shfl_xor(dl, 32, 64);
-            if (l4 == 0) sDl[qrow] = dl;
-            f32x4 dq[4];
-#pragma unroll
-            for (int db = 0; db < 4; ++db) dq[db] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kt = 0; kt < 6; ++kt) {
-                bf16x8 dsb;
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb) {
-                    const f32x4 dp = dp_masked(kt, kb);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) dsb[4 * kb + e] = (bf16)(sc[kt][kb][e] * (dp[e] - dl));
-                }
-#pragma unroll
-                for (int db = 0; db < 4; ++db)
-                    dq[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr8(img0, kt * 32, db, l15, l4), dsb, dq[db], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (qrow < S)
-#pragma unroll
-                for (int db = 0; db < 4; ++db) {
-                    f32x4 o = dq[db];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] *= 0.125f;
-                    const int64_t at = (int64_t)qrow * 3 * H + db * 16 + 4 * l4;
-                    if (p.out_bf16) *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(p.dqkv) + (int64_t)n * S * 3 * H + a * 64 + at) = bf16x4{(bf16)o[0], (bf16)o[1], (bf16)o[2], (bf16)o[3]};
-                    else *reinterpret_cast<f32x4*>(dqkv + at) = o;
-                }
-        }
-    }
-    __syncthreads();
-    // ---- images of sub-pass K: Qs rows, dO rows, Qs^T, dO^T ------------------------------------------------------
-    for (int it = tid; it < LP * 8; it += AB::NT) {
-        const int t = it >> 3, c = it & 7;
-        put_rows(img0, t, c, row8(t, 0, c, QS));
-        put_rows(img1, t, c, do8(t, c));
-    }
-    __syncthreads();
-    // ---- sub-pass K ------------------------------------------------------------------------------------------
-    // (one 16-key block at a time, as sub-pass Q: the Qs / dO fragments are read twice)
-    if (!MODCR_DBG(p.debug & 4)) {
-#pragma unroll 1
-        for (int kb = 0; kb < 2; ++kb) {
-            const int key = t0 + kb * 16 + l15_;
-            bf16x8 fkk[2], fvv[2];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                fkk[ks] = row8(key, 1, ks * 4 + l4_, 1.0f);
-                fvv[ks] = row8(key, 2, ks * 4 + l4_, 1.0f);
-            }
-            const float mkey = sMask[key];
-            f32x4 dk[4], dv[4];
-#pragma unroll
-            for (int db = 0; db < 4; ++db) { dk[db] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[db] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll 1
-            for (int qt = 0; qt < 6; ++qt) {
-                int l15 = l15_, l4 = l4_;
-                asm volatile("" : "+v"(l15), "+v"(l4));
-                bf16x8 pB, dsB;
-#pragma unroll
-                for (int qb = 0; qb < 2; ++qb) {
-                    const int qrow = qt * 32 + qb * 16;
-                    const bf16x8 fq0 = *reinterpret_cast<const bf16x8*>(img0 + swz128(qrow + l15, l4));
-                    const bf16x8 fq1 = *reinterpret_cast<const bf16x8*>(img0 + swz128(qrow + l15, 4 + l4));
-                    const bf16x8 fd0 = *reinterpret_cast<const bf16x8*>(img1 + swz128(qrow + l15, l4));
-                    const bf16x8 fd1 = *reinterpret_cast<const bf16x8*>(img1 + swz128(qrow + l15, 4 + l4));
-                    const f32x4 m4 = *reinterpret_cast<const f32x4*>(sM + qrow + 4 * l4);
-                    const f32x4 i4 = *reinterpret_cast<const f32x4*>(sInv + qrow + 4 * l4);
-                    const f32x4 d4 = *reinterpret_cast<const f32x4*>(sDl + qrow + 4 * l4);
-                    f32x4 c = {mkey, mkey, mkey, mkey};
-                    if (p.bits) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const uint32_t word = sBits[(qrow + 4 * l4 + e) * 6 + (key >> 5)];
-                            if (!((word >> (key & 31)) & 1u)) c[e] += MODCR_NEG * LOG2E;
-                        }
-                    }
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fq0, fkk[0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fq1, fkk[1], c, 0, 0, 0);
-                    f32x4 dp = {0.f, 0.f, 0.f, 0.f};
-                    dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd0, fvv[0], dp, 0, 0, 0);
-                    dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd1, fvv[1], dp, 0, 0, 0);
-                    // dropout: a lane's four values are four queries of ONE key, i.e. four different hash counters; the
-                    // four lanes of a quad (keys of one key group) need the same four, so each hashes one and they are
-                    // exchanged by quad broadcasts: one hash per lane instead of four
-                    uint32_t hqx = 0, hqy = 0;
-                    if (p.drop_thr16)
-                        attn_drop_words((uint32_t)((n * p.A + a) * 256 + qrow + 4 * l4 + (l15 & 3)), key >> 2, p.drop_key, hqx, hqy);
-                    const uint32_t xq[4] = {quad_bcast<0>(hqx), quad_bcast<1>(hqx), quad_bcast<2>(hqx), quad_bcast<3>(hqx)};
-                    const uint32_t yq[4] = {quad_bcast<0>(hqy), quad_bcast<1>(hqy), quad_bcast<2>(hqy), quad_bcast<3>(hqy)};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float pe = __builtin_amdgcn_exp2f(c[e] - m4[e]) * i4[e];
-                        float mk = 1.0f;                    // dropout factor of (query qrow + 4 l4 + e, key)
-                        if (p.drop_thr16)                   // the words of query e were hashed by quad lane e
-                            mk = attn_keep_field(xq[e], yq[e], key & 3, p.drop_thr16) ? p.drop_keep : 0.f;
-                        float dpe = mk * dp[e];
-                        if constexpr (DALIGN) {
-                            const int T = p.align_t, qi = qrow + 4 * l4 + e;
-                            if (qi < T && key >= T && key < S) {
-                                const float da = p.d_align[((int64_t)n * T + qi) * (S - T) + (key - T)];
-                                dpe += p.side_post_drop ? mk * da : da;
-                            }
-                        }
-                        pB[4 * qb + e] = (bf16)(pe * mk);                   // dV takes the masked probabilities
-                        dsB[4 * qb + e] = (bf16)(pe * (dpe - d4[e]));
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#pragma unroll
-                for (int db = 0; db < 4; ++db) {
-                    const bf16x8 qf = tr8(img0, qt * 32, db, l15, l4), df = tr8(img1, qt * 32, db, l15, l4);
-                    dv[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df, pB, dv[db], 0, 0, 0);
-                    dk[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, dsB, dk[db], 0, 0, 0);
-                }
-            }
-            if (key < S)
-#pragma unroll
-                for (int db = 0; db < 4; ++db) {
-                    f32x4 ok = dk[db];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ok[e] *= (1.0f / LOG2E);
-                    const int64_t at = (int64_t)key * 3 * H + H + db * 16 + 4 * l4_;
-                    if (p.out_bf16) {
-                        bf16* ob = reinterpret_cast<bf16*>(p.dqkv) + (int64_t)n * S * 3 * H + a * 64 + at;
-                        const f32x4 ov = dv[db];
-                        *reinterpret_cast<bf16x4*>(ob) = bf16x4{(bf16)ok[0], (bf16)ok[1], (bf16)ok[2], (bf16)ok[3]};
-                        *reinterpret_cast<bf16x4*>(ob + H) = bf16x4{(bf16)ov[0], (bf16)ov[1], (bf16)ov[2], (bf16)ov[3]};
-                    } else {
-                        *reinterpret_cast<f32x4*>(dqkv + at) = ok;
-                        *reinterpret_cast<f32x4*>(dqkv + at + H) = dv[db];
-                    }
-                }
-        }
-    }
-}
-
-// ---- attention core backward, exact fp32 (VALU): one block (4 waves) per (n, head) ------------------------------
-// From the recomputed q|k|v rows [N,S,3H] (fp32) and dctx: dq|dk|dv rows [N,S,3H] (fp32).  No saved
-// probabilities: pass A (K, V in LDS; one query per wave-iteration) recomputes p_ij, forms dp_ij = dO_i.V_j,
-// delta_i = sum_j p dp, ds_ij = p (dp - delta) and dQ_i = sum_j ds_ij K_j / 8, keeping (max, 1/sum, delta) of
-// every row in LDS; pass B (Q, dO in LDS; one key per wave-iteration) rebuilds p and ds from those row
-// statistics and accumulates dV_j = sum_i p_ij dO_i, dK_j = sum_i ds_ij Q_i / 8.  Mask semantics as the forward.
-
-template <typename TD>
-__global__ __launch_bounds__(256) void attn_bwd_f32_kernel(AttnBwdArgs p) {
-    extern __shared__ float sm[];
-    const int S = p.S, H = p.H;
-    float* sA = sm;                          // pass A: K   | pass B: Q      [S][65]
-    float* sB = sA + (size_t)S * 65;         // pass A: V   | pass B: dO     [S][65]
-    float* sMx = sB + (size_t)S * 65;        // row max, 1 / row sum, delta  [3][S]
-    float* sInv = sMx + S;
-    float* sDl = sInv + S;
-    float* sW = sDl + S;                     // per wave: 64 + 64 + S + S floats
-    const int n = blockIdx.x / p.A, a = blockIdx.x % p.A;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* wq = sW + (size_t)wave * (128 + 2 * S);      // query row (A) / key row (B)
-    float* wd = wq + 64;                                 // dO row (A) / value row (B)
-    float* wp = wd + 64;                                 // p_j (B: p_i)
-    float* ws = wp + S;                                  // ds_j (B: ds_i)
-    const int LW = (S + 31) >> 5;
-    const float* qkv = p.qkv + (int64_t)n * S * 3 * H;
-    const TD* dctx = reinterpret_cast<const TD*>(p.dctx) + (int64_t)n * S * H;
-    float* dqkv = p.dqkv + (int64_t)n * S * 3 * H;
-    auto seen = [&](int i, int j) {
-        if (p.bits) return ((p.bits[((int64_t)n * S + i) * LW + (j >> 5)] >> (j & 31)) & 1u) != 0;
-        return p.key_mask[(int64_t)n * S + j] != 0.f;
-    };
-    auto dalign = [&](int i, int j) {       // gradient arriving through the align map
-        const int T = p.align_t;
-        return (p.d_align && i < T && j >= T) ? p.d_align[((int64_t)n * T + i) * (S - T) + (j - T)] : 0.f;
-    };
-    // the forward's attention-probability dropout (tile kernels, csrc/attn_common.h): keep / (1 - p) of weight (i, j), regenerated
-    // from its counter layout -- ctx = (P o m) V, so dP = m o (dO V^T) and dV = (P o m)^T dO; the align map saw the unmasked P
-    const uint32_t dthr = p.drop_thr16;
-    auto dmask = [&](int i, int j) {
-        if (!dthr) return 1.0f;
-        uint32_t hx, hy;
-        attn_drop_words((uint32_t)((n * p.A + a) * 256 + i), j >> 2, p.drop_key, hx, hy);
-        return attn_keep_field(hx, hy, j & 3, dthr) ? p.drop_keep : 0.f;
-    };
-    // ---- pass A ------------------------------------------------------------------------------------------
-    for (int idx = tid; idx < S * 64; idx += 256) {
-        const int j = idx >> 6, d = idx & 63;
-        sA[j * 65 + d] = qkv[(int64_t)j * 3 * H + H + a * 64 + d];
-        sB[j * 65 + d] = qkv[(int64_t)j * 3 * H + 2 * H + a * 64 + d];
-    }
-    __syncthreads();
-    for (int i = wave; i < S; i += 4) {
-        wq[lane] = qkv[(int64_t)i * 3 * H + a * 64 + lane];
-        wd[lane] = to_f32(dctx[(int64_t)i * H + a * 64 + lane]);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        float sv[4], dp[4], mx = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int j = lane + 64 * c;
-            sv[c] = -INFINITY; dp[c] = 0.f;
-            if (j < S) {
-                float s = 0.f, t = 0.f;
-                for (int d = 0; d < 64; ++d) { s = fmaf(wq[d], sA[j * 65 + d], s); t = fmaf(wd[d], sB[j * 65 + d], t); }
-                s = s / 8.0f + (seen(i, j) ? 0.f : MODCR_NEG);
-                sv[c] = s; dp[c] = p.side_post_drop ? (t + dalign(i, j)) * dmask(i, j) : t * dmask(i, j) + dalign(i, j);
-                mx = fmaxf(mx, s);
-            }
-        }
-        mx = wave_max(mx);
-        float sum = 0.f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) if (lane + 64 * c < S) { sv[c] = expf(sv[c] - mx); sum += sv[c]; }
-        sum = wave_sum(sum);
-        const float inv = 1.0f / sum;
-        float dl = 0.f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) if (lane + 64 * c < S) { sv[c] *= inv; dl += sv[c] * dp[c]; }
-        dl = wave_sum(dl);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) if (lane + 64 * c < S) ws[lane + 64 * c] = sv[c] * (dp[c] - dl);
-        if (lane == 0) { sMx[i] = mx; sInv[i] = inv; sDl[i] = dl; }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        float g = 0.f;
-        for (int j = 0; j < S; ++j) g = fmaf(ws[j], sA[j * 65 + lane], g);
-        dqkv[(int64_t)i * 3 * H + a * 64 + lane] = g / 8.0f;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    }
-    __syncthreads();
-    // ---- pass B ------------------------------------------------------------------------------------------
-    for (int idx = tid; idx < S * 64; idx += 256) {
-        const int i = idx >> 6, d = idx & 63;
-        sA[i * 65 + d] = qkv[(int64_t)i * 3 * H + a * 64 + d];
-        sB[i * 65 + d] = to_f32(dctx[(int64_t)i * H + a * 64 + d]);
-    }
-    __syncthreads();
-    for (int j = wave; j < S; j += 4) {
-        wq[lane] = qkv[(int64_t)j * 3 * H + H + a * 64 + lane];
-        wd[lane] = qkv[(int64_t)j * 3 * H + 2 * H + a * 64 + lane];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int i = lane + 64 * c;
-            if (i < S) {
-                float s = 0.f, t = 0.f;
-                for (int d = 0; d < 64; ++d) { s = fmaf(sA[i * 65 + d], wq[d], s); t = fmaf(sB[i * 65 + d], wd[d], t); }
-                s = s / 8.0f + (seen(i, j) ? 0.f : MODCR_NEG);
-                const float pij = expf(s - sMx[i]) * sInv[i];
-                const float mij = dmask(i, j);
-                wp[i] = pij * mij;
-                ws[i] = pij * ((p.side_post_drop ? (t + dalign(i, j)) * mij : t * mij + dalign(i, j)) - sDl[i]);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        float gv = 0.f, gk = 0.f;
-        for (int i = 0; i < S; ++i) { gv = fmaf(wp[i], sB[i * 65 + lane], gv); gk = fmaf(ws[i], sA[i * 65 + lane], gk); }
-        dqkv[(int64_t)j * 3 * H + H + a * 64 + lane] = gk / 8.0f;
-        dqkv[(int64_t)j * 3 * H + 2 * H + a * 64 + lane] = gv;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    }
-}
-
 }  // namespace
 
 extern "C" int modcr_time_next_attn(void* start_event, void* stop_event) {
@@ -2588,396 +2100,4 @@ extern "C" int modcr_qkv_attn_route(int32_t present, int32_t chunk_t, int32_t al
     for (int i = 0; i < 5; ++i) info[1 + i] = r.v[i];
     info[6] = r.concat;
     return MODCR_OK;
-}
-
-
-// ---- backward of modcr_qkv_attn_fwd (no prefix rows) ---------------------------------------------------------------
-static int64_t attn_bwd_sub_ws(int32_t M, int32_t H) {
-    const int64_t a = modcr_linear_bwd_input_workspace(M, 3 * H, H), b = modcr_linear_bwd_weight_workspace(M, 3 * H, H);
-    return ((a > b ? a : b) + 255) & ~(int64_t)255;
-}
-extern "C" int64_t modcr_qkv_attn_bwd_workspace(int32_t N, int32_t S, int32_t H, int32_t dtype) {
-    (void)dtype;
-    const int64_t rows = (int64_t)N * S * 3 * H * (int64_t)sizeof(float);
-    return 2 * ((rows + 255) & ~(int64_t)255) + attn_bwd_sub_ws(N * S, H);
-}
-
-namespace {
-
-// Every backward entry (modcr_qkv_attn_bwd, _dropout_bwd, _lse_bwd, _opt_bwd).
-// ctx + lse (both or neither; bf16 path): the forward's context rows and the row statistics modcr_qkv_attn_lse_fwd wrote.  With
-// them the attention core runs as the five-product kernel of attn_bwd.hip (P rebuilt from lse, delta = rowsum(dO o O));
-// without them, or with an align-map gradient, the older core recomputes the statistics (eight products).
-// flags: MODCR_ATTN_SIDE_POST_DROPOUT = d_align is the gradient of an align map that summed the probabilities AFTER the dropout
-// (modcr_qkv_attn_opt_fwd with the same flag): it enters dP under the forward's mask, m / (1 - p) o d_align
-int attn_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* key_mask, const uint32_t* dense_mask_bits,
-             const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx, float* dwqkv, float* dbqkv, int32_t accumulate,
-             int32_t N, int32_t S, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, const float* d_align, int32_t align_t,
-             const void* ctx, const float* lse, const void* qkv_dump, int32_t flags, void* workspace, int64_t workspace_bytes, int32_t dtype,
-             modcr_stream_t stream) {
-    MODCR_REQUIRE(dctx && x && wqkv && bqkv && dx && dwqkv && dbqkv, "qkv_attn_bwd: null pointer");
-    MODCR_REQUIRE((flags & ~MODCR_ATTN_SIDE_POST_DROPOUT) == 0, "qkv_attn_bwd: unknown flags 0x%x", flags);
-    MODCR_REQUIRE(!d_align || (align_t > 0 && align_t < S), "qkv_attn_bwd: align_t=%d out of range", align_t);
-    MODCR_REQUIRE((ctx == nullptr) == (lse == nullptr), "qkv_attn_bwd: ctx and lse come together");
-    MODCR_REQUIRE(!qkv_dump || (lse && dtype == MODCR_BF16 && S > 64 && S <= 192),
-                  "qkv_attn_bwd: the forward's q|k|v dump is used with ctx + lse, bf16, 64 < S <= 192");
-    MODCR_REQUIRE(attn_p >= 0.f && attn_p < 1.f, "qkv_attn_bwd: attention dropout p=%g out of [0, 1)", attn_p);
-    // the mask of modcr_qkv_attn_dropout_fwd exists for its tile kernels only, and only the MFMA core regenerates it
-    // (64 < S <= 192: the MFMA cores; 192 < S <= 256, the forward's 256-token tile: the exact core below -- the shape class of
-    // BASELINE config 5 with trainable encoders, not a benched path)
-    // (every core regenerates the forward's mask from (seed, offset): the MFMA cores at 64 < S <= 192, the exact core elsewhere and in fp32)
-    MODCR_REQUIRE(attn_p == 0.f || S <= 256, "qkv_attn_bwd: attention-probability dropout needs S <= 256 (S=%d)", S);
-    MODCR_REQUIRE(N > 0 && S > 0 && S <= 256 && A > 0 && H == A * 64, "qkv_attn_bwd: bad shape (N=%d S=%d H=%d A=%d)", N, S, H, A);
-    MODCR_REQUIRE(key_mask || dense_mask_bits, "qkv_attn_bwd: need key_mask or dense_mask_bits");
-    MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "qkv_attn_bwd: unknown dtype %d", dtype);
-    const int64_t need = modcr_qkv_attn_bwd_workspace(N, S, H, dtype);
-    MODCR_REQUIRE(workspace && workspace_bytes >= need, "qkv_attn_bwd: workspace %lld < %lld bytes",
-                  (long long)workspace_bytes, (long long)need);
-    const int M = N * S;
-    const int64_t rows = (((int64_t)M * 3 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
-    float* qkv = (float*)workspace;
-    float* dqkv = (float*)((char*)workspace + rows);
-    // bf16: the two weight / input products run on the MFMA path (workspace); fp32 parity path: exact VALU kernels
-    void* sub = dtype == MODCR_BF16 ? (void*)((char*)workspace + 2 * rows) : nullptr;
-    const int64_t sub_bytes = dtype == MODCR_BF16 ? attn_bwd_sub_ws(M, H) : 0;
-    // 1. recompute q | k | v rows, chunk-mean queries as the forward.  MFMA core: bf16 rows (what the forward's LDS images held;
-    //    half the bytes of the fp32 rows round 1 wrote and read back: 849 MB per call at 128 examples); exact core: fp32
-    const bool mfma_core = dtype == MODCR_BF16 && S <= AB::LP && !modcr_knob_set("MODCR_ATTN_BWD_VALU");
-    const int32_t qdt = mfma_core ? MODCR_BF16 : MODCR_F32;
-    int rc = MODCR_OK;
-    if (!qkv_dump) {                // (with the forward's dump nothing is recomputed: its Q image already holds the chunk means)
-        rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, qkv, 3 * H, M, 3 * H, H, MODCR_ACT_NONE, dtype, qdt, stream);
-        if (rc != MODCR_OK) return rc;
-        if (chunk_id) {
-            rc = modcr_chunk_mean_q_fwd(qkv, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, qdt, stream);
-            if (rc != MODCR_OK) return rc;
-        }
-    }
-    // 2. attention core backward
-    AttnBwdArgs b;
-    b.qkv = qkv; b.qkvb = reinterpret_cast<const bf16*>(qkv); b.dctx = dctx; b.key_mask = key_mask; b.bits = dense_mask_bits; b.dqkv = dqkv;
-    b.N = N; b.S = S; b.H = H; b.A = A; b.out_bf16 = 0;
-    const AttnDrop d = attn_drop(attn_p, seed, offset);     // (as the forward)
-    b.drop_thr16 = d.thr16; b.drop_key = d.key; b.drop_keep = d.keep;
-    b.side_post_drop = (attn_p > 0.f && (flags & MODCR_ATTN_SIDE_POST_DROPOUT)) ? 1 : 0;
-    b.d_align = d_align; b.align_t = align_t;
-    b.ctx = reinterpret_cast<const bf16*>(ctx); b.lse = lse; b.dump = reinterpret_cast<const bf16*>(qkv_dump);
-    b.delta_align = qkv_dump ? qkv : nullptr;               // (with the dump the q|k|v area of the workspace is free: N A S floats of it)
-    b.debug = modcr_knob_int("MODCR_ATTN_BWD_DEBUG", 0);                 // tuning build only
-    const size_t smem = ((size_t)2 * S * 65 + 3 * (size_t)S + 4 * (128 + 2 * (size_t)S)) * sizeof(float);
-    static bool configured_dev[MODCR_MAX_DEV] = {};
-    bool& configured = configured_dev[modcr_device_index()];
-    if (!configured) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_f32_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_f32_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        configured = true;
-    }
-    int gdt = MODCR_F32;            // dtype of the dq | dk | dv rows
-    if (mfma_core && lse && (!d_align || qkv_dump) && !modcr_knob_set("MODCR_ATTN_BWD_OLD")) {
-        b.out_bf16 = 1; gdt = MODCR_BF16;
-        rc = modcr_launch_attn_bwd5(b, (hipStream_t)stream);
-        if (rc != MODCR_OK) return rc;
-    } else if (mfma_core) {
-        b.out_bf16 = 1; gdt = MODCR_BF16;
-        static bool configured2_dev[MODCR_MAX_DEV] = {};
-        bool& configured2 = configured2_dev[modcr_device_index()];
-        if (!configured2) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_mfma_kernel<bf16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, AB::SMEM);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_mfma_kernel<bf16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, AB::SMEM);
-            configured2 = true;
-        }
-        if (d_align) hipLaunchKernelGGL((attn_bwd_mfma_kernel<bf16, true>), dim3(N * A), dim3(AB::NT), AB::SMEM, (hipStream_t)stream, b);
-        else hipLaunchKernelGGL((attn_bwd_mfma_kernel<bf16, false>), dim3(N * A), dim3(AB::NT), AB::SMEM, (hipStream_t)stream, b);
-    } else if (dtype == MODCR_BF16) hipLaunchKernelGGL(attn_bwd_f32_kernel<bf16>, dim3(N * A), dim3(256), smem, (hipStream_t)stream, b);
-    else hipLaunchKernelGGL(attn_bwd_f32_kernel<float>, dim3(N * A), dim3(256), smem, (hipStream_t)stream, b);
-    rc = modcr_check_launch("attn_bwd");
-    if (rc != MODCR_OK) return rc;
-    // 3. the chunk mean is its own adjoint: dq rows of a chunk <- their mean (v10:66-78)
-    if (chunk_id) {
-        rc = modcr_chunk_mean_q_fwd(dqkv, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, gdt, stream);
-        if (rc != MODCR_OK) return rc;
-    }
-    // 4. dX = dqkv . Wqkv;  dWqkv (+)= dqkv^T . X;  dbqkv (+)= column sums
-    rc = modcr_linear_bwd_input_res(dqkv, 3 * H, gdt, wqkv, H, dx_residual, H, dx, H, M, 3 * H, H, dtype, dtype, sub, sub_bytes, stream);
-    if (rc != MODCR_OK) return rc;
-    return modcr_linear_bwd_weight(dqkv, 3 * H, gdt, x, H, dwqkv, dbqkv, M, 3 * H, H, accumulate, dtype, sub, sub_bytes, stream);
-}
-
-}  // namespace
-
-extern "C" int modcr_qkv_attn_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* key_mask,
-                                  const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, void* dx, float* dwqkv, float* dbqkv,
-                                  int32_t accumulate, int32_t N, int32_t S, int32_t H, int32_t A, void* workspace, int64_t workspace_bytes,
-                                  int32_t dtype, modcr_stream_t stream) {
-    return attn_bwd(dctx, x, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, nullptr, dx, dwqkv, dbqkv, accumulate,
-                    N, S, H, A, 0.f, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, workspace, workspace_bytes, dtype, stream);
-}
-
-extern "C" int modcr_qkv_attn_dropout_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* key_mask,
-                                          const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual,
-                                          void* dx, float* dwqkv, float* dbqkv, int32_t accumulate, int32_t N, int32_t S, int32_t H, int32_t A,
-                                          float attn_p, uint64_t seed, uint64_t offset, const float* d_align, int32_t align_t, void* workspace,
-                                          int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
-    return attn_bwd(dctx, x, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, dx_residual, dx, dwqkv, dbqkv, accumulate,
-                    N, S, H, A, attn_p, seed, offset, d_align, align_t, nullptr, nullptr, nullptr, 0, workspace, workspace_bytes, dtype, stream);
-}
-
-extern "C" int modcr_qkv_attn_lse_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* key_mask,
-                                      const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx,
-                                      float* dwqkv, float* dbqkv, int32_t accumulate, int32_t N, int32_t S, int32_t H, int32_t A, float attn_p,
-                                      uint64_t seed, uint64_t offset, const float* d_align, int32_t align_t, const void* ctx, const float* lse,
-                                      const void* qkv_dump, void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream) {
-    return attn_bwd(dctx, x, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, dx_residual, dx, dwqkv, dbqkv, accumulate,
-                    N, S, H, A, attn_p, seed, offset, d_align, align_t, ctx, lse, qkv_dump, 0, workspace, workspace_bytes, dtype, stream);
-}
-
-extern "C" int modcr_qkv_attn_opt_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* key_mask,
-                                      const uint32_t* dense_mask_bits, const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx,
-                                      float* dwqkv, float* dbqkv, int32_t accumulate, int32_t N, int32_t S, int32_t H, int32_t A, float attn_p,
-                                      uint64_t seed, uint64_t offset, const float* d_align, int32_t align_t, const void* ctx, const float* lse,
-                                      const void* qkv_dump, int32_t flags, void* workspace, int64_t workspace_bytes, int32_t dtype,
-                                      modcr_stream_t stream) {
-    return attn_bwd(dctx, x, wqkv, bqkv, key_mask, dense_mask_bits, chunk_id, chunk_t, dx_residual, dx, dwqkv, dbqkv, accumulate,
-                    N, S, H, A, attn_p, seed, offset, d_align, align_t, ctx, lse, qkv_dump, flags, workspace, workspace_bytes, dtype, stream);
-}
-
-// ---- backward of modcr_qkv_attn_bias_fwd: modcr_qkv_attn_bias_bwd (no prefix rows), modcr_qkv_attn_prefix_bwd (hist [N, P, H], P >= 1)
-// and modcr_qkv_attn_gate_bwd (either, + the gradient of head_mask) ----
-// One body, attn_bwd()'s step for step with the cores of attn_bias_bwd.hip in step 2: S queries against P + S <= 256 keys, no
-// align-map gradient.  With prefix rows (no chunk mean then) a second, K | V only set of GEMMs serves them: rows H..3H of wqkv / bqkv
-// are a contiguous [2H, H] sub-block (ldw = H).
-// modcr_qkv_attn_long_bwd is the same body with the key limit 512 (max_keys): at P + S <= 256 nothing differs; above, step 2 runs the
-// streaming cores of attn_long_bwd.hip (no dropout there) and the workspace grows by their per-row statistics.
-namespace {
-
-// The workspace: q | k | v and dq | dk | dv rows of the own rows (rows_x each), k | v and dk | dv rows of the prefix rows (rows_h
-// each; 0 without), then the GEMMs' sub-workspace (the larger of the two sets' needs)
-// ... and, above 256 keys only (the streaming cores), their per-row statistics fp32 [N A][3][S rounded up to 64] at the end
-struct AttnBiasBwdWs {
-    int64_t rows_x, rows_h, sub, stats;
-    int64_t bytes() const { return 2 * rows_x + 2 * rows_h + sub + stats; }
-};
-AttnBiasBwdWs attn_bias_bwd_ws(int32_t N, int32_t S, int32_t P, int32_t H, int max_keys = 256) {
-    AttnBiasBwdWs w;
-    w.stats = (int64_t)P + S <= 256 || max_keys <= 256 ? 0 : (((int64_t)N * (H / 64) * 3 * ((S + 63) & ~63) * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
-    w.rows_x = (((int64_t)N * S * 3 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
-    w.rows_h = (((int64_t)N * P * 2 * H * (int64_t)sizeof(float)) + 255) & ~(int64_t)255;
-    w.sub = attn_bwd_sub_ws(N * S, H);
-    if (P > 0) {
-        const int64_t a = modcr_linear_bwd_input_workspace(N * P, 2 * H, H), b = modcr_linear_bwd_weight_workspace(N * P, 2 * H, H);
-        const int64_t h = ((a > b ? a : b) + 255) & ~(int64_t)255;
-        if (h > w.sub) w.sub = h;
-    }
-    return w;
-}
-
-// 0 = refused, 1 = attn_bias_bwd_mfma_kernel, 2 = attn_bias_bwd_f32_kernel; with max_keys = 512 (modcr_qkv_attn_long_bwd) above 256
-// keys: 3 = the streaming bf16 kernels of attn_long_bwd.hip, 4 = its exact fp32 kernels
-int attn_bias_bwd_core(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype, int max_keys = 256) {
-    if (N <= 0 || S <= 0 || P < 0 || (int64_t)P + S > max_keys || A <= 0 || H != A * 64 || (dtype != MODCR_BF16 && dtype != MODCR_F32)) return 0;
-    if (P + S > 256) return dtype == MODCR_BF16 ? 3 : 4;
-    return dtype == MODCR_BF16 && P + S <= AB::LP ? 1 : 2;
-}
-
-// hist / d_hist / P: the prefix rows and their gradient (null, null, 0 from modcr_qkv_attn_bias_bwd); chunk_id / chunk_t: the chunk
-// mean of the queries (null, 0 from modcr_qkv_attn_prefix_bwd); d_head_mask: fp32 [N, A] (null from both; modcr_qkv_attn_gate_bwd's);
-// max_keys: 256, or 512 from modcr_qkv_attn_long_bwd
-int attn_bias_bwd(const char* who, const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* attn_bias,
-                  int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q, const float* head_mask, int64_t head_mask_stride_n,
-                  const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv,
-                  int32_t accumulate, float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
-                  uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream,
-                  int max_keys = 256) {
-    MODCR_REQUIRE(dctx && x && wqkv && bqkv && dx && (d_hist || !P) && dwqkv && dbqkv, "%s: null pointer", who);
-    MODCR_REQUIRE(dtype == MODCR_BF16 || dtype == MODCR_F32, "%s: unknown dtype %d", who, dtype);
-    MODCR_REQUIRE(N > 0 && S > 0 && A > 0, "%s: bad shape (N=%d S=%d P=%d H=%d A=%d)", who, N, S, P, H, A);
-    MODCR_REQUIRE(H == A * 64, "%s: head size must be 64 (H=%d, A=%d)", who, H, A);
-    if ((int64_t)P + S > max_keys) {
-        modcr_set_error("%s: P + S = %lld keys (P=%d) exceeds the %d-key limit of the attention backward", who, (long long)P + S, P, max_keys);
-        return MODCR_ERR_UNSUPPORTED;
-    }
-    if ((int64_t)P + S > 256 && attn_p > 0.f) {
-        modcr_set_error("%s: attention-probability dropout (p=%g) is not implemented above 256 keys (P+S=%d)", who, attn_p, P + S);
-        return MODCR_ERR_UNSUPPORTED;
-    }
-    // (with d_head_mask a missing head_mask is a mask of ones: the head-importance call)
-    MODCR_REQUIRE(attn_bias || head_mask || d_head_mask, "%s: neither bias nor head_mask%s", who,
-                  P ? "" : " (that call belongs to modcr_qkv_attn_opt_bwd)");
-    MODCR_REQUIRE(attn_bias || !d_bias, "%s: d_bias without a bias", who);
-    MODCR_REQUIRE(attn_p >= 0.f && attn_p < 1.f, "%s: attention dropout p=%g out of [0, 1)", who, attn_p);
-    MODCR_REQUIRE(bias_stride_n >= 0 && bias_stride_a >= 0 && bias_stride_q >= 0 && head_mask_stride_n >= 0, "%s: negative stride", who);
-    // (the cores address a (sequence, head) slice of the bias with 32-bit element offsets)
-    MODCR_REQUIRE(bias_stride_q <= (1 << 20), "%s: bias query stride %lld exceeds 2^20 elements", who, (long long)bias_stride_q);
-    MODCR_REQUIRE(((uintptr_t)attn_bias & 3) == 0 && ((uintptr_t)head_mask & 3) == 0 && ((uintptr_t)d_bias & 3) == 0 &&
-                      ((uintptr_t)d_head_mask & 3) == 0,
-                  "%s: bias / head_mask / d_bias%s not 4-byte aligned", who, d_head_mask ? " / d_head_mask" : "");
-    MODCR_REQUIRE(!chunk_id || (chunk_t > 0 && chunk_t <= S), "%s: chunk_t=%d out of range", who, chunk_t);
-    MODCR_REQUIRE(dtype != MODCR_BF16 || (modcr_aligned16(dctx) && modcr_aligned16(x) && modcr_aligned16(hist) && modcr_aligned16(wqkv) &&
-                                          modcr_aligned16(dx) && modcr_aligned16(d_hist)),
-                  "%s(bf16): 16-byte alignment", who);
-    const AttnBiasBwdWs ws = attn_bias_bwd_ws(N, S, P, H, max_keys);
-    MODCR_REQUIRE(workspace && workspace_bytes >= ws.bytes() && modcr_aligned16(workspace), "%s: workspace %lld < %lld bytes (or unaligned)", who,
-                  (long long)workspace_bytes, (long long)ws.bytes());
-    const int core = attn_bias_bwd_core(N, S, P, H, A, dtype, max_keys);
-    // (the streaming kernels' grid is (block, head, sequence))
-    MODCR_REQUIRE(core < 3 || (N <= 65535 && A <= 65535), "%s: grid of N=%d sequences x A=%d heads too large", who, N, A);
-    const int M = N * S, Mh = N * P;
-    char* w = (char*)workspace;
-    void* qkv = w;
-    void* dqkv = w + ws.rows_x;
-    void* kvh = P ? w + 2 * ws.rows_x : nullptr;
-    void* dkvh = P ? w + 2 * ws.rows_x + ws.rows_h : nullptr;
-    // bf16: the weight / input products run on the MFMA path (workspace); fp32 parity path: exact VALU kernels
-    void* sub = dtype == MODCR_BF16 ? (void*)(w + 2 * ws.rows_x + 2 * ws.rows_h) : nullptr;
-    const int64_t sub_bytes = dtype == MODCR_BF16 ? ws.sub : 0;
-    const size_t esz = dtype == MODCR_BF16 ? 2 : 4;
-    const void* wkv = (const char*)wqkv + (size_t)H * H * esz;                  // rows H..3H of wqkv: the K | V projection [2H, H]
-    // 1. recompute the rows (MFMA core: bf16, exact core: fp32): q | k | v of the own rows, chunk-mean queries as the forward; k | v of
-    //    the prefix rows
-    const int32_t qdt = core == 1 || core == 3 ? MODCR_BF16 : MODCR_F32;
-    int rc = modcr_linear_fwd(x, H, wqkv, H, bqkv, nullptr, 0, 0, qkv, 3 * H, M, 3 * H, H, MODCR_ACT_NONE, dtype, qdt, stream);
-    if (rc != MODCR_OK) return rc;
-    if (chunk_id) {
-        rc = modcr_chunk_mean_q_fwd(qkv, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, qdt, stream);
-        if (rc != MODCR_OK) return rc;
-    }
-    if (P) {
-        rc = modcr_linear_fwd(hist, H, wkv, H, bqkv + H, nullptr, 0, 0, kvh, 2 * H, Mh, 2 * H, H, MODCR_ACT_NONE, dtype, qdt, stream);
-        if (rc != MODCR_OK) return rc;
-    }
-    // 2. attention core backward
-    AttnBiasBwdArgs b;
-    b.qkv = qkv; b.kvh = kvh; b.dctx = dctx; b.dqkv = dqkv; b.dkvh = dkvh;
-    b.bias = attn_bias; b.bias_sn = bias_stride_n; b.bias_sa = bias_stride_a; b.bias_sq = bias_stride_q;
-    b.head_mask = head_mask; b.head_mask_sn = head_mask_stride_n;
-    b.d_bias = d_bias; b.d_head_mask = d_head_mask;
-    const AttnDrop d = attn_drop(attn_p, seed, offset);     // (as the forward)
-    b.drop_thr16 = d.thr16; b.drop_key = d.key; b.drop_keep = d.keep;
-    b.N = N; b.S = S; b.P = P; b.H = H; b.A = A;
-    b.stats = core >= 3 ? (float*)(w + 2 * ws.rows_x + 2 * ws.rows_h + ws.sub) : nullptr;
-    rc = core >= 3 ? modcr_launch_attn_long_bwd(b, core, dtype, (hipStream_t)stream) : modcr_launch_attn_bias_bwd(b, core, dtype, (hipStream_t)stream);
-    if (rc != MODCR_OK) return rc;
-    // 3. the chunk mean is its own adjoint
-    if (chunk_id) {
-        rc = modcr_chunk_mean_q_fwd(dqkv, 3 * H, (int64_t)S * 3 * H, chunk_id, N, chunk_t, H, qdt, stream);
-        if (rc != MODCR_OK) return rc;
-    }
-    // 4. own rows: dX = dqkv . Wqkv (+ dx_residual);  dWqkv (+)= dqkv^T . X;  dbqkv (+)= column sums
-    rc = modcr_linear_bwd_input_res(dqkv, 3 * H, qdt, wqkv, H, dx_residual, H, dx, H, M, 3 * H, H, dtype, dtype, sub, sub_bytes, stream);
-    if (rc != MODCR_OK) return rc;
-    rc = modcr_linear_bwd_weight(dqkv, 3 * H, qdt, x, H, dwqkv, dbqkv, M, 3 * H, H, accumulate, dtype, sub, sub_bytes, stream);
-    if (rc != MODCR_OK || !P) return rc;
-    // 5. prefix rows, K | V only: d_hist = d(k|v) . Wqkv[H:3H];  dWqkv[H:3H] += d(k|v)^T . hist;  dbqkv[H:3H] += column sums
-    rc = modcr_linear_bwd_input_res(dkvh, 2 * H, qdt, wkv, H, nullptr, 0, d_hist, H, Mh, 2 * H, H, dtype, dtype, sub, sub_bytes, stream);
-    if (rc != MODCR_OK) return rc;
-    return modcr_linear_bwd_weight(dkvh, 2 * H, qdt, hist, H, dwqkv + (size_t)H * H, dbqkv + H, Mh, 2 * H, H, 1, dtype, sub, sub_bytes, stream);
-}
-
-}  // namespace
-
-extern "C" int64_t modcr_qkv_attn_bias_bwd_workspace(int32_t N, int32_t S, int32_t H, int32_t dtype) {
-    (void)dtype;
-    return attn_bias_bwd_ws(N, S, 0, H).bytes();            // (= modcr_qkv_attn_bwd_workspace)
-}
-
-extern "C" int modcr_qkv_attn_bias_bwd_route(int32_t N, int32_t S, int32_t H, int32_t A, int32_t dtype) {
-    return attn_bias_bwd_core(N, S, 0, H, A, dtype);
-}
-
-extern "C" int modcr_qkv_attn_bias_bwd(const void* dctx, const void* x, const void* wqkv, const float* bqkv, const float* attn_bias,
-                                       int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q, const float* head_mask,
-                                       int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t, const float* dx_residual, void* dx,
-                                       float* dwqkv, float* dbqkv, int32_t accumulate, float* d_bias, int32_t N, int32_t S, int32_t H, int32_t A,
-                                       float attn_p, uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
-                                       modcr_stream_t stream) {
-    return attn_bias_bwd("qkv_attn_bias_bwd", dctx, x, nullptr, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask,
-                         head_mask_stride_n, chunk_id, chunk_t, dx_residual, dx, nullptr, dwqkv, dbqkv, accumulate, d_bias, nullptr, N, S, 0, H, A,
-                         attn_p, seed, offset, workspace, workspace_bytes, dtype, stream);
-}
-
-extern "C" int64_t modcr_qkv_attn_prefix_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
-    (void)dtype;
-    return N <= 0 || S <= 0 || P <= 0 || H <= 0 ? 0 : attn_bias_bwd_ws(N, S, P, H).bytes();
-}
-
-extern "C" int modcr_qkv_attn_prefix_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype) {
-    return P <= 0 ? 0 : attn_bias_bwd_core(N, S, P, H, A, dtype);
-}
-
-extern "C" int modcr_qkv_attn_prefix_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
-                                         const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
-                                         const float* head_mask, int64_t head_mask_stride_n, const float* dx_residual, void* dx, void* d_hist,
-                                         float* dwqkv, float* dbqkv, int32_t accumulate, float* d_bias, int32_t N, int32_t S, int32_t P, int32_t H,
-                                         int32_t A, float attn_p, uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes,
-                                         int32_t dtype, modcr_stream_t stream) {
-    const char* who = "qkv_attn_prefix_bwd";
-    MODCR_REQUIRE(P >= 1 && hist, "%s: no prefix rows (P=%d, hist %s): that call belongs to modcr_qkv_attn_bias_bwd", who, P, hist ? "given" : "null");
-    return attn_bias_bwd(who, dctx, x, hist, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask, head_mask_stride_n,
-                         nullptr, 0, dx_residual, dx, d_hist, dwqkv, dbqkv, accumulate, d_bias, nullptr, N, S, P, H, A, attn_p, seed, offset,
-                         workspace, workspace_bytes, dtype, stream);
-}
-
-// ---- modcr_qkv_attn_gate_bwd: the two entries above in one (P >= 0), with the gradient of head_mask ----
-// what the gate entry and modcr_qkv_attn_long_bwd check before the shared body: P >= 0, hist / d_hist exactly with prefix rows, no chunk mean
-// with them
-static int attn_gate_precheck(const char* who, const void* hist, const void* d_hist, const int32_t* chunk_id, int32_t P) {
-    MODCR_REQUIRE(P >= 0, "%s: bad shape (P=%d)", who, P);
-    MODCR_REQUIRE((hist != nullptr) == (P > 0) && (d_hist != nullptr) == (P > 0),
-                  "%s: hist and d_hist are given exactly with prefix rows (P=%d, hist %s, d_hist %s)", who, P, hist ? "given" : "null",
-                  d_hist ? "given" : "null");
-    MODCR_REQUIRE(!chunk_id || P == 0, "%s: no chunk-mean queries with prefix rows (P=%d)", who, P);
-    return MODCR_OK;
-}
-
-extern "C" int64_t modcr_qkv_attn_gate_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
-    (void)dtype;
-    return N <= 0 || S <= 0 || P < 0 || H <= 0 ? 0 : attn_bias_bwd_ws(N, S, P, H).bytes();
-}
-
-extern "C" int modcr_qkv_attn_gate_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype) {
-    return attn_bias_bwd_core(N, S, P, H, A, dtype);
-}
-
-extern "C" int modcr_qkv_attn_gate_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
-                                       const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
-                                       const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
-                                       const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv, int32_t accumulate,
-                                       float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
-                                       uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
-                                       modcr_stream_t stream) {
-    const char* who = "qkv_attn_gate_bwd";
-    const int rc = attn_gate_precheck(who, hist, d_hist, chunk_id, P);
-    if (rc != MODCR_OK) return rc;
-    return attn_bias_bwd(who, dctx, x, hist, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask, head_mask_stride_n,
-                         chunk_id, chunk_t, dx_residual, dx, d_hist, dwqkv, dbqkv, accumulate, d_bias, d_head_mask, N, S, P, H, A, attn_p, seed,
-                         offset, workspace, workspace_bytes, dtype, stream);
-}
-
-// ---- modcr_qkv_attn_long_bwd: modcr_qkv_attn_gate_bwd with the key limit 512 (opt-in; the streaming cores above 256 keys) ----
-extern "C" int64_t modcr_qkv_attn_long_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
-    (void)dtype;
-    return N <= 0 || S <= 0 || P < 0 || H <= 0 || (int64_t)P + S > 512 ? 0 : attn_bias_bwd_ws(N, S, P, H, 512).bytes();
-}
-
-extern "C" int modcr_qkv_attn_long_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype) {
-    return attn_bias_bwd_core(N, S, P, H, A, dtype, 512);
-}
-
-extern "C" int modcr_qkv_attn_long_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
-                                       const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
-                                       const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
-                                       const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv, int32_t accumulate,
-                                       float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
-                                       uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
-                                       modcr_stream_t stream) {
-    if ((int64_t)P + S <= 256)
-        return modcr_qkv_attn_gate_bwd(dctx, x, hist, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask,
-                                       head_mask_stride_n, chunk_id, chunk_t, dx_residual, dx, d_hist, dwqkv, dbqkv, accumulate, d_bias, d_head_mask,
-                                       N, S, P, H, A, attn_p, seed, offset, workspace, workspace_bytes, dtype, stream);
-    const char* who = "qkv_attn_long_bwd";
-    const int rc = attn_gate_precheck(who, hist, d_hist, chunk_id, P);
-    if (rc != MODCR_OK) return rc;
-    return attn_bias_bwd(who, dctx, x, hist, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask, head_mask_stride_n,
-                         chunk_id, chunk_t, dx_residual, dx, d_hist, dwqkv, dbqkv, accumulate, d_bias, d_head_mask, N, S, P, H, A, attn_p, seed,
-                         offset, workspace, workspace_bytes, dtype, stream, 512);
 }

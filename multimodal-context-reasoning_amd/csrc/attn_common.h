@@ -1,5 +1,7 @@
-// Helpers shared by the attention kernels (attn.hip: forward tile kernels + the older backward cores; attn_bwd.hip: the
-// five-product backward core): the attention-probability dropout hash, LDS row swizzles, the backward argument block.
+// Helpers shared by the attention files -- attn.hip (the forward: tile kernels and host side), attn_long.hip (the streaming forward),
+// attn_bwd.hip and attn_bwd_older.hip (the binary-mask backward cores: five-product; older MFMA and exact), attn_bias_bwd.hip and
+// attn_long_bwd.hip (the bias family's whole-row and streaming backward cores), attn_bwd_host.hip (the host side of every backward entry; no kernel): the
+// attention-probability dropout hash and its host form, LDS row swizzles, the argument blocks, the backward's core ids and launchers.
 #pragma once
 #include "common.h"
 
@@ -110,8 +112,30 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr float LOG2E = 1.44269504088896340736f;
 
+// attention-probability dropout as the host hands it to a kernel: the 64-bit key of (seed, offset), thr16 = round(p * 2^16) (0 = off)
+// and 1 / (1 - p); thr2 = the packed threshold of the bf16 tile kernels
+struct AttnDrop {
+    uint64_t key; uint32_t thr16; float keep;
+    uint32_t thr2() const { return thr16 ? attn_thrm1_2(thr16) : 0; }
+};
+inline AttnDrop attn_drop(float attn_p, uint64_t seed, uint64_t offset) {
+    if (!(attn_p > 0.f)) return {0, 0, 1.f};
+    return {seed + offset * 0x9E3779B97F4A7C15ull, attn_thr16(attn_p), 1.0f / (1.0f - attn_p)};
+}
+
+// token tile of attn_bwd_mfma_kernel (AB::LP) and key limit of the bf16 MFMA backward cores: what the backward's route function compares with
+constexpr int ATTN_BWD_MFMA_LP = 192;
 
 }  // namespace
+
+// The cores of the attention backward, as attn_bwd_route() (attn_bwd_host.hip) names them.  Mask family (key_mask / dense bits):
+// FIVE = attn_bwd5_kernel / attn_bwd6_kernel, MFMA / MFMA_DALIGN = attn_bwd_mfma_kernel<bf16, DALIGN>, EXACT = attn_bwd_f32_kernel;
+// bias family (additive bias, head mask, prefix rows): BIAS_MFMA / BIAS_EXACT = the whole-row cores of attn_bias_bwd.hip, STREAM /
+// STREAM_EXACT = the streaming cores of attn_long_bwd.hip above 256 keys.
+enum AttnBwdCore {
+    ATTN_BWD_REFUSED = 0, ATTN_BWD_FIVE, ATTN_BWD_MFMA, ATTN_BWD_MFMA_DALIGN, ATTN_BWD_EXACT,
+    ATTN_BWD_BIAS_MFMA, ATTN_BWD_BIAS_EXACT, ATTN_BWD_STREAM, ATTN_BWD_STREAM_EXACT
+};
 
 struct AttnBwdArgs {
     const float* qkv; const void* dctx; const float* key_mask; const uint32_t* bits; float* dqkv;
@@ -140,6 +164,9 @@ struct AttnBwdArgs {
 
 // attn_bwd.hip: launches attn_bwd5_kernel on `b` (bf16 rows, 0 < S <= 192, lse and ctx given, no align-map gradient)
 __attribute__((visibility("hidden"))) int modcr_launch_attn_bwd5(const AttnBwdArgs& b, hipStream_t stream);
+// attn_bwd_older.hip: launches the older cores on `b`: ATTN_BWD_MFMA / ATTN_BWD_MFMA_DALIGN (bf16 rows in and out, S <= 192) or ATTN_BWD_EXACT
+// (fp32 rows in and out, S <= 256; dctx in `dtype`)
+__attribute__((visibility("hidden"))) int modcr_launch_attn_bwd_older(const AttnBwdArgs& b, AttnBwdCore core, int32_t dtype, hipStream_t stream);
 
 // attn_bias_bwd.hip: the attention core backward under an additive bias and / or a head mask, S queries against L = P + S keys
 // (modcr_qkv_attn_bias_bwd: P = 0; modcr_qkv_attn_prefix_bwd: P > 0 prefix keys).  The own rows' q | k | v projection qkv [N*S][3H]

@@ -1083,19 +1083,23 @@ ATTN_BWD_MAX_KEYS = 256
 ATTN_BIAS_BWD_CORES = {0: "refused", 1: "mfma", 2: "exact"}
 
 
+def _attn_bwd_route(entry, cores, *shape):
+    return cores[getattr(lib(), entry + "_route")(*shape)]
+
+
 def qkv_attn_bias_bwd_route(n, s, h, a, dtype=BF16):
     """The core modcr_qkv_attn_bias_bwd runs for this shape (nothing is launched): "mfma", "exact" or "refused"."""
-    return ATTN_BIAS_BWD_CORES[lib().modcr_qkv_attn_bias_bwd_route(n, s, h, a, dtype)]
+    return _attn_bwd_route("modcr_qkv_attn_bias_bwd", ATTN_BIAS_BWD_CORES, n, s, h, a, dtype)
 
 
 def qkv_attn_prefix_bwd_route(n, s, p, h, a, dtype=BF16):
     """The core modcr_qkv_attn_prefix_bwd runs for this shape (nothing is launched): "mfma", "exact" or "refused"."""
-    return ATTN_BIAS_BWD_CORES[lib().modcr_qkv_attn_prefix_bwd_route(n, s, p, h, a, dtype)]
+    return _attn_bwd_route("modcr_qkv_attn_prefix_bwd", ATTN_BIAS_BWD_CORES, n, s, p, h, a, dtype)
 
 
 def qkv_attn_gate_bwd_route(n, s, p, h, a, dtype=BF16):
     """The core modcr_qkv_attn_gate_bwd runs for this shape, p >= 0 prefix rows (nothing is launched): "mfma", "exact" or "refused"."""
-    return ATTN_BIAS_BWD_CORES[lib().modcr_qkv_attn_gate_bwd_route(n, s, p, h, a, dtype)]
+    return _attn_bwd_route("modcr_qkv_attn_gate_bwd", ATTN_BIAS_BWD_CORES, n, s, p, h, a, dtype)
 
 
 def _attn_bias_bwd_operands(who, x, hist, attn_bias, head_mask, d_bias, d_head_mask, a, max_keys):
@@ -1124,47 +1128,49 @@ def _attn_bias_bwd_operands(who, x, hist, attn_bias, head_mask, d_bias, d_head_m
     return p, bias, strides, hm, hsn
 
 
+# The bias family's four C entries take the same operands by name; each lacks some.  Their argument order, as include/modcr_hip.h has it:
+_GATE_BWD_ARGS = ("dctx", "x", "hist", "wqkv", "bqkv", "bias", "bsn", "bsa", "bsq", "hm", "hsn", "chunk_id", "chunk_t", "res", "dx", "d_hist",
+                  "dwqkv", "dbqkv", "accumulate", "d_bias", "d_head_mask", "n", "s", "p", "h", "a", "ap", "seed", "off", "ws", "need", "dt", "stream")
+_ATTN_BIAS_BWD_ARGS = {
+    "bias": tuple(k for k in _GATE_BWD_ARGS if k not in ("hist", "d_hist", "d_head_mask", "p")),
+    "prefix": tuple(k for k in _GATE_BWD_ARGS if k not in ("chunk_id", "chunk_t", "d_head_mask")),
+    "gate": _GATE_BWD_ARGS,
+    "long": _GATE_BWD_ARGS,
+}
+
+
 def _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, a, accumulate, attn_dropout, dx_residual,
-                       d_head_mask=None):
-    """qkv_attn_bwd with attn_bias / head_mask: modcr_qkv_attn_bias_bwd -> dx, or with hist modcr_qkv_attn_prefix_bwd -> (dx, d_hist);
-    with d_head_mask modcr_qkv_attn_gate_bwd for both"""
+                       d_head_mask=None, long=False):
+    """The bias family of the attention backward, one marshalling path for its four C entries: long (qkv_attn_long_bwd) ->
+    modcr_qkv_attn_long_bwd, else with d_head_mask -> modcr_qkv_attn_gate_bwd, else with hist -> modcr_qkv_attn_prefix_bwd, else
+    modcr_qkv_attn_bias_bwd.  Returns dx, or (dx, d_hist) with hist."""
+    who = "qkv_attn_long_bwd" if long else "qkv_attn_bwd"
     dt = dt_of(x)
     n, s, h = x.shape
-    p, bias, (bsn, bsa, bsq), hm, hsn = _attn_bias_bwd_operands("qkv_attn_bwd", x, hist, attn_bias, head_mask, d_bias, d_head_mask, a, ATTN_BWD_MAX_KEYS)
+    p, bias, (bsn, bsa, bsq), hm, hsn = _attn_bias_bwd_operands(who, x, hist, attn_bias, head_mask, d_bias, d_head_mask, a,
+                                                                ATTN_BWD_LONG_MAX_KEYS if long else ATTN_BWD_MAX_KEYS)
+    ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
+    if long and p + s > ATTN_BWD_MAX_KEYS and ap > 0:
+        raise ValueError("%s: attention-probability dropout (p=%g) is not implemented above %d keys (P + S = %d)" % (who, ap, ATTN_BWD_MAX_KEYS, p + s))
+    entry = "long" if long else "gate" if d_head_mask is not None else "prefix" if p else "bias"
+    fn, ws_fn = {"bias": (lib().modcr_qkv_attn_bias_bwd, lib().modcr_qkv_attn_bias_bwd_workspace),
+                 "prefix": (lib().modcr_qkv_attn_prefix_bwd, lib().modcr_qkv_attn_prefix_bwd_workspace),
+                 "gate": (lib().modcr_qkv_attn_gate_bwd, lib().modcr_qkv_attn_gate_bwd_workspace),
+                 "long": (lib().modcr_qkv_attn_long_bwd, lib().modcr_qkv_attn_long_bwd_workspace)}[entry]
     x, dctx = _contig(x), _contig(dctx)
     dx = torch.empty_like(x)
-    res = _contig(dx_residual, torch.float32) if dx_residual is not None else None
-    ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
-    if d_head_mask is not None:
-        hist = _contig(hist) if p else None
-        d_hist = torch.empty_like(hist) if p else None
-        need = lib().modcr_qkv_attn_gate_bwd_workspace(n, s, p, h, dt)
-        ws = _workspace("attn_bwd", need, x.device)
-        chunk_t = 0 if chunk_id is None else chunk_id.shape[1]
-        _check(lib().modcr_qkv_attn_gate_bwd(_ptr(dctx), _ptr(x), _ptr(hist), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq,
-                                             _ptr(hm), hsn, _ptr(chunk_id), chunk_t, _ptr(res), _ptr(dx), _ptr(d_hist), _ptr(dwqkv), _ptr(dbqkv),
-                                             1 if accumulate else 0, _ptr(d_bias), _ptr(d_head_mask), n, s, p, h, a, float(ap), seed, off,
-                                             _ptr(ws), need, dt, _stream()),
-               "modcr_qkv_attn_gate_bwd")
-        return (dx, d_hist) if p else dx
-    if p:
-        hist = _contig(hist)
-        d_hist = torch.empty_like(hist)
-        need = lib().modcr_qkv_attn_prefix_bwd_workspace(n, s, p, h, dt)
-        ws = _workspace("attn_bwd", need, x.device)
-        _check(lib().modcr_qkv_attn_prefix_bwd(_ptr(dctx), _ptr(x), _ptr(hist), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq,
-                                               _ptr(hm), hsn, _ptr(res), _ptr(dx), _ptr(d_hist), _ptr(dwqkv), _ptr(dbqkv), 1 if accumulate else 0,
-                                               _ptr(d_bias), n, s, p, h, a, float(ap), seed, off, _ptr(ws), need, dt, _stream()),
-               "modcr_qkv_attn_prefix_bwd")
-        return dx, d_hist
-    need = lib().modcr_qkv_attn_bias_bwd_workspace(n, s, h, dt)
-    ws = _workspace("attn_bwd", need, x.device)
-    chunk_t = 0 if chunk_id is None else chunk_id.shape[1]
-    _check(lib().modcr_qkv_attn_bias_bwd(_ptr(dctx), _ptr(x), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq, _ptr(hm), hsn,
-                                         _ptr(chunk_id), chunk_t, _ptr(res), _ptr(dx), _ptr(dwqkv), _ptr(dbqkv), 1 if accumulate else 0, _ptr(d_bias),
-                                         n, s, h, a, float(ap), seed, off, _ptr(ws), need, dt, _stream()),
-           "modcr_qkv_attn_bias_bwd")
-    return dx
+    hist = _contig(hist) if p else None
+    d_hist = torch.empty_like(hist) if p else None
+    need = ws_fn(n, s, h, dt) if entry == "bias" else ws_fn(n, s, p, h, dt)
+    tensors = dict(dctx=dctx, x=x, hist=hist, wqkv=_contig(wqkv), bqkv=bqkv, bias=bias, hm=hm, chunk_id=chunk_id, dx=dx, d_hist=d_hist, dwqkv=dwqkv,
+                   dbqkv=dbqkv, d_bias=d_bias, d_head_mask=d_head_mask, ws=_workspace("attn_bwd", need, x.device),
+                   res=_contig(dx_residual, torch.float32) if dx_residual is not None else None)
+    v = dict(n=n, s=s, p=p, h=h, a=a, dt=dt, bsn=bsn, bsa=bsa, bsq=bsq, hsn=hsn, ap=float(ap), seed=seed, off=off, need=need,
+             chunk_t=0 if chunk_id is None else chunk_id.shape[1], accumulate=1 if accumulate else 0)
+    v.update((k, _ptr(t)) for k, t in tensors.items())          # (a tensor that is not on the GPU is refused here, before the stream is asked for)
+    v["stream"] = _stream()
+    _check(fn(*[v[k] for k in _ATTN_BIAS_BWD_ARGS[entry]]), "modcr_qkv_attn_%s_bwd" % entry)
+    return (dx, d_hist) if p else dx
 
 
 ATTN_BWD_LONG_MAX_KEYS = 512
@@ -1174,7 +1180,7 @@ ATTN_LONG_BWD_CORES = {0: "refused", 1: "mfma", 2: "exact", 3: "stream", 4: "str
 def qkv_attn_long_bwd_route(n, s, p, h, a, dtype=BF16):
     """The core modcr_qkv_attn_long_bwd runs for this shape, p >= 0 prefix rows (nothing is launched): "mfma" / "exact" (P + S <= 256,
     modcr_qkv_attn_gate_bwd's), "stream" / "stream-exact" (256 < P + S <= 512, csrc/attn_long_bwd.hip) or "refused"."""
-    return ATTN_LONG_BWD_CORES[lib().modcr_qkv_attn_long_bwd_route(n, s, p, h, a, dtype)]
+    return _attn_bwd_route("modcr_qkv_attn_long_bwd", ATTN_LONG_BWD_CORES, n, s, p, h, a, dtype)
 
 
 def qkv_attn_long_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, chunk_id=None, num_heads=None, accumulate=False, attn_dropout=None,
@@ -1189,33 +1195,8 @@ def qkv_attn_long_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, chunk_id
         if attn_bias is not None:
             raise ValueError("qkv_attn_long_bwd: attn_bias replaces key_mask")
         attn_bias = fold_key_mask(key_mask)
-    return _qkv_attn_long_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, num_heads, accumulate,
-                              attn_dropout, dx_residual, d_head_mask)
-
-
-def _qkv_attn_long_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, a, accumulate, attn_dropout, dx_residual,
-                       d_head_mask):
-    who = "qkv_attn_long_bwd"
-    dt = dt_of(x)
-    n, s, h = x.shape
-    p, bias, (bsn, bsa, bsq), hm, hsn = _attn_bias_bwd_operands(who, x, hist, attn_bias, head_mask, d_bias, d_head_mask, a, ATTN_BWD_LONG_MAX_KEYS)
-    ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
-    if p + s > ATTN_BWD_MAX_KEYS and ap > 0:
-        raise ValueError("%s: attention-probability dropout (p=%g) is not implemented above %d keys (P + S = %d)" % (who, ap, ATTN_BWD_MAX_KEYS, p + s))
-    x, dctx = _contig(x), _contig(dctx)
-    dx = torch.empty_like(x)
-    res = _contig(dx_residual, torch.float32) if dx_residual is not None else None
-    hist = _contig(hist) if p else None
-    d_hist = torch.empty_like(hist) if p else None
-    need = lib().modcr_qkv_attn_long_bwd_workspace(n, s, p, h, dt)
-    ws = _workspace("attn_bwd", need, x.device)
-    chunk_t = 0 if chunk_id is None else chunk_id.shape[1]
-    _check(lib().modcr_qkv_attn_long_bwd(_ptr(dctx), _ptr(x), _ptr(hist), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq,
-                                         _ptr(hm), hsn, _ptr(chunk_id), chunk_t, _ptr(res), _ptr(dx), _ptr(d_hist), _ptr(dwqkv), _ptr(dbqkv),
-                                         1 if accumulate else 0, _ptr(d_bias), _ptr(d_head_mask), n, s, p, h, a, float(ap), seed, off,
-                                         _ptr(ws), need, dt, _stream()),
-           "modcr_qkv_attn_long_bwd")
-    return (dx, d_hist) if p else dx
+    return _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, num_heads, accumulate,
+                              attn_dropout, dx_residual, d_head_mask, long=True)
 
 
 def fold_key_mask(key_mask):

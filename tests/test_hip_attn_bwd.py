@@ -176,7 +176,7 @@ def test_attn_bwd5_vs_oracle(mh, s, t, mask, chunk, p):
                                               (230, 194, "key", False, 0.0)])
 def test_attn_bwd_on_the_256_token_tile_with_attention_dropout(mh, s, t, mask, chunk, p):
     """192 < S <= 256 (BASELINE config 5's S = 230 with trainable encoders, VERDICT r03 missing 3): the forward runs the 256-token
-    tile kernel with its attention-probability dropout, the backward the exact core (csrc/attn.hip attn_bwd_f32_kernel), which
+    tile kernel with its attention-probability dropout, the backward the exact core (csrc/attn_bwd_older.hip attn_bwd_f32_kernel), which
     regenerates the forward's mask from the counter layout of csrc/attn_common.h (LP = 256) -- against torch autograd of the
     reference formula with the mask restated on the host."""
     n, h, a = 2, 256, 4
