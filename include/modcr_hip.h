@@ -125,7 +125,7 @@ int modcr_qkv_attn_opt_fwd(const void* x, const void* hist, const void* wqkv, co
  *   head_mask fp32, element (n, a) at head_mask[n head_mask_stride_n + a] (stride 0 = one [A] vector for every sequence):
  *             multiplies the head's probabilities after softmax and dropout -- its 64 context columns, probs and align_map.
  *             NULL = 1.  bias and head_mask may not both be NULL (that call is modcr_qkv_attn_opt_fwd).
- *   attn_p > 0 (P + S <= 256 only, MODCR_ERR_UNSUPPORTED above): the keep decisions every other route makes for the same
+ *   attn_p > 0 (P + S <= 256 only, MODCR_ERR_UNSUPPORTED above; modcr_qkv_attn_long_drop_fwd goes on to 512): the keep decisions every other route makes for the same
  *             (seed, offset); the context uses P o m / (1 - p), the side outputs the un-dropped probabilities, or with
  *             MODCR_ATTN_SIDE_POST_DROPOUT the post-dropout ones.
  *   chunk_id / ctx / probs / align_map / align_t: as modcr_qkv_attn_fwd.  No lse, no qkv_dump; the backward is
@@ -140,6 +140,22 @@ int modcr_qkv_attn_bias_fwd(const void* x, const void* hist, const void* wqkv, c
                             void* ctx, float* probs, float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P,
                             int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
                             void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
+/* modcr_qkv_attn_bias_fwd with attention-probability dropout above 256 keys (opt-in: training a batch padded past 256 keys under the
+ * reference's live nn.Dropout).  The arguments are modcr_qkv_attn_bias_fwd's, in its order; the workspace is
+ * modcr_qkv_attn_bias_workspace.
+ *   P + S <= 256 or attn_p = 0: the call IS modcr_qkv_attn_bias_fwd -- same bits, same codes, same messages.
+ *   256 < P + S <= 512 and attn_p > 0: the streaming core's dropout instantiations under the WIDE counter layout: the counter row
+ *             of (sequence n, head a, query q) is (n A + a) 512 + q instead of (n A + a) 256 + q, a row has up to 64 words; l4, the
+ *             word index 2 (key >> 4) + ((key >> 1) & 1), the multipliers, the fold, the key of (seed, offset), the threshold and
+ *             1 / (1 - p) are those of every other route.  probs / align_map: the un-dropped probabilities, or with
+ *             MODCR_ATTN_SIDE_POST_DROPOUT the post-dropout ones.  The counter is 32 bits: N * A > 2^21 returns MODCR_ERR_INVALID.
+ * The backward is modcr_qkv_attn_long_drop_bwd. */
+int modcr_qkv_attn_long_drop_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                                 const float* bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                                 const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
+                                 void* ctx, float* probs, float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P,
+                                 int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
+                                 void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
 /* The forward over the LIVE-ROW layout of a frozen encoder pass.  Sequence n keeps only its first L_n rows (1 <= L_n <= S: the
  * rows behind them are padded image regions -- keys that every mask hides, queries that no consumer reads), and the kept rows of
  * all sequences lie back to back:
@@ -534,7 +550,7 @@ int modcr_qkv_attn_gate_bwd(const void* dctx, const void* x, const void* hist, c
  *             query kernel (row statistics, then dS / d_bias / dQ per 64-query block) and a key kernel (dK | dV per 64-key block).
  *             d_bias, d_head_mask, -inf entries, all -inf rows and head_mask = 0 behave as documented for the entries above; every
  *             output element is written by exactly one lane, no atomics, repeated calls are bit-identical.  No attention-probability
- *             dropout there: attn_p > 0 returns MODCR_ERR_UNSUPPORTED (the dropout counter of a head ends at 256 queries).
+ *             dropout from this entry there: attn_p > 0 returns MODCR_ERR_UNSUPPORTED (modcr_qkv_attn_long_drop_bwd carries it).
  *             The workspace is the gate entry's layout followed by the per-row statistics, fp32 [N A][3][S rounded up to 64].
  *   P + S > 512 returns MODCR_ERR_UNSUPPORTED.
  * modcr_qkv_attn_long_bwd_route: 0 = refused, 1 = MFMA core, 2 = exact core (both as modcr_qkv_attn_gate_bwd_route), 3 = streaming
@@ -549,6 +565,23 @@ int modcr_qkv_attn_long_bwd(const void* dctx, const void* x, const void* hist, c
                             float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
                             uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
                             modcr_stream_t stream);
+/* modcr_qkv_attn_long_bwd with attention-probability dropout above 256 keys: the backward of modcr_qkv_attn_long_drop_fwd.  The
+ * arguments are modcr_qkv_attn_long_bwd's, in its order; _workspace and _route answer what that entry's answer (codes 0-4).
+ *   P + S <= 256 or attn_p = 0: the call IS modcr_qkv_attn_long_bwd -- same body, same bits, same codes, same messages.
+ *   256 < P + S <= 512 and attn_p > 0: the streaming cores' DROP instantiations regenerate the forward's keep mask m from (seed,
+ *             offset) under the wide counter layout (row (n A + a) 512 + q) in the query kernel and again in the key kernel --
+ *             nothing of it is stored.  With P~ = P o m / (1 - p): D_i = dctx_i . (P~.V)_i (what d_head_mask sums),
+ *             dP = (dctx.V^T) o m / (1 - p), dS' = P o (dP - D), dV = P~^T.dO; d_bias, dQ, dK follow from dS'.  One lane per output
+ *             element, no atomics, repeated calls bit-identical.  N * A > 2^21 returns MODCR_ERR_INVALID. */
+int64_t modcr_qkv_attn_long_drop_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype);
+int modcr_qkv_attn_long_drop_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype);
+int modcr_qkv_attn_long_drop_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                                 const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                                 const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
+                                 const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv, int32_t accumulate,
+                                 float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
+                                 uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                                 modcr_stream_t stream);
 
 /* ---- backward of the encoder layer's GEMM blocks (autograd of BertSelfOutput / BertIntermediate / BertOutput,
  * a_bert:362-373, :425-437, :440-451).  Gradients of parameters are fp32; dgamma / dbeta are ACCUMULATED (caller

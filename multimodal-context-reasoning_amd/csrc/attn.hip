@@ -413,7 +413,7 @@ __global__ __launch_bounds__(NW * HPW * 64, OCC) void qkv_attn_bf16_kernel(AttnA
                 // 0-3 / 4-7 of pb are keys 32 kt + 16 s2 + 4 h + 0..3 and + 8, i.e. the l4 groups h and h + 2 of the 16-key
                 // block 2 kt + s2 of this lane's query (mask layout: attn_common.h)
                 u32x4_t w = __builtin_bit_cast(u32x4_t, pb);
-                const uint32_t row = (uint32_t)((n * p.A + a) * 256 + qi);
+                const uint32_t row = (uint32_t)((n * p.A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + qi);
                 const uint32_t b0 = attn_drop_base(row, (uint32_t)h, p.drop_key), b1 = attn_drop_base(row, (uint32_t)(h + 2), p.drop_key);
                 const int j0 = (2 * kt + s2) * 2;
                 w[0] &= attn_keep2(attn_drop_word(b0, j0, p.drop_key), p.drop_thr2);
@@ -732,7 +732,7 @@ __device__ __attribute__((noinline)) void attn4_exact_tail(unsigned char* smem, 
     }
     uint32_t dbase[NQB];                                    // dropout bases of this lane's query rows (attn_common.h)
 #pragma unroll
-    for (int qb = 0; qb < NQB; ++qb) dbase[qb] = attn_drop_base((uint32_t)((n * A + a) * 256 + qbase + qb * 16 + l15 - P), (uint32_t)l4, drop_key);
+    for (int qb = 0; qb < NQB; ++qb) dbase[qb] = attn_drop_base((uint32_t)((n * A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + qbase + qb * 16 + l15 - P), (uint32_t)l4, drop_key);
     float mx[NQB], ls[NQB], inv[NQB];
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) {
@@ -1327,7 +1327,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn4_kernel(AttnArgs p) {
         if constexpr (DROP) {
             asm volatile("" : "+v"(dkey));
 #pragma unroll
-            for (int qb = 0; qb < NQB; ++qb) dbase[qb] = attn_drop_base((uint32_t)((n * p.A + a) * 256 + qbase + qb * 16 + l15b - P), (uint32_t)l4b, dkey);
+            for (int qb = 0; qb < NQB; ++qb) dbase[qb] = attn_drop_base((uint32_t)((n * p.A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + qbase + qb * 16 + l15b - P), (uint32_t)l4b, dkey);
         }
         f32x4 ol[NQB];
 #pragma unroll
@@ -1689,7 +1689,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(AttnF32Args p) {
                 float pd = pj;                              // after nn.Dropout (modeling_bert.py:69): what multiplies V
                 if (p.drop_thr16) {
                     uint32_t hx, hy;
-                    attn_drop_words((uint32_t)((n * p.A + a) * 256 + i), j >> 2, p.drop_key, hx, hy);
+                    attn_drop_words((uint32_t)((n * p.A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + i), j >> 2, p.drop_key, hx, hy);
                     pd = attn_keep_field(hx, hy, j & 3, p.drop_thr16) ? pj * p.drop_keep : 0.f;
                 }
                 sP[wave * L + j] = pd;
@@ -1738,6 +1738,7 @@ namespace {
 struct AttnCall {
     const char* who;
     int32_t present, chunk_t, align_t, N, S, P, H, A; float attn_p; int32_t flags; int64_t ws_bytes; bool ws_aligned16; int32_t dtype;
+    bool wide_dropout = false;      // attention dropout above 256 keys is served (modcr_qkv_attn_long_drop_fwd: the wide counter layout)
 };
 
 int attn_present(const void* dense_mask_bits, const void* chunk_id, const void* probs, const void* align_map, const void* lse, const void* qkv_dump) {
@@ -1756,11 +1757,14 @@ int attn_fwd_setup(const AttnCall& c, bool given, bool has_hist, bool aligned16)
     MODCR_REQUIRE(c.N > 0 && c.S > 0 && c.P >= 0 && c.A > 0, "%s: bad shape", who);
     MODCR_REQUIRE(c.H == c.A * 64, "%s: head size must be 64 (H=%d, A=%d)", who, c.H, c.A);
     const int L = c.P + c.S;
-    if (L > 512 || (c.attn_p > 0.f && L > 256)) {
+    if (L > 512 || (c.attn_p > 0.f && L > 256 && !c.wide_dropout)) {
         if (L > 512) modcr_set_error("%s: P+S=%d exceeds the 512-key limit of the attention forward", who, L);
         else modcr_set_error("%s: attention-probability dropout (p=%g) is not implemented above 256 keys (P+S=%d)", who, c.attn_p, L);
         return MODCR_ERR_UNSUPPORTED;
     }
+    // (the wide counter layout: (n A + head) x 512 rows x 4 counters in 32 bits)
+    MODCR_REQUIRE(!(c.attn_p > 0.f && L > 256) || (int64_t)c.N * c.A <= ATTN_DROP_WIDE_MAX_NA,
+                  "%s: N * A = %lld (N=%d, A=%d) exceeds the 2^21 (sequence, head) pairs of the wide dropout counter", who, (long long)c.N * c.A, c.N, c.A);
     // (above 256 keys the binary-mask entries have only ever asked whether p > 0: anything else is "no dropout" there)
     MODCR_REQUIRE((L > 256 && !bias) || (c.attn_p >= 0.f && c.attn_p < 1.f), "%s: attention dropout p=%g out of [0, 1)", who, c.attn_p);
     MODCR_REQUIRE(c.P == 0 || has_hist, "%s: P=%d but hist is null", who, c.P);
@@ -1781,10 +1785,10 @@ int attn_opt_checks(const AttnCall& c, bool has_mask, bool dump_aligned16) {
 }
 
 // modcr_qkv_attn_bias_fwd's own checks (b: its bias / head_mask arguments)
-int attn_bias_checks(const AttnLongArgs& b) {
-    MODCR_REQUIRE(b.bias || b.head_mask, "qkv_attn_bias_fwd: neither bias nor head_mask (that call belongs to modcr_qkv_attn_opt_fwd)");
-    MODCR_REQUIRE(b.bias_sn >= 0 && b.bias_sa >= 0 && b.bias_sq >= 0 && b.head_mask_sn >= 0, "qkv_attn_bias_fwd: negative stride");
-    MODCR_REQUIRE(((uintptr_t)b.bias & 3) == 0 && ((uintptr_t)b.head_mask & 3) == 0, "qkv_attn_bias_fwd: bias / head_mask not 4-byte aligned");
+int attn_bias_checks(const char* who, const AttnLongArgs& b) {
+    MODCR_REQUIRE(b.bias || b.head_mask, "%s: neither bias nor head_mask (that call belongs to modcr_qkv_attn_opt_fwd)", who);
+    MODCR_REQUIRE(b.bias_sn >= 0 && b.bias_sa >= 0 && b.bias_sq >= 0 && b.head_mask_sn >= 0, "%s: negative stride", who);
+    MODCR_REQUIRE(((uintptr_t)b.bias & 3) == 0 && ((uintptr_t)b.head_mask & 3) == 0, "%s: bias / head_mask not 4-byte aligned", who);
     return MODCR_OK;
 }
 
@@ -1959,13 +1963,16 @@ int attn_fwd(const void* x, const void* hist, const void* wqkv, const float* bqk
              const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs, float* align_map, int32_t align_t, float* lse, void* qkv_dump,
              int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
              void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream, const AttnLongArgs* bias = nullptr,
-             const int32_t* row_start = nullptr) {
-    const AttnCall c = {bias ? "qkv_attn_bias_fwd" : row_start ? "qkv_attn_rows_fwd" : "qkv_attn_fwd",
+             const int32_t* row_start = nullptr, bool wide_dropout = false) {
+    // (wide_dropout: modcr_qkv_attn_long_drop_fwd; it shows, name included, only where it changes the call: dropout above 256 keys)
+    const bool wide = wide_dropout && bias && (int64_t)P + S > 256 && attn_p > 0.f;
+    AttnCall c = {wide ? "qkv_attn_long_drop_fwd" : bias ? "qkv_attn_bias_fwd" : row_start ? "qkv_attn_rows_fwd" : "qkv_attn_fwd",
                         (bias ? MODCR_ATTN_HAS_BIAS : 0) | (row_start ? MODCR_ATTN_HAS_ROW_START : 0) | attn_present(dense_mask_bits, chunk_id, probs, align_map, lse, qkv_dump), chunk_t, align_t,
                         N, S, P, H, A, attn_p, flags, workspace ? workspace_bytes : 0, modcr_aligned16(workspace), dtype};
+    c.wide_dropout = wide;
     int rc = attn_fwd_setup(c, x && wqkv && bqkv && ctx, hist != nullptr,
                             modcr_aligned16(x) && modcr_aligned16(wqkv) && modcr_aligned16(ctx) && (P == 0 || modcr_aligned16(hist)));
-    if (rc == MODCR_OK) rc = bias ? attn_bias_checks(*bias) : attn_opt_checks(c, key_mask || dense_mask_bits, modcr_aligned16(qkv_dump));
+    if (rc == MODCR_OK) rc = bias ? attn_bias_checks(c.who, *bias) : attn_opt_checks(c, key_mask || dense_mask_bits, modcr_aligned16(qkv_dump));
     if (rc != MODCR_OK) return rc;
     const AttnRoute r = attn_fwd_route(c);
     if (r.rc != MODCR_OK) return r.rc;
@@ -2081,6 +2088,22 @@ extern "C" int modcr_qkv_attn_bias_fwd(const void* x, const void* hist, const vo
     b.head_mask = head_mask; b.head_mask_sn = head_mask_stride_n;
     return attn_fwd(x, hist, wqkv, bqkv, nullptr, nullptr, chunk_id, chunk_t, ctx, probs, align_map, align_t, nullptr, nullptr,
                     N, S, P, H, A, attn_p, seed, offset, flags, workspace, workspace_bytes, dtype, stream, &b);
+}
+
+// modcr_qkv_attn_bias_fwd with attention-probability dropout above 256 keys (opt-in): the same arguments, the same workspace
+// (modcr_qkv_attn_bias_workspace).  At P + S <= 256 or attn_p = 0 it is that entry's call; above, MODE 2 of the streaming core runs
+// under the wide counter layout of attn_common.h (row stride 512), N * A <= 2^21.
+extern "C" int modcr_qkv_attn_long_drop_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* bias,
+                                            int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q, const float* head_mask,
+                                            int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
+                                            float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
+                                            uint64_t seed, uint64_t offset, int32_t flags, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                                            modcr_stream_t stream) {
+    AttnLongArgs b = {};
+    b.bias = bias; b.bias_sn = bias_stride_n; b.bias_sa = bias_stride_a; b.bias_sq = bias_stride_q;
+    b.head_mask = head_mask; b.head_mask_sn = head_mask_stride_n;
+    return attn_fwd(x, hist, wqkv, bqkv, nullptr, nullptr, chunk_id, chunk_t, ctx, probs, align_map, align_t, nullptr, nullptr,
+                    N, S, P, H, A, attn_p, seed, offset, flags, workspace, workspace_bytes, dtype, stream, &b, nullptr, true);
 }
 
 extern "C" int modcr_qkv_attn_route(int32_t present, int32_t chunk_t, int32_t align_t, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A,

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(384, 3) void attn_bias_bwd_mfma_kernel(AttnBiasBwdA
             if (l4 == 0) { sM[qrow] = m; sInv[qrow] = inv; }
         }
         // ctx = hm (P o m / (1 - p)) V, so dP = hm m / (1 - p) o (dO V^T); without hm here
-        const uint32_t dbase = attn_drop_base((uint32_t)((n * p.A + a) * 256 + qrow), (uint32_t)l4, p.drop_key);
+        const uint32_t dbase = attn_drop_base((uint32_t)((n * p.A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + qrow), (uint32_t)l4, p.drop_key);
         auto dp_masked = [&](int kt, int kb) {
             const int krow = kt * 32 + kb * 16;
             const bf16x8 fv0 = *reinterpret_cast<const bf16x8*>(img1 + swz128(krow + l15, l4));
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(384, 3) void attn_bias_bwd_mfma_kernel(AttnBiasBwdA
                 // dropout: a lane's four values are four queries of ONE key, four hash counters; each lane of a quad hashes one
                 // and they are exchanged by quad broadcasts (attn_bwd_mfma_kernel)
                 uint32_t hqx = 0, hqy = 0;
-                if (dthr) attn_drop_words((uint32_t)((n * p.A + a) * 256 + qrow + 4 * l4 + (l15 & 3)), key >> 2, p.drop_key, hqx, hqy);
+                if (dthr) attn_drop_words((uint32_t)((n * p.A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + qrow + 4 * l4 + (l15 & 3)), key >> 2, p.drop_key, hqx, hqy);
                 const uint32_t xq[4] = {quad_bcast<0>(hqx), quad_bcast<1>(hqx), quad_bcast<2>(hqx), quad_bcast<3>(hqx)};
                 const uint32_t yq[4] = {quad_bcast<0>(hqy), quad_bcast<1>(hqy), quad_bcast<2>(hqy), quad_bcast<3>(hqy)};
 #pragma unroll
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(256) void attn_bias_bwd_f32_kernel(AttnBiasBwdArgs 
     auto dmask = [&](int i, int j) {        // hm x keep / (1 - p) of weight (query i, key j)
         if (!dthr) return keepv;
         uint32_t hx, hy;
-        attn_drop_words((uint32_t)((n * p.A + a) * 256 + i), j >> 2, p.drop_key, hx, hy);
+        attn_drop_words((uint32_t)((n * p.A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + i), j >> 2, p.drop_key, hx, hy);
         return attn_keep_field(hx, hy, j & 3, dthr) ? keepv : 0.f;
     };
     // DHM: the same weight's factor WITHOUT hm, keep / (1 - p), next to it (one hash for both); keepv stays folded as it is --
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(256) void attn_bias_bwd_f32_kernel(AttnBiasBwdArgs 
         m1 = keep1;
         if (!dthr) return keepv;
         uint32_t hx, hy;
-        attn_drop_words((uint32_t)((n * p.A + a) * 256 + i), j >> 2, p.drop_key, hx, hy);
+        attn_drop_words((uint32_t)((n * p.A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + i), j >> 2, p.drop_key, hx, hy);
         const bool kept = attn_keep_field(hx, hy, j & 3, dthr);
         if (!kept) m1 = 0.f;
         return kept ? keepv : 0.f;

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd5_kernel(AttnBwdArgs p) {
                     // of one key group) need the same four, so each hashes one and they are exchanged by quad broadcasts
                     uint32_t hx, hy;
                     const int qrow = it * 32 + qt * 16 + 4 * g + (l15 & 3), key = krow + l15;
-                    attn_drop_words((uint32_t)((n * p.A + a) * 256 + qrow), key >> 2, p.drop_key, hx, hy);
+                    attn_drop_words((uint32_t)((n * p.A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + qrow), key >> 2, p.drop_key, hx, hy);
                     const uint32_t xq[4] = {quad_bcast<0>(hx), quad_bcast<1>(hx), quad_bcast<2>(hx), quad_bcast<3>(hx)};
                     const uint32_t yq[4] = {quad_bcast<0>(hy), quad_bcast<1>(hy), quad_bcast<2>(hy), quad_bcast<3>(hy)};
 #pragma unroll
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(256) void attn_dalign_delta_kernel(AttnBwdArgs p, i
             const int q = qt * 16 + 4 * g4 + e;
             nl[e] = q < T ? -p.lse[(int64_t)tile * S + q] : -INFINITY;
             acc[e] = 0.f;
-            dbase[e] = post ? attn_drop_base((uint32_t)(tile * 256 + q), (uint32_t)(l15 >> 2), p.drop_key) : 0u;
+            dbase[e] = post ? attn_drop_base((uint32_t)(tile * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + q), (uint32_t)(l15 >> 2), p.drop_key) : 0u;
         }
         for (int kt = T >> 4; kt * 16 < S; ++kt) {
             const int key = kt * 16 + l15, kc = min(key, S - 1);
@@ -616,7 +616,7 @@ __global__ __launch_bounds__((64 * KT / 16 + 4) * 64) void attn_bwd6_kernel(Attn
         fk1 = *reinterpret_cast<const bf16x8*>(sK + aRow1 + key0 * 128);
         // dropout (attn_common.h): Weyl product of the base counter of (query 4 g4 + (l15 & 3), this lane's l4 group) + per-block
         // strides below; the two word multipliers of this wave's 16-key block
-        const uint32_t cm0 = (uint32_t)((((n * A + a) * 256 + 4 * g4 + (l15 & 3)) * 4) + (((key0 + l15) >> 2) & 3)) * MODCR_DROP_WEYL;
+        const uint32_t cm0 = (uint32_t)((((n * A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + 4 * g4 + (l15 & 3)) * 4) + (((key0 + l15) >> 2) & 3)) * MODCR_DROP_WEYL;
         const uint32_t cm16 = (uint32_t)(16 * 4) * MODCR_DROP_WEYL;                     // 16 queries further
         const uint32_t dcx = attn_drop_const((key0 >> 4) * 2), dcy = attn_drop_const((key0 >> 4) * 2 + 1);
         bf16x8 nv0, nv1;                                    // the next tile's V rows / key mask, loaded under the last block

@@ -1,6 +1,7 @@
-// Host side of the attention backward (CDNA4 / gfx950): the eight entries modcr_qkv_attn_bwd, _dropout_bwd, _lse_bwd, _opt_bwd (the mask
-// family: key_mask / dense bits, S <= 256, no prefix rows) and _bias_bwd, _prefix_bwd, _gate_bwd, _long_bwd (the bias family: additive
-// bias and / or head mask, P >= 0 prefix rows, P + S <= 256, or <= 512 from _long_bwd), their _workspace and _route companions.
+// Host side of the attention backward (CDNA4 / gfx950): the nine entries modcr_qkv_attn_bwd, _dropout_bwd, _lse_bwd, _opt_bwd (the mask
+// family: key_mask / dense bits, S <= 256, no prefix rows) and _bias_bwd, _prefix_bwd, _gate_bwd, _long_bwd, _long_drop_bwd (the bias
+// family: additive bias and / or head mask, P >= 0 prefix rows, P + S <= 256, or <= 512 from _long_bwd -- without attention dropout
+// above 256 keys -- and _long_drop_bwd -- with it, the wide counter layout), their _workspace and _route companions.
 // No kernel lives here: the cores are in attn_bwd.hip (five-product), attn_bwd_older.hip (older MFMA, exact), attn_bias_bwd.hip (bias MFMA, bias exact) and
 // attn_long_bwd.hip (stream, stream exact), behind the four launchers of attn_common.h.
 //
@@ -22,7 +23,8 @@ namespace {
 struct AttnBwdCall {
     const char* who;                // the entry's name in the bias family's messages (the mask family's all say qkv_attn_bwd)
     bool bias_family;
-    int max_keys;                   // bias family: 256, or 512 from modcr_qkv_attn_long_bwd
+    int max_keys;                   // bias family: 256, or 512 from modcr_qkv_attn_long_bwd / _long_drop_bwd
+    bool wide_dropout;              // bias family: attention dropout above 256 keys is served (modcr_qkv_attn_long_drop_bwd: the wide counter layout)
     const void* dctx; const void* x; const void* hist; const void* wqkv; const float* bqkv;
     const float* key_mask; const uint32_t* bits;                                            // mask family
     const float* bias; int64_t bias_sn, bias_sa, bias_sq; const float* head_mask; int64_t head_mask_sn;    // bias family
@@ -127,10 +129,13 @@ int attn_bwd_bias_checks(const AttnBwdCall& c, AttnBwdWs& ws, AttnBwdCore& core)
         modcr_set_error("%s: P + S = %lld keys (P=%d) exceeds the %d-key limit of the attention backward", who, (long long)P + S, P, c.max_keys);
         return MODCR_ERR_UNSUPPORTED;
     }
-    if ((int64_t)P + S > 256 && c.attn_p > 0.f) {
+    if ((int64_t)P + S > 256 && c.attn_p > 0.f && !c.wide_dropout) {
         modcr_set_error("%s: attention-probability dropout (p=%g) is not implemented above 256 keys (P+S=%d)", who, c.attn_p, P + S);
         return MODCR_ERR_UNSUPPORTED;
     }
+    // (the wide counter layout: (n A + head) x 512 rows x 4 counters in 32 bits)
+    MODCR_REQUIRE(!((int64_t)P + S > 256 && c.attn_p > 0.f) || (int64_t)N * A <= ATTN_DROP_WIDE_MAX_NA,
+                  "%s: N * A = %lld (N=%d, A=%d) exceeds the 2^21 (sequence, head) pairs of the wide dropout counter", who, (long long)N * A, N, A);
     // (with d_head_mask a missing head_mask is a mask of ones: the head-importance call)
     MODCR_REQUIRE(c.bias || c.head_mask || c.d_head_mask, "%s: neither bias nor head_mask%s", who,
                   P ? "" : " (that call belongs to modcr_qkv_attn_opt_bwd)");
@@ -420,6 +425,34 @@ extern "C" int modcr_qkv_attn_long_bwd(const void* dctx, const void* x, const vo
                                    bias_stride_q, head_mask, head_mask_stride_n, dx_residual, dx, dwqkv, dbqkv, accumulate, d_bias, N, S, H, A, attn_p,
                                    seed, offset, workspace, workspace_bytes, dtype, stream);
     c.max_keys = 512;
+    c.hist = hist; c.d_hist = d_hist; c.P = P; c.chunk_id = chunk_id; c.chunk_t = chunk_t; c.d_head_mask = d_head_mask;
+    const int rc = attn_gate_precheck(c);
+    return rc != MODCR_OK ? rc : attn_bwd(c);
+}
+
+// ---- modcr_qkv_attn_long_drop_bwd: modcr_qkv_attn_long_bwd with attention-probability dropout above 256 keys (opt-in; the DROP cores) ----
+extern "C" int64_t modcr_qkv_attn_long_drop_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
+    return modcr_qkv_attn_long_bwd_workspace(N, S, P, H, dtype);
+}
+
+extern "C" int modcr_qkv_attn_long_drop_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype) {
+    return attn_bias_bwd_route(N, S, P, H, A, dtype, 512);
+}
+
+extern "C" int modcr_qkv_attn_long_drop_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                                            const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                                            const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
+                                            const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv, int32_t accumulate,
+                                            float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
+                                            uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                                            modcr_stream_t stream) {
+    // at P + S <= 256 or attn_p = 0 this is modcr_qkv_attn_long_bwd's call, by its names in the messages too; above, step 3 runs the
+    // streaming cores' DROP instantiations under the wide counter layout (attn_common.h) -- same workspace, same route
+    const bool wide = (int64_t)P + S > 256 && attn_p > 0.f;
+    AttnBwdCall c = attn_bias_call(wide ? "qkv_attn_long_drop_bwd" : (int64_t)P + S <= 256 ? "qkv_attn_gate_bwd" : "qkv_attn_long_bwd", dctx, x, wqkv, bqkv,
+                                   attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask, head_mask_stride_n, dx_residual, dx, dwqkv, dbqkv,
+                                   accumulate, d_bias, N, S, H, A, attn_p, seed, offset, workspace, workspace_bytes, dtype, stream);
+    c.max_keys = 512; c.wide_dropout = true;
     c.hist = hist; c.d_hist = d_hist; c.P = P; c.chunk_id = chunk_id; c.chunk_t = chunk_t; c.d_head_mask = d_head_mask;
     const int rc = attn_gate_precheck(c);
     return rc != MODCR_OK ? rc : attn_bwd(c);

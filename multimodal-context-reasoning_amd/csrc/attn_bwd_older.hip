@@ -188,7 +188,7 @@ __global__ __launch_bounds__(384, 3) void attn_bwd_mfma_kernel(AttnBwdArgs p) {
             }
             // forward dropout on the probabilities: O = (P o m) V with m = keep / (1 - p), so dP = m o (dO V^T) below
             const uint32_t dthr = p.drop_thr16;
-            const uint32_t dbase = attn_drop_base((uint32_t)((n * p.A + a) * 256 + qrow), (uint32_t)l4, p.drop_key);
+            const uint32_t dbase = attn_drop_base((uint32_t)((n * p.A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + qrow), (uint32_t)l4, p.drop_key);
             auto dp_masked = [&](int kt, int kb) {
                 const int krow = kt * 32 + kb * 16;
                 const bf16x8 fv0 = *reinterpret_cast<const bf16x8*>(img1 + swz128(krow + l15, l4));
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(384, 3) void attn_bwd_mfma_kernel(AttnBwdArgs p) {
                     // exchanged by quad broadcasts: one hash per lane instead of four
                     uint32_t hqx = 0, hqy = 0;
                     if (p.drop_thr16)
-                        attn_drop_words((uint32_t)((n * p.A + a) * 256 + qrow + 4 * l4 + (l15 & 3)), key >> 2, p.drop_key, hqx, hqy);
+                        attn_drop_words((uint32_t)((n * p.A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + qrow + 4 * l4 + (l15 & 3)), key >> 2, p.drop_key, hqx, hqy);
                     const uint32_t xq[4] = {quad_bcast<0>(hqx), quad_bcast<1>(hqx), quad_bcast<2>(hqx), quad_bcast<3>(hqx)};
                     const uint32_t yq[4] = {quad_bcast<0>(hqy), quad_bcast<1>(hqy), quad_bcast<2>(hqy), quad_bcast<3>(hqy)};
 #pragma unroll
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(256) void attn_bwd_f32_kernel(AttnBwdArgs p) {
     auto dmask = [&](int i, int j) {
         if (!dthr) return 1.0f;
         uint32_t hx, hy;
-        attn_drop_words((uint32_t)((n * p.A + a) * 256 + i), j >> 2, p.drop_key, hx, hy);
+        attn_drop_words((uint32_t)((n * p.A + a) * attn_drop_stride(ATTN_DROP_NARROW_KEYS) + i), j >> 2, p.drop_key, hx, hy);
         return attn_keep_field(hx, hy, j & 3, dthr) ? p.drop_keep : 0.f;
     };
     // ---- pass A ------------------------------------------------------------------------------------------

@@ -8,15 +8,21 @@
 namespace {
 
 // nn.Dropout on the softmax output (modeling_bert.py:69 / v10:101), counter-based, two levels (round 5):
-//     base(row, l4)  = fold(cm * 0x85EBCA6B + K),  cm = (row * 4 + l4) * 0x9E3779B1 mod 2^32,  row = (n * A + head) * 256 + query
+//     base(row, l4)  = fold(cm * 0x85EBCA6B + K),  cm = (row * 4 + l4) * 0x9E3779B1 mod 2^32,  row = (n * A + head) * R + query
 //     word(base, j)  = fold(base * C[j] + K),      fold(p) = lo32(p) ^ hi32(p) of the 64-bit sum (one v_mad_u64_u32 + one v_xor)
+// R = attn_drop_stride(L) is the row stride of a (sequence, head), chosen per CALL from its key count L = P + S:
+//     L <= 256: R = 256, a row has words j = 0..31 -- every kernel of every file, bit for bit what it has always been;
+//     L >  256: R = 512, a row has words j = 0..63 -- the wide layout of the streaming cores (attn_long.hip MODE 2, attn_long_bwd.hip DROP).
+// With R = 256 the counter of query >= 256 of head a would be the counter of query - 256 of head a + 1; R = 512 keeps the rows of
+// 512 queries apart.  The counter row * 4 + l4 is 32 bits wide: the wide layout takes (n * A + head) < 2^21, which the host checks
+// (N * A <= 2^21) before it launches.
 // K = the 64-bit key derived from (seed, offset) on the host.  Key `key` of a query row takes l4 = (key >> 2) & 3 (its group of
 // four inside a 16-key block), word j = 2 * (key >> 4) + ((key >> 1) & 1) and the 16-bit field key & 1 of it (low / high half);
 // the weight is kept iff that field, read as a signed 16-bit number, is >= thr16 - 32768 with thr16 = round(p * 2^16) -- one
 // saturating packed subtract + arithmetic shift per word gives the 0xffff / 0 keep masks of a packed bf16 pair.
 // C[j] = fmix32((j + 1) * 0x9E3779B1) | 1: a compile-time literal wherever j is (the unrolled key tiles of every MFMA kernel).
-// The layout does not depend on the token tile, so every kernel (128 / 192 / 256-token tiles, the older kernel, the three backward
-// cores) regenerates the same mask for P + S <= 256.
+// The layout does not depend on the token tile, so every kernel (128 / 192 / 256-token tiles, the older kernel, the backward
+// cores) regenerates the same mask for P + S <= 256, and the streaming forward and backward cores the same one above.
 // Why this form: the round-3/4 hash (Weyl product, two xorshift-multiply rounds per group of four keys, 15-bit fields) was 19 VALU
 // instructions per four decisions incl. the compare -- 686 of the ~900 VALU instructions of the forward's phase B, 7 % of the kernel;
 // here a lane's base is hashed once per (query, l4) and tile, and every further word costs two instructions: 10 per eight decisions
@@ -31,11 +37,21 @@ __host__ __device__ constexpr uint32_t attn_drop_const(int j) {
     x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
     return x | 1u;
 }
+// row stride of a (sequence, head) in the counter: 256 up to 256 keys, 512 above (the wide layout).  Kernels that never see more than
+// 256 keys call it with ATTN_DROP_NARROW_KEYS and get the literal.
+constexpr int ATTN_DROP_NARROW_KEYS = 256;
+constexpr int ATTN_DROP_WIDE_KEYS = 512;
+constexpr int64_t ATTN_DROP_WIDE_MAX_NA = 1ll << 21;        // N * A of a wide call: (N A) 512 x 4 counters fit 32 bits
+__host__ __device__ constexpr int attn_drop_stride(int L) { return L > ATTN_DROP_NARROW_KEYS ? ATTN_DROP_WIDE_KEYS : ATTN_DROP_NARROW_KEYS; }
+// the counter row of (sequence n, head, query) in a call of A heads and L keys
+__host__ __device__ constexpr uint32_t attn_drop_row(int n, int A, int head, int query, int L) {
+    return (uint32_t)((n * A + head) * attn_drop_stride(L) + query);
+}
 __device__ __forceinline__ uint32_t attn_drop_fold(uint32_t a, uint32_t c, uint64_t k) {
     const uint64_t p = (uint64_t)a * c + k;
     return (uint32_t)p ^ (uint32_t)(p >> 32);
 }
-// row = (n * A + head) * 256 + query (tile row: prefix rows count), l4 = 0..3
+// row = attn_drop_row(n, A, head, query, L) (tile row: prefix rows count), l4 = 0..3
 __device__ __forceinline__ uint32_t attn_drop_base(uint32_t row, uint32_t l4, uint64_t k) {
     return attn_drop_fold((row * 4u + l4) * MODCR_DROP_WEYL, 0x85EBCA6Bu, k);
 }
@@ -194,7 +210,7 @@ struct AttnBiasBwdArgs {
 };
 // core: 1 = attn_bias_bwd_mfma_kernel (bf16, P + S <= 192), 2 = attn_bias_bwd_f32_kernel (P + S <= 256); prefix rows where b.P > 0
 __attribute__((visibility("hidden"))) int modcr_launch_attn_bias_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype, hipStream_t stream);
-// attn_long_bwd.hip: the streaming cores for P + S <= 512 keys, no dropout; core: 3 = the bf16 MFMA kernels, 4 = the exact fp32 kernels
+// attn_long_bwd.hip: the streaming cores for 256 < P + S <= 512 keys (dropout: the wide counter layout); core: 3 = the bf16 MFMA kernels, 4 = the exact fp32 kernels
 // (fp32 dtype only: its dctx is fp32); b.stats given
 __attribute__((visibility("hidden"))) int modcr_launch_attn_long_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype, hipStream_t stream);
 
@@ -207,7 +223,7 @@ struct AttnLongArgs {
     void* ctx; float* probs; float* align_map;
     int N, S, P, H, A, align_t;
     // bias variant: bias[n sn + a sa + q sq + j] fp32 (strides in elements, 0 = broadcast; NULL = no bias), head_mask[n hsn + a]
-    // (NULL = 1); dropout of the probabilities (P + S <= 256): 0 = off, else thr16 = round(p * 2^16), the 64-bit key, 1 / (1 - p)
+    // (NULL = 1); dropout of the probabilities (counter stride attn_drop_stride(P + S)): 0 = off, else thr16 = round(p * 2^16), the 64-bit key, 1 / (1 - p)
     const float* bias; int64_t bias_sn, bias_sa, bias_sq;
     const float* head_mask; int64_t head_mask_sn;
     uint32_t drop_thr16;

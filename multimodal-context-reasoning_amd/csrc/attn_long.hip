@@ -2,7 +2,8 @@
 //   * 256 < P + S <= 512 keys with a binary mask (key mask / dense mask bits), no attention-probability dropout (inference /
 //     eval mode): modcr_qkv_attn_opt_fwd above the tile kernels' 256 keys;
 //   * any P + S <= 512 with an ADDITIVE fp32 bias per (sequence, head, query, key) and / or a per-head multiplier
-//     (modcr_qkv_attn_bias_fwd): the BIAS instantiations below, see "Bias variant" further down.
+//     (modcr_qkv_attn_bias_fwd; with attention-probability dropout above 256 keys modcr_qkv_attn_long_drop_fwd): the BIAS
+//     instantiations below, see "Bias variant" further down.
 //
 // The tile kernels of attn.hip hold the whole key row of a head in LDS; above 256 keys it does not fit, so this core
 // streams the keys in tiles of 64 with an online softmax (flash-style).  Its inputs are the q | k | v rows the dispatcher
@@ -33,7 +34,8 @@
 // 0 and probabilities 0 -- the one deliberate difference from the reference, whose softmax gives NaN there.  A row of -10000
 // everywhere is the uniform softmax, as on the binary routes.  head_mask[n hsn + a] (NULL = 1) multiplies the head's probabilities
 // after softmax and dropout: the 64 context columns in the epilogue and the side outputs in the second sweep.
-// Dropout (P + S <= 256 only, MODE 2): the keep decisions of attn_common.h for row counter (n A + head) x 256 + query, keys over
+// Dropout (MODE 2): the keep decisions of attn_common.h for row counter attn_drop_row(n, A, head, query, P + S) -- stride 256 up to
+// 256 keys, the wide layout (stride 512, words up to 63) above, which only modcr_qkv_attn_long_drop_fwd lets through -- keys over
 // [prefix ; x]; the lane's g is the layout's l4, so attn_drop8_rt clears the dropped bf16 pairs of the P^T fragments as in the tile
 // kernels.  The context is P o m / (1 - p); the side outputs are the un-dropped probabilities, or with side_post_drop the
 // post-dropout ones (the second sweep regenerates the keep bits).
@@ -219,7 +221,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MODE != 0 ?
     if constexpr (MODE == 2) {
         dthr2 = attn_thrm1_2(p.drop_thr16);
 #pragma unroll
-        for (int qs = 0; qs < 2; ++qs) dbase[qs] = attn_drop_base((uint32_t)((n * p.A + a) * 256 + qrow[qs]), (uint32_t)g, p.drop_key);
+        for (int qs = 0; qs < 2; ++qs) dbase[qs] = attn_drop_base(attn_drop_row(n, p.A, a, qrow[qs], L), (uint32_t)g, p.drop_key);
     }
 
     f32x4 bcur[2][4], bnext[2][4];
@@ -404,7 +406,7 @@ __global__ __launch_bounds__(256) void attn_long_f32_kernel(AttnLongArgs p) {
     [[maybe_unused]] auto keep = [&](int t, int qi) {
         const int j = t * 64 + lane;
         uint32_t hx, hy;
-        attn_drop_words((uint32_t)((n * p.A + a) * 256 + q0 + qi), j >> 2, p.drop_key, hx, hy);
+        attn_drop_words(attn_drop_row(n, p.A, a, q0 + qi, L), j >> 2, p.drop_key, hx, hy);
         return attn_keep_field(hx, hy, j & 3, p.drop_thr16) ? p.drop_keep : 0.f;
     };
 

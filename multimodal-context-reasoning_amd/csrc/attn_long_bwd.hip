@@ -1,7 +1,8 @@
 // Streaming attention core backward (CDNA4 / gfx950; head size 64): the arithmetic of attn_bias_bwd.hip -- additive fp32 bias, head
 // mask, prefix rows, gradient of the head mask -- for S queries against 256 < L = P + S <= 512 keys, where a head's key row no longer
-// fits LDS.  No attention-probability dropout (the dropout counter layout of attn_common.h ends at 256 queries).  Per (sequence n,
-// head a), keys j < P are the prefix rows, keys j >= P the sequence's own rows:
+// fits LDS.  Attention-probability dropout in the DROP instantiations (modcr_qkv_attn_long_drop_bwd): the wide counter layout of
+// attn_common.h (row stride 512), regenerated in both kernels, never stored; see "Dropout" below.  Per (sequence n, head a), keys
+// j < P are the prefix rows, keys j >= P the sequence's own rows:
 //     s_ij = q_i.k_j / 8 + bias[n, a, i, j]     P = softmax_j(s)     ctx = hm[n, a] P.V
 //     dV = hm P^T.dctx     dP = hm (dctx.V^T)     dS = P o (dP - rowsum(dP o P))
 //     dQ = dS.K / 8  [S rows]     dK = dS^T.Q / 8  [L rows]     d_bias = dS  [N, A, S, L]     d_hm[n, a] = sum_i dctx_i . (P.V)_i
@@ -33,6 +34,15 @@
 // pre-scaled: the accumulator takes log2e / 8.
 // fp32 core (core 4): the same tiling with VALU products; the streamed row on the lane for the scores, the feature on the lane for
 // the accumulators.  fp32 rows and fp32 dctx: the host sends every bf16 call above 256 keys to core 3.
+//
+// Dropout (template parameter DROP; the instantiations without it compile as before): with m the forward's keep mask and
+// P~ = P o m / (1 - p),   ctx = hm P~.V,   D_i = dctx_i . (P~.V)_i,   dP = (dctx.V^T) o m / (1 - p),   dS' = P o (dP - D),   dV = P~^T.dO.
+//   query kernel: the query lies on the lane and its g is the layout's l4, so one hash base per lane serves both sweeps; sweep 1
+//     clears the dropped bf16 pairs of the P^T fragments as the forward does (attn_drop8_rt; the row sum keeps the un-dropped
+//     weights) and D takes 1 / (1 - p); sweep 2 multiplies dP by keep / (1 - p) from the two words of each 16-key block.
+//   key kernel: the key lies on the lane, its four values are four QUERIES -- four counter rows, but one l4 and one pair of word
+//     multipliers, fixed for the whole kernel.  Each lane of a quad hashes the row of one of the quad's four queries and the words
+//     travel by quad broadcasts (attn_bias_bwd_mfma_kernel's scheme): three multiply-folds per lane and 16-query block.
 #include "common.h"
 #include "attn_common.h"
 
@@ -66,7 +76,7 @@ __device__ __forceinline__ f32x4 alb_bias4(const float* row, bool vec, int j, in
 }
 
 // ---- bf16 core, query kernel: statistics sweep + query sweep of one 64-query block -----------------------------------------
-template <bool BIAS, bool DBIAS>
+template <bool BIAS, bool DBIAS, bool DROP>
 __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[ALB::SMEM];
     const int S = p.S, P = p.P, L = S + P, H = p.H;
@@ -96,6 +106,13 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
     if constexpr (BIAS) {
         brow = p.bias + (int64_t)n * p.bias_sn + (int64_t)a * p.bias_sa + (int64_t)qc * p.bias_sq;
         bvec = (reinterpret_cast<uintptr_t>(brow) & 15) == 0;
+    }
+
+    // dropout: the lane's hash base (its g is the layout's l4; the wide layout: L > 256), the packed threshold
+    [[maybe_unused]] uint32_t dbase = 0u, dthr2 = 0u;
+    if constexpr (DROP) {
+        dbase = attn_drop_base(attn_drop_row(n, p.A, a, qrow, L), (uint32_t)g, p.drop_key);
+        dthr2 = attn_thrm1_2(p.drop_thr16);
     }
 
     // staging: piece r of thread t = row (t + 256 r) >> 3 of the tile, 16-byte chunk t & 7; zeros beyond L
@@ -189,6 +206,10 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
                 sum += e;
                 pb[kb >> 1][(kb & 1) * 4 + i] = (bf16)e;
             }
+        if constexpr (DROP) {                               // the row sum keeps the un-dropped weights; the context takes P o m
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) pb[ks] = attn_drop8_rt(pb[ks], dbase, 2 * t + ks, p.drop_key, dthr2);
+        }
         lsum = lsum * alpha + sum;
         const unsigned char* V = smem + b * ALB::BUF + ALB::IMG;
 #pragma unroll
@@ -214,7 +235,7 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
     }
     dl += __shfl_xor(dl, 16, 64);
     dl += __shfl_xor(dl, 32, 64);
-    dl *= inv;
+    dl *= DROP ? inv * p.drop_keep : inv;
     if (g == 0) { stats[qrow] = mf; stats[SP + qrow] = inv; stats[2 * SP + qrow] = dl; }
 
     // ---- sweep 2: dS, d_bias, dQ ------------------------------------------------------------------------------------
@@ -240,6 +261,12 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
             f32x4 dp = {0.f, 0.f, 0.f, 0.f};
             dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v0, fdo[0], dp, 0, 0, 0);
             dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, fdo[1], dp, 0, 0, 0);
+            if constexpr (DROP) {                           // dP = (dctx.V^T) o m / (1 - p): the two words of this 16-key block
+                const uint32_t hx = attn_drop_word(dbase, 2 * (4 * t + kb), p.drop_key);
+                const uint32_t hy = attn_drop_word(dbase, 2 * (4 * t + kb) + 1, p.drop_key);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) dp[i] = attn_keep_field(hx, hy, i, p.drop_thr16) ? dp[i] * p.drop_keep : 0.f;
+            }
             f32x4 ds;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -274,7 +301,7 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
 }
 
 // ---- bf16 core, key kernel: dK | dV of one 64-key block over the streamed query tiles ----------------------------------------
-template <bool BIAS>
+template <bool BIAS, bool DROP>
 __global__ __launch_bounds__(256) void attn_long_bwd_k_kernel(AttnBiasBwdArgs p) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[ALB::SMEM];
     const int S = p.S, P = p.P, L = S + P, H = p.H;
@@ -304,6 +331,15 @@ __global__ __launch_bounds__(256) void attn_long_bwd_k_kernel(AttnBiasBwdArgs p)
             fkk[ds] = *reinterpret_cast<const bf16x8*>(row + 32 * ds + 8 * g);
             fvv[ds] = *reinterpret_cast<const bf16x8*>(row + H + 32 * ds + 8 * g);
         }
+    }
+    // dropout: what the lane's key fixes for the whole kernel -- its l4, the multipliers of its 16-key block's two words -- and the
+    // counter row of query 0 of this (sequence, head); the lane hashes query q0 + (l15 & 3) of its quad's four
+    [[maybe_unused]] uint32_t drow0 = 0u, dl4 = 0u, dcx = 0u, dcy = 0u;
+    if constexpr (DROP) {
+        drow0 = attn_drop_row(n, p.A, a, l15 & 3, L);
+        dl4 = (uint32_t)(key >> 2) & 3u;
+        dcx = attn_drop_const(2 * (key >> 4));
+        dcy = attn_drop_const(2 * (key >> 4) + 1);
     }
     // staging of query tile t: Q | dO rows, zeros beyond S
     bf16x8 qreg[2], dreg[2];
@@ -358,12 +394,27 @@ __global__ __launch_bounds__(256) void attn_long_bwd_k_kernel(AttnBiasBwdArgs p)
             f32x4 dp = {0.f, 0.f, 0.f, 0.f};
             dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd0, fvv[0], dp, 0, 0, 0);
             dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd1, fvv[1], dp, 0, 0, 0);
+            // dropout: the lane's four values are four queries of ONE key, four counter rows; each lane of a quad hashes one of them
+            // (both words of the key's 16-key block) and quad broadcasts hand them round
+            [[maybe_unused]] uint32_t xq[4], yq[4];
+            if constexpr (DROP) {
+                const uint32_t hb = attn_drop_base(drow0 + (uint32_t)q0, dl4, p.drop_key);
+                const uint32_t hqx = attn_drop_fold(hb, dcx, p.drop_key), hqy = attn_drop_fold(hb, dcy, p.drop_key);
+                xq[0] = quad_bcast<0>(hqx); xq[1] = quad_bcast<1>(hqx); xq[2] = quad_bcast<2>(hqx); xq[3] = quad_bcast<3>(hqx);
+                yq[0] = quad_bcast<0>(hqy); yq[1] = quad_bcast<1>(hqy); yq[2] = quad_bcast<2>(hqy); yq[3] = quad_bcast<3>(hqy);
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float sv = (BIAS ? fmaf(c[e], SC, bq[e] * LOG2E) : c[e] * SC) + kpad;
                 const float pe = __builtin_amdgcn_exp2f(sv - m4[e]) * i4[e];
-                pB[qb >> 1][(qb & 1) * 4 + e] = (bf16)pe;
-                dsB[qb >> 1][(qb & 1) * 4 + e] = (bf16)(pe * (dp[e] - d4[e]));
+                if constexpr (DROP) {
+                    const float mk = attn_keep_field(xq[e], yq[e], key & 3, p.drop_thr16) ? p.drop_keep : 0.f;   // of (query q0 + e, key)
+                    pB[qb >> 1][(qb & 1) * 4 + e] = (bf16)(pe * mk);        // dV takes the masked probabilities
+                    dsB[qb >> 1][(qb & 1) * 4 + e] = (bf16)(pe * (mk * dp[e] - d4[e]));
+                } else {
+                    pB[qb >> 1][(qb & 1) * 4 + e] = (bf16)pe;
+                    dsB[qb >> 1][(qb & 1) * 4 + e] = (bf16)(pe * (dp[e] - d4[e]));
+                }
             }
         }
 #pragma unroll
@@ -401,6 +452,7 @@ __global__ __launch_bounds__(64) void attn_long_bwd_dhm_kernel(const float* stat
 }
 
 // ---- exact fp32 core, query kernel: 4 waves x 16 queries; K, V tiles of 64 keys in LDS ----------------------------------------
+template <bool DROP>
 __global__ __launch_bounds__(256) void attn_long_bwd_q_f32_kernel(AttnBiasBwdArgs p) {
     extern __shared__ float sm[];
     float* sK = sm;                          // [64][65]
@@ -450,6 +502,13 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_f32_kernel(AttnBiasBwdArg
         const int q = min(q0 + qi, S - 1);
         return bias ? fmaf(s, SC, bias[(int64_t)q * p.bias_sq + j] * LOG2E) : s * SC;
     };
+    // DROP: keep / (1 - p) or 0 of key 64 t + lane for query q0 + qi (the wide layout)
+    [[maybe_unused]] auto keep = [&](int t, int qi) {
+        const int j = t * 64 + lane;
+        uint32_t hx, hy;
+        attn_drop_words(attn_drop_row(n, p.A, a, q0 + qi, L), j >> 2, p.drop_key, hx, hy);
+        return attn_keep_field(hx, hy, j & 3, p.drop_thr16) ? p.drop_keep : 0.f;
+    };
     // ---- sweep 1: statistics --------------------------------------------------------------------------------
     float m[16], lsum[16], o[16];
 #pragma unroll
@@ -465,7 +524,8 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_f32_kernel(AttnBiasBwdArg
             const float e = exp2f(s - ms);
             lsum[qi] = lsum[qi] * alpha + wave_sum(e);
             m[qi] = mn;
-            p_img[lane] = e;
+            if constexpr (DROP) p_img[lane] = e * keep(t, qi);      // the row sum keeps the un-dropped weights
+            else p_img[lane] = e;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             float acc = 0.f;
 #pragma unroll 8
@@ -496,6 +556,7 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_f32_kernel(AttnBiasBwdArg
             float dp = 0.f;
 #pragma unroll 8
             for (int d = 0; d < 64; ++d) dp = fmaf(d_img[qi * 64 + d], sV[lane * 65 + d], dp);
+            if constexpr (DROP) dp *= keep(t, qi);
             const float ds = exp2f(s - m[qi]) * lsum[qi] * (dp - o[qi]);
             if (dbias && q < S && j < L) dbias[(int64_t)q * L + j] = ds * hm;
             p_img[lane] = ds;
@@ -514,6 +575,7 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_f32_kernel(AttnBiasBwdArg
 }
 
 // ---- exact fp32 core, key kernel: 4 waves x 16 keys; Q, dO tiles of 64 queries in LDS -----------------------------------------
+template <bool DROP>
 __global__ __launch_bounds__(256) void attn_long_bwd_k_f32_kernel(AttnBiasBwdArgs p) {
     extern __shared__ float sm[];
     float* sQ = sm;                          // [64][65]
@@ -571,8 +633,16 @@ __global__ __launch_bounds__(256) void attn_long_bwd_k_f32_kernel(AttnBiasBwdArg
             float sv = -INFINITY;
             if (j < L) sv = bias ? fmaf(s, SC, bias[(int64_t)min(i, S - 1) * p.bias_sq + j] * LOG2E) : s * SC;
             const float pe = exp2f(sv - mi) * ii;
-            wp[lane] = pe;
-            ws[lane] = pe * (dp - di);
+            if constexpr (DROP) {               // keep / (1 - p) or 0 of (query i, key j): dV takes the masked probabilities
+                uint32_t hx, hy;
+                attn_drop_words(attn_drop_row(n, p.A, a, i, L), j >> 2, p.drop_key, hx, hy);
+                const float mk = attn_keep_field(hx, hy, j & 3, p.drop_thr16) ? p.drop_keep : 0.f;
+                wp[lane] = pe * mk;
+                ws[lane] = pe * (mk * dp - di);
+            } else {
+                wp[lane] = pe;
+                ws[lane] = pe * (dp - di);
+            }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             float gv = 0.f, gk = 0.f;
 #pragma unroll 8
@@ -607,29 +677,31 @@ int alb_configure(K kernel, int bytes, bool& configured) {
     return MODCR_OK;
 }
 
+template <bool DROP>
 int launch_bf16(const AttnBiasBwdArgs& b, hipStream_t st) {
     const dim3 gq((b.S + 63) / 64, b.A, b.N), gk((b.S + b.P + 63) / 64, b.A, b.N);
-    if (!b.bias) hipLaunchKernelGGL((attn_long_bwd_q_kernel<false, false>), gq, dim3(ALB::NT), 0, st, b);
-    else if (!b.d_bias) hipLaunchKernelGGL((attn_long_bwd_q_kernel<true, false>), gq, dim3(ALB::NT), 0, st, b);
-    else hipLaunchKernelGGL((attn_long_bwd_q_kernel<true, true>), gq, dim3(ALB::NT), 0, st, b);
+    if (!b.bias) hipLaunchKernelGGL((attn_long_bwd_q_kernel<false, false, DROP>), gq, dim3(ALB::NT), 0, st, b);
+    else if (!b.d_bias) hipLaunchKernelGGL((attn_long_bwd_q_kernel<true, false, DROP>), gq, dim3(ALB::NT), 0, st, b);
+    else hipLaunchKernelGGL((attn_long_bwd_q_kernel<true, true, DROP>), gq, dim3(ALB::NT), 0, st, b);
     int rc = modcr_check_launch("attn_long_bwd_q");
     if (rc != MODCR_OK) return rc;
-    if (b.bias) hipLaunchKernelGGL((attn_long_bwd_k_kernel<true>), gk, dim3(ALB::NT), 0, st, b);
-    else hipLaunchKernelGGL((attn_long_bwd_k_kernel<false>), gk, dim3(ALB::NT), 0, st, b);
+    if (b.bias) hipLaunchKernelGGL((attn_long_bwd_k_kernel<true, DROP>), gk, dim3(ALB::NT), 0, st, b);
+    else hipLaunchKernelGGL((attn_long_bwd_k_kernel<false, DROP>), gk, dim3(ALB::NT), 0, st, b);
     return modcr_check_launch("attn_long_bwd_k");
 }
 
+template <bool DROP>
 int launch_f32(const AttnBiasBwdArgs& b, hipStream_t st) {
     static bool configured_q[MODCR_MAX_DEV] = {}, configured_k[MODCR_MAX_DEV] = {};
-    int rc = alb_configure(&attn_long_bwd_q_f32_kernel, ALB::F32_Q, configured_q[modcr_device_index()]);
+    int rc = alb_configure(&attn_long_bwd_q_f32_kernel<DROP>, ALB::F32_Q, configured_q[modcr_device_index()]);
     if (rc != MODCR_OK) return rc;
-    rc = alb_configure(&attn_long_bwd_k_f32_kernel, ALB::F32_K, configured_k[modcr_device_index()]);
+    rc = alb_configure(&attn_long_bwd_k_f32_kernel<DROP>, ALB::F32_K, configured_k[modcr_device_index()]);
     if (rc != MODCR_OK) return rc;
     const dim3 gq((b.S + 63) / 64, b.A, b.N), gk((b.S + b.P + 63) / 64, b.A, b.N);
-    hipLaunchKernelGGL(attn_long_bwd_q_f32_kernel, gq, dim3(256), ALB::F32_Q, st, b);
+    hipLaunchKernelGGL(attn_long_bwd_q_f32_kernel<DROP>, gq, dim3(256), ALB::F32_Q, st, b);
     rc = modcr_check_launch("attn_long_bwd_q_f32");
     if (rc != MODCR_OK) return rc;
-    hipLaunchKernelGGL(attn_long_bwd_k_f32_kernel, gk, dim3(256), ALB::F32_K, st, b);
+    hipLaunchKernelGGL(attn_long_bwd_k_f32_kernel<DROP>, gk, dim3(256), ALB::F32_K, st, b);
     return modcr_check_launch("attn_long_bwd_k_f32");
 }
 
@@ -641,18 +713,21 @@ int modcr_launch_attn_long_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype
                       (b.bias || b.head_mask || b.d_head_mask) && (b.bias || !b.d_bias),
                   "attn_long_bwd: null pointer");
     MODCR_REQUIRE((core == 3 || core == 4) && b.N > 0 && b.N <= 65535 && b.A > 0 && b.A <= 65535 && b.H == b.A * 64 && b.S > 0 && b.P >= 0 &&
-                      (int64_t)b.S + b.P <= 512 && b.drop_thr16 == 0,
+                      (int64_t)b.S + b.P <= 512,
                   "attn_long_bwd: unsupported call (core=%d S=%d P=%d dropout %s)", core, b.S, b.P, b.drop_thr16 ? "on" : "off");
+    // (dropout: the wide counter layout, which exists above 256 keys only and takes (n A + head) 512 x 4 counters in 32 bits)
+    MODCR_REQUIRE(b.drop_thr16 == 0 || ((int64_t)b.S + b.P > ATTN_DROP_NARROW_KEYS && (int64_t)b.N * b.A <= ATTN_DROP_WIDE_MAX_NA),
+                  "attn_long_bwd: dropout on the streaming cores needs more than 256 keys and N * A = %lld <= 2^21", (long long)b.N * b.A);
     MODCR_REQUIRE(((uintptr_t)b.stats & 15) == 0, "attn_long_bwd: the row statistics are not 16-byte aligned");
     int rc;
     if (core == 3) {
         MODCR_REQUIRE(dtype == MODCR_BF16 && modcr_aligned16(b.qkv) && modcr_aligned16(b.kvh) && modcr_aligned16(b.dctx) && modcr_aligned16(b.dqkv) &&
                           modcr_aligned16(b.dkvh),
                       "attn_long_bwd: the MFMA core takes 16-byte aligned bf16 rows");
-        rc = launch_bf16(b, stream);
+        rc = b.drop_thr16 ? launch_bf16<true>(b, stream) : launch_bf16<false>(b, stream);
     } else {
         MODCR_REQUIRE(dtype == MODCR_F32, "attn_long_bwd: the exact core takes fp32 rows and fp32 dctx (bf16 above 256 keys runs the MFMA core)");
-        rc = launch_f32(b, stream);
+        rc = b.drop_thr16 ? launch_f32<true>(b, stream) : launch_f32<false>(b, stream);
     }
     if (rc != MODCR_OK || !b.d_head_mask) return rc;
     hipLaunchKernelGGL(attn_long_bwd_dhm_kernel, dim3(b.N * b.A), dim3(64), 0, stream, b.stats, b.d_head_mask, b.S, (b.S + 63) & ~63);

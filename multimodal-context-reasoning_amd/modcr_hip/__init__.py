@@ -40,6 +40,8 @@ SIGNATURES = {
     "modcr_qkv_attn_bias_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "modcr_qkv_attn_bias_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i32,
                                        _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _i32, _vp, _i64, _i32, _vp]),
+    "modcr_qkv_attn_long_drop_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i32,
+                                            _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _i32, _vp, _i64, _i32, _vp]),
     "modcr_qkv_attn_route": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i64, _i32, _i32, _c.POINTER(_i32)]),
     "modcr_linear_splitk_workspace": (_i64, [_i32, _i32, _i32]),
     "modcr_linear_splitk_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
@@ -112,6 +114,10 @@ SIGNATURES = {
                                        _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
     "modcr_qkv_attn_long_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
                                        _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
+    "modcr_qkv_attn_long_drop_bwd_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_long_drop_bwd_route": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_long_drop_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
+                                            _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
     "modcr_linear_residual_ln_bwd_workspace": (_i64, [_i32, _i32, _i32]),
     "modcr_linear_residual_ln_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
                                             _vp, _i64, _i32, _vp]),
@@ -415,11 +421,14 @@ ATTN_SIDE_POST_DROPOUT = 1      # include/modcr_hip.h: MODCR_ATTN_SIDE_POST_DROP
 # mode only: no attention-probability dropout, no row statistics, no backward)
 ATTN_TILE_KEYS = 256
 ATTN_MAX_KEYS = 512
+# keys up to which the opt-in wide dropout counter layout (csrc/attn_common.h: row stride 512 above 256 keys) carries the
+# attention-probability dropout: qkv_attn(wide_dropout=True) / qkv_attn_long_bwd(wide_dropout=True)
+ATTN_DROPOUT_WIDE_MAX_KEYS = 512
 
 
 def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=None, want_probs=False,
              align_map=None, align_t=0, num_heads=None, workspace=None, out=None, attn_dropout=None, lse=None, dump=None,
-             side_post_dropout=False, attn_bias=None, head_mask=None, row_start=None):
+             side_post_dropout=False, attn_bias=None, head_mask=None, row_start=None, wide_dropout=False):
     """Fused QKV projection + attention.  x [N,S,H]; returns (ctx [N,S,H], probs or None).
     row_start: int32 [N+1] device table of the live-row layout (LiveRows; modcr_qkv_attn_rows_fwd): x and ctx are [N,S,H] BUFFERS
     whose first row_start[N] rows hold the sequences' live rows back to back.  No hist / probs / lse / dump / attn_bias there; a
@@ -428,6 +437,8 @@ def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=N
     attention_mask, soft biases, -inf entries); head_mask: [A], [1,A,1,1], [N,A] or [N,A,1,1], multiplies the probabilities of a
     head after softmax and dropout.  Either one sends the call to modcr_qkv_attn_bias_fwd (the streaming core with a float bias,
     P + S <= 512, dropout up to 256 keys); they replace key_mask / mask_bits and do not combine with lse / dump.
+    wide_dropout (that route only): the call goes to modcr_qkv_attn_long_drop_fwd, which carries the dropout on to 512 keys under the
+    wide counter layout; at P + S <= 256 or without dropout it changes nothing.
     attn_dropout = (p, seed, offset): training-mode dropout of the attention probabilities.
     side_post_dropout: probs / align_map are the probabilities AFTER that dropout, P o m / (1 - p), as the reference's modules
     return them (modeling_bert.py:69-74); default: the un-dropped ones (and no probs output under dropout).
@@ -453,13 +464,15 @@ def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=N
     p = 0 if hist is None else hist.shape[1]
     if p + s > ATTN_MAX_KEYS:
         raise ValueError("qkv_attn: P + S = %d keys exceeds the %d-key limit of the attention forward" % (p + s, ATTN_MAX_KEYS))
+    if wide_dropout and attn_bias is None and head_mask is None:
+        raise ValueError("qkv_attn: wide_dropout belongs to the attn_bias / head_mask route (fold a binary key mask with fold_key_mask)")
     if attn_bias is not None or head_mask is not None:
         if key_mask is not None or mask_bits is not None:
             raise ValueError("qkv_attn: attn_bias / head_mask replace key_mask / mask_bits (fold a binary mask into the bias as 0 / -10000)")
         if lse is not None or dump is not None:
             raise ValueError("qkv_attn: no row statistics (lse) / q|k|v dump on the attn_bias / head_mask route (forward only)")
         return _qkv_attn_bias(x, wqkv, bqkv, attn_bias, head_mask, hist, chunk_id, want_probs, align_map, align_t, a, workspace, out,
-                              attn_dropout, side_post_dropout)
+                              attn_dropout, side_post_dropout, wide_dropout)
     if (dt == BF16 and attn_dropout is not None and attn_dropout[0] > 0.0 and side_post_dropout and (want_probs or align_map is not None)
             and not side_outputs_on_tiles(s, p, h, a)):
         # post-dropout side outputs are served by the bf16 TILE kernels only (modcr_qkv_attn_opt_fwd returns MODCR_ERR_UNSUPPORTED on
@@ -530,14 +543,14 @@ def _head_mask_2d(head_mask, n, a):
 
 
 def _qkv_attn_bias(x, wqkv, bqkv, attn_bias, head_mask, hist, chunk_id, want_probs, align_map, align_t, a, workspace, out, attn_dropout,
-                   side_post_dropout):
-    """qkv_attn with attn_bias / head_mask: modcr_qkv_attn_bias_fwd"""
+                   side_post_dropout, wide_dropout=False):
+    """qkv_attn with attn_bias / head_mask: modcr_qkv_attn_bias_fwd, or with wide_dropout modcr_qkv_attn_long_drop_fwd"""
     dt = dt_of(x)
     n, s, h = x.shape
     p = 0 if hist is None else hist.shape[1]
     l = p + s
     ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
-    if ap > 0.0 and l > ATTN_TILE_KEYS:
+    if ap > 0.0 and l > ATTN_TILE_KEYS and not wide_dropout:
         raise ValueError("qkv_attn: attention-probability dropout with attn_bias / head_mask stops at %d keys (P + S = %d)" % (ATTN_TILE_KEYS, l))
     bias, (bsn, bsa, bsq) = (None, (0, 0, 0)) if attn_bias is None else _bias_strides(attn_bias, n, a, s, l)
     hm, hsn = (None, 0) if head_mask is None else _head_mask_2d(head_mask, n, a)
@@ -548,11 +561,12 @@ def _qkv_attn_bias(x, wqkv, bqkv, attn_bias, head_mask, hist, chunk_id, want_pro
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=x.device)
     chunk_t = 0 if chunk_id is None else chunk_id.shape[1]
-    _check(lib().modcr_qkv_attn_bias_fwd(_ptr(x), _ptr(hist), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq, _ptr(hm), hsn,
-                                         _ptr(chunk_id), chunk_t, _ptr(ctx), _ptr(probs), _ptr(align_map), align_t, n, s, p, h, a,
-                                         float(ap), seed, off, ATTN_SIDE_POST_DROPOUT if side_post_dropout else 0,
-                                         _ptr(workspace), need, dt, _stream()),
-           "modcr_qkv_attn_bias_fwd")
+    entry = "modcr_qkv_attn_long_drop_fwd" if wide_dropout else "modcr_qkv_attn_bias_fwd"
+    _check(getattr(lib(), entry)(_ptr(x), _ptr(hist), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq, _ptr(hm), hsn,
+                                 _ptr(chunk_id), chunk_t, _ptr(ctx), _ptr(probs), _ptr(align_map), align_t, n, s, p, h, a,
+                                 float(ap), seed, off, ATTN_SIDE_POST_DROPOUT if side_post_dropout else 0,
+                                 _ptr(workspace), need, dt, _stream()),
+           entry)
     return ctx, probs
 
 
@@ -1136,13 +1150,14 @@ _ATTN_BIAS_BWD_ARGS = {
     "prefix": tuple(k for k in _GATE_BWD_ARGS if k not in ("chunk_id", "chunk_t", "d_head_mask")),
     "gate": _GATE_BWD_ARGS,
     "long": _GATE_BWD_ARGS,
+    "long_drop": _GATE_BWD_ARGS,
 }
 
 
 def _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, a, accumulate, attn_dropout, dx_residual,
-                       d_head_mask=None, long=False):
-    """The bias family of the attention backward, one marshalling path for its four C entries: long (qkv_attn_long_bwd) ->
-    modcr_qkv_attn_long_bwd, else with d_head_mask -> modcr_qkv_attn_gate_bwd, else with hist -> modcr_qkv_attn_prefix_bwd, else
+                       d_head_mask=None, long=False, wide_dropout=False):
+    """The bias family of the attention backward, one marshalling path for its five C entries: long (qkv_attn_long_bwd) ->
+    modcr_qkv_attn_long_bwd, or with wide_dropout modcr_qkv_attn_long_drop_bwd, else with d_head_mask -> modcr_qkv_attn_gate_bwd, else with hist -> modcr_qkv_attn_prefix_bwd, else
     modcr_qkv_attn_bias_bwd.  Returns dx, or (dx, d_hist) with hist."""
     who = "qkv_attn_long_bwd" if long else "qkv_attn_bwd"
     dt = dt_of(x)
@@ -1150,13 +1165,14 @@ def _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_
     p, bias, (bsn, bsa, bsq), hm, hsn = _attn_bias_bwd_operands(who, x, hist, attn_bias, head_mask, d_bias, d_head_mask, a,
                                                                 ATTN_BWD_LONG_MAX_KEYS if long else ATTN_BWD_MAX_KEYS)
     ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
-    if long and p + s > ATTN_BWD_MAX_KEYS and ap > 0:
+    if long and p + s > ATTN_BWD_MAX_KEYS and ap > 0 and not wide_dropout:
         raise ValueError("%s: attention-probability dropout (p=%g) is not implemented above %d keys (P + S = %d)" % (who, ap, ATTN_BWD_MAX_KEYS, p + s))
-    entry = "long" if long else "gate" if d_head_mask is not None else "prefix" if p else "bias"
+    entry = ("long_drop" if wide_dropout else "long") if long else "gate" if d_head_mask is not None else "prefix" if p else "bias"
     fn, ws_fn = {"bias": (lib().modcr_qkv_attn_bias_bwd, lib().modcr_qkv_attn_bias_bwd_workspace),
                  "prefix": (lib().modcr_qkv_attn_prefix_bwd, lib().modcr_qkv_attn_prefix_bwd_workspace),
                  "gate": (lib().modcr_qkv_attn_gate_bwd, lib().modcr_qkv_attn_gate_bwd_workspace),
-                 "long": (lib().modcr_qkv_attn_long_bwd, lib().modcr_qkv_attn_long_bwd_workspace)}[entry]
+                 "long": (lib().modcr_qkv_attn_long_bwd, lib().modcr_qkv_attn_long_bwd_workspace),
+                 "long_drop": (lib().modcr_qkv_attn_long_drop_bwd, lib().modcr_qkv_attn_long_drop_bwd_workspace)}[entry]
     x, dctx = _contig(x), _contig(dctx)
     dx = torch.empty_like(x)
     hist = _contig(hist) if p else None
@@ -1184,11 +1200,14 @@ def qkv_attn_long_bwd_route(n, s, p, h, a, dtype=BF16):
 
 
 def qkv_attn_long_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, chunk_id=None, num_heads=None, accumulate=False, attn_dropout=None,
-                      dx_residual=None, attn_bias=None, head_mask=None, d_bias=None, hist=None, d_head_mask=None):
+                      dx_residual=None, attn_bias=None, head_mask=None, d_bias=None, hist=None, d_head_mask=None, wide_dropout=False):
     """qkv_attn_bwd's attn_bias / head_mask / hist route with the key limit 512 instead of 256 (modcr_qkv_attn_long_bwd): the backward
     of a forward that ran qkv_attn(attn_bias=, head_mask=, hist=) at P + S <= 512 keys.  Returns dx, or (dx, d_hist) with hist.  At
     P + S <= 256 the call is modcr_qkv_attn_gate_bwd's, bit for bit; above, the streaming cores run and attention dropout is refused.
-    A binary key_mask [N, L] is folded into a [N,1,1,L] 0 / -10000 bias (fold the forward the same way); chunk_id only without hist."""
+    A binary key_mask [N, L] is folded into a [N,1,1,L] 0 / -10000 bias (fold the forward the same way); chunk_id only without hist.
+    wide_dropout: the backward of a forward that ran qkv_attn(wide_dropout=True) (modcr_qkv_attn_long_drop_bwd): above 256 keys the
+    streaming cores regenerate that forward's keep mask from attn_dropout = (p, seed, offset) under the wide counter layout; at
+    P + S <= 256 or without dropout it changes nothing."""
     if hist is not None and chunk_id is not None:
         raise ValueError("qkv_attn_long_bwd: hist (prefix rows) does not combine with chunk_id")
     if key_mask is not None:
@@ -1196,7 +1215,7 @@ def qkv_attn_long_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, chunk_id
             raise ValueError("qkv_attn_long_bwd: attn_bias replaces key_mask")
         attn_bias = fold_key_mask(key_mask)
     return _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, num_heads, accumulate,
-                              attn_dropout, dx_residual, d_head_mask, long=True)
+                              attn_dropout, dx_residual, d_head_mask, long=True, wide_dropout=bool(wide_dropout))
 
 
 def fold_key_mask(key_mask):

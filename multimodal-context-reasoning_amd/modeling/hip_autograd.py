@@ -23,11 +23,16 @@ def set_exact(flag):
 
 LONG_BACKWARD = False      # True = trainable layers above 256 keys run the streaming attention backward (up to 512 keys, no
                            # attention-probability dropout there); opt-in, set by the run scripts' --modcr_long_backward
+LONG_DROPOUT = False       # True (with LONG_BACKWARD) = attention-probability dropout is carried above 256 keys too, under the wide
+                           # counter layout (modcr_qkv_attn_long_drop_fwd / _bwd); opt-in, --modcr_long_dropout
 
 
-def set_long_backward(flag):
-    global LONG_BACKWARD
+def set_long_backward(flag, dropout=False):
+    """flag: trainable layers above 256 keys run the streaming attention backward; dropout (only with flag): they also apply the
+    attention-probability dropout there.  set_long_backward(True) and set_long_backward(False) leave the dropout switch off."""
+    global LONG_BACKWARD, LONG_DROPOUT
     LONG_BACKWARD = bool(flag)
+    LONG_DROPOUT = bool(flag) and bool(dropout)
 
 
 def _w_for(x, w):
@@ -391,7 +396,7 @@ def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, par
         if s > mh.ATTN_BWD_LONG_MAX_KEYS:
             raise NotImplementedError("a trainable layer at %s = %d exceeds the %d keys the streaming attention backward takes" %
                                       (what, s, mh.ATTN_BWD_LONG_MAX_KEYS))
-        if attn_p > 0.0:
+        if attn_p > 0.0 and not LONG_DROPOUT:
             raise NotImplementedError("attention-probability dropout (p=%g) in a trainable layer needs %s <= %d (%s = %d): set "
                                       "attention_probs_dropout_prob = 0 to train above %d keys" %
                                       (attn_p, what, mh.ATTN_TILE_KEYS, what, s, mh.ATTN_TILE_KEYS))
@@ -409,7 +414,8 @@ def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, par
                                               side_post_dropout=bool(packed.get("_side_post", True)) if isinstance(packed, dict) else True,
                                               attn_bias=None if attn_bias is None else attn_bias.detach(),
                                               head_mask=None if head_mask is None else head_mask.detach(),
-                                              hist=None if hist is None else hist.detach(), long_backward=long_bwd)
+                                              hist=None if hist is None else hist.detach(), long_backward=long_bwd,
+                                              long_dropout=long_bwd and LONG_DROPOUT)
     ctx.saved, ctx.packed = saved, packed
     ctx.holder = align[2] if align is not None else None
     ctx.params = params                  # (the Parameter objects: the gradient sink writes into their .grad views)

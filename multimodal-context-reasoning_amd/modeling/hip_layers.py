@@ -183,7 +183,8 @@ def attn_dropout_supported(x, num_heads):
 
 
 def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None, chunk_id=None, p=0.0, attn_p=0.0,
-                        align_map=None, align_t=0, side_post_dropout=True, attn_bias=None, head_mask=None, hist=None, long_backward=False):
+                        align_map=None, align_t=0, side_post_dropout=True, attn_bias=None, head_mask=None, hist=None, long_backward=False,
+                        long_dropout=False):
     """p: hidden_dropout_prob of BertSelfOutput / BertOutput in training mode (a_bert:369-373, :446-451);
     attn_p: attention_probs_dropout_prob (modeling_bert.py:69), applied inside the attention kernels;
     align_map [N,T,R] fp32 (+= head-summed text->region probabilities of this layer, v10:982), align_t = T;
@@ -198,12 +199,16 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
     long_backward: above 256 keys (256 < P + S <= 512) the forward takes the biased route -- a binary key_mask is folded into a
     0 / -10000 bias, with or without hist, chunk_id allowed without hist; no lse / dump -- and layer_backward runs the streaming
     attention backward (mh.qkv_attn_long_bwd).  No attention dropout, mask bits or align map there.  At P + S <= 256 it changes
-    nothing."""
+    nothing.
+    long_dropout (with long_backward, above 256 keys): attn_p > 0 is served there too -- the DROPOUT counters are taken as below 256
+    keys (n A s (P + S) of them), the forward runs mh.qkv_attn(wide_dropout=True) under the wide counter layout and layer_backward
+    regenerates its mask (mh.qkv_attn_long_bwd(wide_dropout=True))."""
     n, s, h = x.shape
     pl = 0 if hist is None else hist.shape[1]
     long_backward = bool(long_backward) and pl + s > mh.ATTN_BWD_MAX_KEYS
+    long_dropout = bool(long_dropout) and long_backward and attn_p > 0.0
     if long_backward:
-        if attn_p > 0.0:
+        if attn_p > 0.0 and not long_dropout:
             raise NotImplementedError("attention-probability dropout in a trainable layer needs P + S <= 256 (S=%d, P=%d): set "
                                       "attention_probs_dropout_prob = 0 to train above 256 keys" % (s, pl))
         if mask_bits is not None or align_map is not None:
@@ -230,7 +235,7 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
         raise ValueError("layer_forward_train: no align map (and no align-map gradient) on the attn_bias / head_mask route")
     adrop = None
     if attn_p > 0.0:
-        if not attn_dropout_supported(x, num_heads) or pl + s > 256:
+        if (not attn_dropout_supported(x, num_heads) or pl + s > 256) and not long_dropout:
             raise NotImplementedError("attention-probability dropout in a trainable layer needs P + S <= 256 (S=%d, P=%d, dtype=%s)" % (s, pl, x.dtype))
         seed, off = mh.DROPOUT.take(n * num_heads * s * (pl + s))
         adrop = (float(attn_p), seed, off)
@@ -244,7 +249,7 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
     post = bool(side_post_dropout and adrop is not None and align_map is not None)
     if biased:
         ctx, _ = mh.qkv_attn(x, layer["wqkv"], layer["bqkv"], chunk_id=chunk_id, num_heads=num_heads, attn_dropout=adrop,
-                             attn_bias=attn_bias, head_mask=head_mask, hist=hist)
+                             attn_bias=attn_bias, head_mask=head_mask, hist=hist, **({"wide_dropout": True} if long_dropout else {}))
     else:
         ctx, _ = mh.qkv_attn(x, layer["wqkv"], layer["bqkv"], key_mask=key_mask, mask_bits=mask_bits, chunk_id=chunk_id,
                              num_heads=num_heads, attn_dropout=adrop, align_map=align_map, align_t=align_t, lse=lse, dump=dump,
@@ -263,7 +268,7 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
     saved = dict(x=x, ctx=ctx, pre1=pre1, a=a, inter=inter, u=u, pre2=pre2, num_heads=num_heads, eps=eps,
                  key_mask=key_mask, mask_bits=mask_bits, chunk_id=chunk_id, drop1=drop1, drop2=drop2, adrop=adrop,
                  align_t=align_t if align_map is not None else 0, lse=lse, dump=dump, side_post=post,
-                 attn_bias=attn_bias, head_mask=head_mask, hist=hist, long_backward=long_backward)
+                 attn_bias=attn_bias, head_mask=head_mask, hist=hist, long_backward=long_backward, long_dropout=long_dropout)
     return y.view(n, s, h), saved
 
 
@@ -355,11 +360,12 @@ def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None, want_d_
             raise ValueError("layer_backward: want_d_head_mask for a layer that ran without head_mask")
         d_hm = torch.empty((n, saved["num_heads"]), dtype=f32, device=dev) if want_d_head_mask else None
         # (a layer that ran with long_backward above 256 keys: the streaming backward, modcr_qkv_attn_long_bwd)
+        # (... and with long_dropout under attention dropout: its DROP cores, modcr_qkv_attn_long_drop_bwd)
         attn_bwd = mh.qkv_attn_long_bwd if saved.get("long_backward") else mh.qkv_attn_bwd
         dx = attn_bwd(d_ctx.view(n, s, h), x, layer["wqkv"], layer["bqkv"], dwqkv, dbqkv, chunk_id=saved["chunk_id"],
                       num_heads=saved["num_heads"], attn_dropout=saved.get("adrop"), dx_residual=d_pre1.view(n, s, h),
                       attn_bias=saved.get("attn_bias"), head_mask=saved.get("head_mask"), d_bias=d_bias, hist=hist,
-                      d_head_mask=d_hm)
+                      d_head_mask=d_hm, **({"wide_dropout": True} if saved.get("long_dropout") else {}))
         if hist is not None:
             dx, g["history_state"] = dx
         if want_d_bias:

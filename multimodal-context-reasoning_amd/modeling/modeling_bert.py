@@ -37,7 +37,7 @@ class CaptionBertSelfAttention(BertSelfAttention):
         per-head multiplier of the probabilities, mh.qkv_attn's general route.  row_start: x and out are [N,S,H] buffers in the
         live-row layout (mh.LiveRows); the attention-dropout counters are those of the dense call."""
         w, b = self.packed_qkv(x.dtype)
-        drop = None
+        drop, wide = None, False
         if self.training and self.dropout.p > 0.0:      # nn.Dropout on the probabilities (modeling_bert.py:69), training mode
             n, s, h = x.shape
             l = s + (0 if hist is None else hist.shape[1])
@@ -45,8 +45,19 @@ class CaptionBertSelfAttention(BertSelfAttention):
             # under dropout is the post-dropout one, as the reference returns it (modeling_bert.py:69-74) -- on shapes the bf16 tile
             # kernels do not serve, mh.qkv_attn runs that call on the exact-fp32 route.  What the library does not offer is an error,
             # not a silently un-dropped forward:
-            if l > 256:
-                raise NotImplementedError("attention-probability dropout: P + S = %d exceeds the 256 keys the attention kernels take" % l)
+            # (above 256 keys: only with hip_autograd.set_long_backward(True, dropout=True), on the attn_bias route under the wide
+            # counter layout -- a binary key mask is folded into a 0 / -10000 bias; dense phase masks stay at 256 keys)
+            wide = l > 256
+            if wide:
+                from . import hip_autograd
+                if not hip_autograd.LONG_DROPOUT or l > mh.ATTN_DROPOUT_WIDE_MAX_KEYS or mask_bits is not None or row_start is not None:
+                    raise NotImplementedError("attention-probability dropout: P + S = %d exceeds the 256 keys the attention kernels take" % l)
+                if key_mask is not None:
+                    if attn_bias is not None:
+                        raise ValueError("hip_forward: attn_bias replaces key_mask")
+                    attn_bias, key_mask = mh.fold_key_mask(key_mask), None
+                if attn_bias is None and head_mask is None:
+                    attn_bias = torch.zeros((1, 1, 1, l), dtype=torch.float32, device=x.device)
             if want_probs and not self.side_post_dropout:
                 raise NotImplementedError("a probabilities output in training mode is the post-dropout one (modeling_bert.py:69-74); "
                                           "config.modcr_align_map_post_dropout=False offers the un-dropped align map only")
@@ -56,7 +67,8 @@ class CaptionBertSelfAttention(BertSelfAttention):
                            want_probs=want_probs, align_map=align_map, align_t=align_t,
                            num_heads=self.num_attention_heads, workspace=workspace, out=out, attn_dropout=drop,
                            side_post_dropout=self.side_post_dropout and drop is not None and (want_probs or align_map is not None),
-                           attn_bias=attn_bias, head_mask=head_mask, **({} if row_start is None else {"row_start": row_start}))
+                           attn_bias=attn_bias, head_mask=head_mask, **({} if row_start is None else {"row_start": row_start}),
+                           **({"wide_dropout": True} if wide else {}))
 
     def forward(self, hidden_states, attention_mask, head_mask=None, history_state=None):
         n, s, _ = hidden_states.shape

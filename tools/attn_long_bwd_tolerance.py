@@ -10,6 +10,12 @@ bias forms, head mask (1, 0.5), no dropout.  Each line is the share of a bound t
 if one exceeded half a bound, the INPUT would have to change, not the bound.
 
     python tools/attn_long_bwd_tolerance.py [--out profiles/attn_long_bwd_tolerance_report.txt]
+
+--drop: the same restatement with the attention-probability dropout of the wide counter layout (modcr_qkv_attn_long_drop_fwd / _bwd),
+on the cases of tests/test_hip_attn_long_drop.py: the keep mask m of tests/attn_wide_drop.py clears the bf16 probabilities that enter
+the context and D, 1 / (1 - p) multiplies in fp32, dP takes m / (1 - p), the dV operand is bf16(P / (1 - p)) o m.
+
+    python tools/attn_long_bwd_tolerance.py --drop [--out profiles/attn_long_drop_tolerance_report.txt]
 """
 import argparse
 import os
@@ -30,10 +36,11 @@ def r16(t):
     return t.float().to(torch.bfloat16).double()
 
 
-def rounded_restatement(shape, bias, hm):
-    """(ctx, dx, d_hist or None, dWqkv, dbqkv, dS, d_hm) of the bf16 route's arithmetic in float64 with its roundings"""
+def rounded_restatement(shape, bias, hm, keep=None, pd=0.0, c=None):
+    """(ctx, dx, d_hist or None, dWqkv, dbqkv, dS, d_hm) of the bf16 route's arithmetic in float64 with its roundings; keep [N, A, S, L]
+    (0 / 1) and pd: the attention-probability dropout of the DROP instantiations; c: another case than the shape's"""
     n, s, p, h, a = shape
-    c = T.case(shape)
+    c = T.case(shape) if c is None else c
     w, b, x = (t.double() for t in c[:3])
     hist = c[3].double() if p else torch.zeros(n, 0, h, dtype=torch.float64)
     dctx = c[-1].double()
@@ -45,16 +52,24 @@ def rounded_restatement(shape, bias, hm):
     k = sp(torch.cat([kvh[..., :h], qkv[..., h:2 * h]], 1))
     v = sp(torch.cat([kvh[..., h:], qkv[..., 2 * h:]], 1))
     do = sp(dctx)
-    P = torch.softmax(q @ k.transpose(-1, -2) / 8.0 + bias.double(), -1)
+    P = torch.softmax(q @ k.transpose(-1, -2) / 8.0 + (0.0 if bias is None else bias.double()), -1)
     hmv = hm.double().reshape(n, a, 1, 1)
     back = lambda t: t.transpose(1, 2).reshape(n, t.shape[2], h)
-    ctx = r16(back(r16(P) @ v * hmv))
-    dp = do @ v.transpose(-1, -2)
-    dl = (r16(P) @ v * do).sum(-1, keepdim=True)                            # D = dctx . (P.V), P as the context product takes it
+    if keep is None:
+        ctx = r16(back(r16(P) @ v * hmv))
+        dp = do @ v.transpose(-1, -2)
+        dl = (r16(P) @ v * do).sum(-1, keepdim=True)                        # D = dctx . (P.V), P as the context product takes it
+        Pv = r16(P)                                                         # the dV operand
+    else:
+        inv = 1.0 / (1.0 - pd)
+        ctx = r16(back((r16(P) * keep) @ v * hmv * inv))                    # dropped bf16 weights cleared, 1 / (1 - p) in fp32
+        dp = do @ v.transpose(-1, -2) * keep * inv
+        dl = ((r16(P) * keep) @ v * do).sum(-1, keepdim=True) * inv
+        Pv = r16(P * inv) * keep
     ds = P * (dp - dl)
     dq = r16(back(r16(ds) @ k * hmv * 0.125))
     dk = r16(back(r16(ds).transpose(-1, -2) @ q * hmv * 0.125))
-    dv = r16(back(r16(P).transpose(-1, -2) @ do * hmv))
+    dv = r16(back(Pv.transpose(-1, -2) @ do * hmv))
     dqkv = torch.cat([dq, dk[:, p:], dv[:, p:]], -1)                         # [N, S, 3H]
     dkvh = torch.cat([dk[:, :p], dv[:, :p]], -1)                             # [N, P, 2H]
     dx = r16(dqkv @ w)
@@ -66,10 +81,72 @@ def rounded_restatement(shape, bias, hm):
     return ctx, dx, dh, dw, db, ds * hmv, dl.sum((-1, -2))
 
 
+def uses(names, got, ref, shape, tol=2e-2):
+    """[(quantity, share of its bound)] of one case, as test_hip_attn_long_bwd.check_all holds them"""
+    n, s, p, h, a = shape
+    out = []
+    for nm, g, r in zip(names, got, ref):
+        if r is None:
+            continue
+        g, r = g.clone(), r.clone()
+        if nm == "dbqkv":
+            g[h:2 * h] = 0
+            r[h:2 * h] = 0
+        out.append((nm, float((g - r).abs().max()) / max(1.0, float(r.abs().max())) / tol))
+        if nm in ("dx", "d_hist", "dwqkv"):
+            out.append((nm + " rel L2", float((g - r).norm() / r.norm()) / 2e-2))
+    out.append(("key-bias slice", float(got[4][h:2 * h].abs().max()) / (tol * max(1.0, float(ref[4].abs().max())) * (n * s) ** 0.5 * 0.25)))
+    return out
+
+
+def main_drop(out):
+    import attn_wide_drop as W
+    import test_hip_attn_long_drop as D
+    names = ("ctx", "dx", "d_hist", "dwqkv", "dbqkv", "d_bias", "d_head_mask")
+    lines = ["bf16-rounded restatement of the attention backward from 257 to 512 keys UNDER ATTENTION DROPOUT (wide counter layout, p = %g)" % D.DROP[0],
+             "against float64 with the same mask (CPU): PREDICTED share of each bound of tests/test_hip_attn_long_drop.py used by the number",
+             "formats alone.  max|err| / max(1, max|ref|) against 2e-2; relative L2 against 2e-2; key-bias slice against 2e-2 x scale x",
+             "sqrt(N S) / 4; the flat-score case also d_bias element-wise against 2e-2 x max|d_bias| and against 2e-2 x its row's max|d_bias| (no floor of 1).  The chunk-mean case",
+             "(2, 320, 0, 256, 4) is not restated: the chunk mean adds no rounding site that the dropout touches.", ""]
+    worst = {}
+    cases = [(shape, form, None) for shape in D.SHAPES for form in D.FORMS] + [(D.SHAPES[1], "flat scores", D.flat_case(D.SHAPES[1])[0])]
+    for shape, form, c in cases:
+        n, s, p, h, a = shape
+        if c is None:
+            bias, hm = D.operands(form, shape)
+            ref = D.form_reference(shape, form)
+        else:
+            bias, hm = torch.zeros(n, a, s, s), torch.ones(n, a)
+            ref = D.reference(shape, bias, hm, D.DROP, c=c)
+        keep = W.keep_of_call(n, a, s, p, D.DROP).double()
+        got = rounded_restatement(shape, bias, hm.expand(n, a), keep, D.DROP[0], c=c)
+        row = uses(names, got, ref, shape)
+        if c is not None:
+            row.append(("d_bias element-wise", float((got[5] - ref[5]).abs().max()) / float(ref[5].abs().max()) / 2e-2))
+            row.append(("d_bias / row max", float(((got[5] - ref[5]).abs() / ref[5].abs().amax(-1, keepdim=True)).max()) / 2e-2))
+        for nm, use in row:
+            worst[nm] = max(worst.get(nm, (0.0, None)), (use, (shape, form)))
+        lines.append("%-24s %-11s %s" % (shape, form, "  ".join("%s %4.1f %%" % (nm, 100 * u) for nm, u in row)))
+    lines += ["", "worst predicted use of each bound:"]
+    for nm, (use, where) in worst.items():
+        lines.append("  %-20s %5.1f %%  at %s %s" % (nm, 100 * use, where[0], where[1]))
+    top = max(u for u, _ in worst.values())
+    lines += ["", "largest predicted share: %.1f %% -- %s" % (100 * top, "below half of every bound: inputs, p and bounds stand" if top < 0.5 else
+                                                              "ABOVE HALF A BOUND: reduce that case's p or weight scale")]
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    with open(out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attn_long_bwd_tolerance_report.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--drop", action="store_true", help="the dropout cases of tests/test_hip_attn_long_drop.py")
     args = ap.parse_args()
+    if args.drop:
+        return main_drop(args.out or os.path.join(ROOT, "profiles", "attn_long_drop_tolerance_report.txt"))
+    args.out = args.out or os.path.join(ROOT, "profiles", "attn_long_bwd_tolerance_report.txt")
     lines = ["bf16-rounded restatement of the attention backward from 257 to 512 keys against float64 (CPU): share of each bound of",
              "tests/test_hip_attn_long_bwd.py used by the number formats alone.  Soft-bias case: head mask (1, 0.5), no dropout.",
              "max|err| / max(1, max|ref|) against 2e-2; relative L2 against 2e-2; key-bias slice against 2e-2 x scale x sqrt(N S) / 4.", ""]
