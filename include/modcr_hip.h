@@ -400,7 +400,31 @@ int modcr_mc_ce_fwd_bwd(const float* logits, const float* label, float* loss, fl
  * Size the workspace with the query and nothing else: modcr_linear_bwd_weight_workspace(M, N, K) is the maximum over the forms the
  * call may take (plain, half-TN, the swapped dW^T form with its transposing reduction, the per-row-block bias partials), and the
  * fast forms are taken only when workspace_bytes >= that figure -- a buffer sized by an older rule (X^T + splits * N * K * 4)
- * is still CORRECT (the call falls back to the generic split-K route) but slower, with no error. */
+ * is still CORRECT (the call falls back to the generic split-K route) but slower, with no error.
+ *
+ * modcr_linear_bwd_weight_route / modcr_linear_bwd_input_route report the route the compute entry takes for the same arguments
+ * (no stream), decided by the same host functions (gemm.hip: route_bwd_weight, route_bwd_input).  They dereference nothing:
+ * pointers are inspected for NULL and alignment only.  They return MODCR_OK or the compute entry's refusal.
+ *   dW: info[0] = form (MODCR_BWD_WEIGHT_*: F32 the exact fallback, NT both operands transposed, HALF_TN dY transposed and X
+ *       token-major, SWAPPED dW^T = X^T . dY with X transposed and dY token-major, TN no transposes -- tuning build only; tried
+ *       in the order TN, SWAPPED, HALF_TN, NT, F32), info[1] = splits, info[2] = 64-token K-tiles per split (both 0 for F32),
+ *       info[3] = the product's launcher (MODCR_BWD_PRODUCT_*: the persistent split-K kernel, the forward's dispatcher, or the
+ *       fp32 kernel), info[4] = 1 when the product writes dW itself (one split, no accumulation; F32), info[5] = the reduction
+ *       (MODCR_BWD_REDUCE_*), info[6] = how db is formed (MODCR_BWD_DB_*: NONE not wanted; FUSED_REDUCE / FUSED_FOLD partial
+ *       column sums from the dY transpose, folded by extra blocks of the reduction / by a launch of its own; ROWSUM row sums of
+ *       dY^T; BLOCK_FOLD per-row-block column sums of dY + their fold; ATOMIC memset + atomic column sums (TN); COLSUM the
+ *       generic column-sum kernel (F32)).
+ *   dX: `residual` = the fp32 rows that the layer composites add in the product's epilogue (NULL for modcr_linear_bwd_input
+ *       itself).  info[0] = form (MODCR_BWD_INPUT_*: F32 the exact fallback, FWD through modcr_linear_fwd, SPLITK through
+ *       modcr_linear_splitk_fwd), info[1] = 1 when an fp32 dY is cast and zero-padded to bf16 first, info[2..5] = what
+ *       modcr_linear_route reports for the inner product (FWD only, 0 otherwise).  Refusals: those of modcr_linear_bwd_input and, for
+ *       FWD, of the inner modcr_linear_fwd; the alignment checks modcr_linear_splitk_fwd makes on its workspace are not repeated. */
+enum { MODCR_BWD_WEIGHT_F32 = 1, MODCR_BWD_WEIGHT_NT = 2, MODCR_BWD_WEIGHT_HALF_TN = 3, MODCR_BWD_WEIGHT_SWAPPED = 4, MODCR_BWD_WEIGHT_TN = 5 };
+enum { MODCR_BWD_PRODUCT_F32 = 0, MODCR_BWD_PRODUCT_SPLITK = 1, MODCR_BWD_PRODUCT_DISPATCH = 2 };
+enum { MODCR_BWD_REDUCE_NONE = 0, MODCR_BWD_REDUCE_PLAIN = 1, MODCR_BWD_REDUCE_TRANSPOSED = 2 };
+enum { MODCR_BWD_DB_NONE = 0, MODCR_BWD_DB_FUSED_REDUCE = 1, MODCR_BWD_DB_FUSED_FOLD = 2, MODCR_BWD_DB_ROWSUM = 3, MODCR_BWD_DB_BLOCK_FOLD = 4,
+       MODCR_BWD_DB_ATOMIC = 5, MODCR_BWD_DB_COLSUM = 6 };
+enum { MODCR_BWD_INPUT_F32 = 1, MODCR_BWD_INPUT_FWD = 2, MODCR_BWD_INPUT_SPLITK = 3 };
 int64_t modcr_linear_bwd_input_workspace(int32_t M, int32_t N, int32_t K);
 int modcr_linear_bwd_input(const void* dY, int64_t lddy, int32_t dy_dtype, const void* W, int64_t ldw,
                            void* dX, int64_t lddx, int32_t M, int32_t N, int32_t K, int32_t dtype,
@@ -411,6 +435,13 @@ int modcr_linear_bwd_weight(const void* dY, int64_t lddy, int32_t dy_dtype, cons
                             float* dW, float* db, int32_t M, int32_t N, int32_t K, int32_t accumulate,
                             int32_t dtype, void* workspace, int64_t workspace_bytes,
                             modcr_stream_t stream);
+int modcr_linear_bwd_weight_route(const void* dY, int64_t lddy, int32_t dy_dtype, const void* X, int64_t ldx,
+                                  const float* dW, const float* db, int32_t M, int32_t N, int32_t K, int32_t accumulate,
+                                  int32_t dtype, const void* workspace, int64_t workspace_bytes, int32_t* info);
+int modcr_linear_bwd_input_route(const void* dY, int64_t lddy, int32_t dy_dtype, const void* W, int64_t ldw,
+                                 const float* residual, int64_t ldr, const void* dX, int64_t lddx, int32_t M, int32_t N,
+                                 int32_t K, int32_t dtype, int32_t out_dtype, const void* workspace,
+                                 int64_t workspace_bytes, int32_t* info);
 /* y = LN(x + residual): dX (= d residual) from dY; dgamma/dbeta fp32, ACCUMULATED (atomics; the
  * caller zeroes them).  residual may be NULL.  All fp32. */
 int modcr_layernorm_bwd(const float* dY, const float* x, const float* residual, const float* gamma,

@@ -1842,19 +1842,24 @@ inline int rev_walk_for(const LinearArgs& p) {
     return (int64_t)p.M * p.K * 2 > ((int64_t)256 << 20);
 }
 
+// Reserve `bytes` of dynamic LDS for `kernel`, once per device: `configured` is the calling launcher's own (per instantiation) flags.
+int reserve_lds(bool (&configured)[MODCR_MAX_DEV], const void* kernel, int bytes, const char* what) {
+    bool& done = configured[modcr_device_index()];
+    if (done) return MODCR_OK;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+        modcr_set_error("%s: cannot reserve %d bytes of LDS: %s", what, bytes, hipGetErrorString(e));
+        return MODCR_ERR_LAUNCH;
+    }
+    done = true;
+    return MODCR_OK;
+}
+
 template <int ACT, int RES, int OUT, int DIRECT>
 int launch_t192d(LinearArgs p, hipStream_t st) {
-    static bool configured_dev[MODCR_MAX_DEV] = {};
-    bool& configured = configured_dev[modcr_device_index()];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_t192_kernel<ACT, RES, OUT, DIRECT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, T192::SMEM);
-        if (e != hipSuccess) {
-            modcr_set_error("linear: cannot reserve %d bytes of LDS: %s", T192::SMEM, hipGetErrorString(e));
-            return MODCR_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    static bool configured[MODCR_MAX_DEV] = {};
+    const int rc = reserve_lds(configured, reinterpret_cast<const void*>(&linear_bf16_t192_kernel<ACT, RES, OUT, DIRECT>), T192::SMEM, "linear");
+    if (rc != MODCR_OK) return rc;
     p.tiles_m = (p.M + 191) / 192;
     p.tiles_n = p.N / 384;
     const int ntiles = p.tiles_m * p.tiles_n;
@@ -1890,9 +1895,10 @@ bool t192_ok(const LinearArgs& p) {
 // 32 workgroups of an XCD work on 2.7 tile rows x all 12 column tiles at a time: 4.7 MB of weights against 4 MB of L2, re-fetched every
 // round (profiles/r03_gemm_pmc_ffn_up.txt: 2 x FETCH_SIZE = 1.06 GB against 146 MB of operands).  Groups of tiles_n / 2 (or / 4)
 // columns whose weight slice is <= 2.5 MB keep that slice resident: the activations are then read once per group.  Returns the column
-// tiles per group, 0 = row-major walk.
-int p8_ngroup(const LinearArgs& p) {
-    const int tiles_m = (p.M + 255) / 256, tiles_n = p.N / 256;
+// tiles per group, 0 = row-major walk.  bn = the tile width: 256, or the 128 of the tuning build's dual-workgroup kernel (whole 256-row
+// tiles, never split: d4_shape).
+int column_groups(const LinearArgs& p, int bn) {
+    const int tiles_m = (p.M + 255) / 256, tiles_n = p.N / bn;
     int ngroup = 0;
     if (!p.k_tiles_per_split && tiles_m >= 64) {
         const int64_t wbytes = (int64_t)p.N * p.K * 2;
@@ -1906,17 +1912,9 @@ int p8_ngroup(const LinearArgs& p) {
 
 template <int ACT, int RES, int OUT, int DIRECT, int TN = 0, int SPEC = 0>
 int launch_p8d(LinearArgs p, hipStream_t st) {
-    static bool configured_dev[MODCR_MAX_DEV] = {};
-    bool& configured = configured_dev[modcr_device_index()];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_p8_kernel<ACT, RES, OUT, DIRECT, TN, SPEC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, P8::SMEM);
-        if (e != hipSuccess) {
-            modcr_set_error("linear: cannot reserve %d bytes of LDS: %s", P8::SMEM, hipGetErrorString(e));
-            return MODCR_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    static bool configured[MODCR_MAX_DEV] = {};
+    const int rc = reserve_lds(configured, reinterpret_cast<const void*>(&linear_bf16_p8_kernel<ACT, RES, OUT, DIRECT, TN, SPEC>), P8::SMEM, "linear");
+    if (rc != MODCR_OK) return rc;
     if constexpr (TN == 2) {
         // the half-TN staging replaces a K-tile past kvalid by the last valid one: exact only for whole K-tiles of tokens (and an A operand
         // zero-padded past kvalid, which modcr_linear_bwd_weight's transposes guarantee)
@@ -1932,7 +1930,7 @@ int launch_p8d(LinearArgs p, hipStream_t st) {
     p.pf_next = modcr_knob_int("MODCR_GEMM_PF", 0);                      // tuning build only: A/B of the epilogue's L2 warm-up (off)
     p.stpol = modcr_knob_int("MODCR_GEMM_STPOL", 0);                     // tuning build only
     p.rev_walk = (p.k_tiles_per_split || TN) ? 0 : rev_walk_for(p);
-    p.ngroup = p8_ngroup(p);
+    p.ngroup = column_groups(p, 256);
     // persistent: one workgroup per CU (a multiple of 8 so a workgroup's tiles stay on one XCD's chunk)
     const int nwg = p.tiles_m * p.tiles_n * (p.k_tiles_per_split ? (p.K >> 6) / p.k_tiles_per_split : 1);
     const int ncu = modcr_device_cus();
@@ -1947,35 +1945,14 @@ inline bool d4_shape(const LinearArgs& p) {
            (p.lda % 8) == 0 && (p.ldw % 8) == 0 && (!p.bias || modcr_aligned16(p.bias)) &&
            (int64_t)p.lda * 64 * 2 < (1ll << 31) && (int64_t)p.ldw * 64 * 2 < (1ll << 31) && (int64_t)p.ldc * 32 < (1ll << 31);
 }
-// column groups as in p8_ngroup (a group's weight slice <= 2.5 MB stays in the XCD's L2), over 128-column tiles
-int d4_ngroup(const LinearArgs& p) {
-    const int tiles_m = p.M / 256, tiles_n = p.N / 128;
-    int ngroup = 0;
-    if (tiles_m >= 64) {
-        const int64_t wbytes = (int64_t)p.N * p.K * 2;
-        for (int parts = 2; parts <= 4 && wbytes > (3 << 20); parts *= 2)
-            if (tiles_n % parts == 0 && wbytes / parts <= (5 << 19)) { ngroup = tiles_n / parts; break; }
-    }
-    if (modcr_knob_set("MODCR_GEMM_NGROUP")) ngroup = modcr_knob_int("MODCR_GEMM_NGROUP", 0);       // tuning build only
-    if (ngroup < 0 || (ngroup > 0 && (tiles_n % ngroup) != 0)) ngroup = 0;
-    return ngroup;
-}
 template <int ACT, int OUT>
 int launch_d4(LinearArgs p, hipStream_t st) {
-    static bool configured_dev[MODCR_MAX_DEV] = {};
-    bool& configured = configured_dev[modcr_device_index()];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_d4_kernel<ACT, OUT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, D4::SMEM);
-        if (e != hipSuccess) {
-            modcr_set_error("linear (d4): cannot reserve %d bytes of LDS: %s", D4::SMEM, hipGetErrorString(e));
-            return MODCR_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    static bool configured[MODCR_MAX_DEV] = {};
+    const int rc = reserve_lds(configured, reinterpret_cast<const void*>(&linear_bf16_d4_kernel<ACT, OUT>), D4::SMEM, "linear (d4)");
+    if (rc != MODCR_OK) return rc;
     p.tiles_m = p.M / 256;
     p.tiles_n = p.N / 128;
-    p.ngroup = d4_ngroup(p);
+    p.ngroup = column_groups(p, 128);
     p.order = modcr_knob_int("MODCR_GEMM_ORDER", 0);                      // tuning build only
     const int nwg = p.tiles_m * p.tiles_n;
     const int slots = 2 * (modcr_device_cus() & ~7);          // two workgroups per CU
@@ -2029,17 +2006,9 @@ bool p8_ok(const LinearArgs& p) {
 
 template <typename T, int ACT, int RES, int OUT>
 int launch_linear(LinearArgs p, hipStream_t st) {
-    static bool configured_dev[MODCR_MAX_DEV] = {};
-    bool& configured = configured_dev[modcr_device_index()];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_kernel<T, ACT, RES, OUT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, T::SMEM);
-        if (e != hipSuccess) {
-            modcr_set_error("linear: cannot reserve %d bytes of LDS: %s", T::SMEM, hipGetErrorString(e));
-            return MODCR_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    static bool configured[MODCR_MAX_DEV] = {};
+    const int rc = reserve_lds(configured, reinterpret_cast<const void*>(&linear_bf16_kernel<T, ACT, RES, OUT>), T::SMEM, "linear");
+    if (rc != MODCR_OK) return rc;
     p.tiles_m = (p.M + T::BM - 1) / T::BM;
     p.tiles_n = (p.N + T::BN - 1) / T::BN;
     p.order = modcr_knob_int("MODCR_GEMM_ORDER", 0);                      // tuning build only
@@ -2102,12 +2071,12 @@ LinearRoute route_bf16(const LinearArgs& p) {
                 if (r.variant == P8_D4) {       // (launch_d4: column groups, no reversed walk)
                     r.kernel = MODCR_ROUTE_D4;
                     r.variant = 0;
-                    r.ngroup = d4_ngroup(p);
+                    r.ngroup = column_groups(p, 128);
                     return r;
                 }
 #endif
                 r.kernel = MODCR_ROUTE_P8;
-                r.ngroup = p8_ngroup(p);
+                r.ngroup = column_groups(p, 256);
                 r.rev_walk = rev_walk_for(p);
                 return r;
             }
@@ -2352,6 +2321,19 @@ int launch_gemm_f32(const GemmF32Args& a, hipStream_t st) {
     return modcr_check_launch("gemm_f32");
 }
 
+// The arguments of a plain bf16 product C[M,N] = A[M,K] . W[N,K]^T, every field set: no bias, no residual, no activation, no
+// split, the launchers' fields zero.  The one place a LinearArgs is filled; a caller adds the few fields that differ.
+LinearArgs linear_args(const void* A, int64_t lda, const void* W, int64_t ldw, const void* C, int64_t ldc, int out_dtype, int M, int N, int K) {
+    LinearArgs p;
+    p.A = (const bf16*)A; p.lda = lda; p.W = (const bf16*)W; p.ldw = ldw; p.bias = nullptr;
+    p.res = nullptr; p.ldr = 0; p.res_dtype = 0; p.C = const_cast<void*>(C); p.ldc = ldc; p.out_dtype = out_dtype;
+    p.M = M; p.N = N; p.K = K; p.act = MODCR_ACT_NONE;
+    p.tiles_m = p.tiles_n = 0; p.ngroup = p.order = 0;
+    p.vec_ok = (ldc % 4 == 0) && modcr_aligned16(C);
+    p.k_tiles_per_split = 0; p.split_stride = 0;
+    return p;
+}
+
 // argument checks of modcr_linear_fwd / modcr_linear_route, and the arguments of the product: `p` (bf16) or `a` (fp32)
 int linear_setup(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const void* residual, int64_t ldr,
                  int32_t res_dtype, const void* C, int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t act, int32_t dtype,
@@ -2365,12 +2347,9 @@ int linear_setup(const void* A, int64_t lda, const void* W, int64_t ldw, const f
                       "linear_fwd(bf16): K=%d must be a multiple of 64, lda=%lld ldw=%lld multiples of 8 "
                       "(zero-pad with modcr_cast_pad)", K, (long long)lda, (long long)ldw);
         MODCR_REQUIRE(modcr_aligned16(A) && modcr_aligned16(W), "linear_fwd(bf16): 16-byte alignment");
-        p.A = (const bf16*)A; p.lda = lda; p.W = (const bf16*)W; p.ldw = ldw; p.bias = bias;
-        p.res = residual; p.ldr = ldr; p.res_dtype = res_dtype; p.C = const_cast<void*>(C); p.ldc = ldc;
-        p.out_dtype = out_dtype; p.M = M; p.N = N; p.K = K; p.act = act;
-        p.tiles_m = p.tiles_n = 0;
-        p.vec_ok = (ldc % 4 == 0) && modcr_aligned16(C) && (!residual || ((ldr % 4 == 0) && modcr_aligned16(residual)));
-        p.k_tiles_per_split = 0; p.split_stride = 0;
+        p = linear_args(A, lda, W, ldw, C, ldc, out_dtype, M, N, K);
+        p.bias = bias; p.res = residual; p.ldr = ldr; p.res_dtype = res_dtype; p.act = act;
+        p.vec_ok = p.vec_ok && (!residual || ((ldr % 4 == 0) && modcr_aligned16(residual)));
         return MODCR_OK;
     }
     MODCR_REQUIRE(dtype == MODCR_F32, "linear_fwd: unknown dtype %d", dtype);
@@ -2731,6 +2710,20 @@ BwdWeightPlan plan_bwd_weight(int M, int N, int K) {
     p.total = p.off_dbp + align_up((p.Mp / 64) * (int64_t)(N > K ? N : K) * 4, 256);
     return p;
 }
+// the TN form's plan (tuning build): no transposes, the partials alone.  splits: a divisor of the 64-token K-tiles with an even
+// quotient >= 4, closest to ~2 rounds of 256 work items, at most 32; splits = 0: the token count has none
+BwdWeightPlan plan_bwd_weight_tn(int M, int N, int K) {
+    BwdWeightPlan p = {M, 0, 0, 0, 0, 0, 0};
+    const int ktiles = M / 64, tiles = (N / 256) * (K / 256);
+    for (int sp = 1; sp <= 32 && sp <= ktiles; ++sp) {
+        if (ktiles % sp) continue;
+        const int kps = ktiles / sp;
+        if ((kps & 1) || kps < 4) continue;
+        if (!p.splits || abs(sp * tiles - 512) < abs(p.splits * tiles - 512)) p.splits = sp;
+    }
+    if (p.splits) { p.kps = ktiles / p.splits; p.total = (int64_t)p.splits * N * K * 4; }
+    return p;
+}
 
 }  // namespace
 
@@ -2771,11 +2764,8 @@ extern "C" int modcr_linear_splitk_fwd(const void* A, int64_t lda, const void* W
     MODCR_REQUIRE((lda % 8) == 0 && (ldw % 8) == 0 && modcr_aligned16(A) && modcr_aligned16(W) && modcr_aligned16(workspace),
                   "linear_splitk_fwd: 16-byte alignment");
     hipStream_t st = (hipStream_t)stream;
-    LinearArgs p;
-    p.A = (const bf16*)A; p.lda = lda; p.W = (const bf16*)W; p.ldw = ldw; p.bias = nullptr; p.res = nullptr; p.ldr = 0;
-    p.res_dtype = 0; p.C = workspace; p.ldc = N; p.out_dtype = MODCR_F32; p.M = M; p.N = N; p.K = K;
-    p.act = MODCR_ACT_NONE; p.tiles_m = p.tiles_n = 0; p.vec_ok = 1;
-    p.k_tiles_per_split = pl.kps; p.split_stride = (int64_t)M * N;
+    LinearArgs p = linear_args(A, lda, W, ldw, workspace, N, MODCR_F32, M, N, K);
+    p.vec_ok = 1; p.k_tiles_per_split = pl.kps; p.split_stride = (int64_t)M * N;
     MODCR_REQUIRE(p8_ok(p), "linear_splitk_fwd: shape not supported by the persistent kernel");
     int rc = launch_p8<MODCR_ACT_NONE, 0, MODCR_F32>(p, st);
     if (rc != MODCR_OK) return rc;
@@ -2788,21 +2778,49 @@ extern "C" int modcr_linear_splitk_fwd(const void* A, int64_t lda, const void* W
     return modcr_check_launch("reduce_bias_act");
 }
 
-// MFMA route for dW: transpose dY and X to [*, M] bf16 (contraction dim contiguous), NT GEMM with
-// split-K into fp32 partials, reduce.  db = row sums of dY^T.
-extern "C" int64_t modcr_linear_bwd_weight_workspace(int32_t M, int32_t N, int32_t K) {
-    const int64_t a = plan_bwd_weight(M, N, K).total, b = plan_bwd_weight(M, K, N).total;       // (the swapped form of a dY wider than X)
-    return a > b ? a : b;
+// ---- dX[M,K] = dY[M,N] . W[N,K] (+ res) -------------------------------------------------------------------------------------
+// MFMA route: the NT product (M, K, Np) of dY (bf16, N zero-padded to Np = a multiple of 64) with W^T [K,Np]: through the
+// dispatcher (modcr_linear_fwd), or split-K over the chip for few rows.  Without a workspace that holds the plan, or N < 64:
+// the exact fp32 kernel.
+namespace {
+// the workspace: W^T [K,Np] | bf16 dY [M,Np] (fp32 dY only) | split-K partials of the few-row case
+struct BwdInputPlan { int64_t Np, off_wt, off_dy, off_sk, sk_bytes, total; };
+BwdInputPlan plan_bwd_input(int M, int N, int K) {
+    BwdInputPlan pl = {align_up(N, 64), 0, 0, 0, 0, 0};
+    pl.off_dy = align_up((int64_t)K * pl.Np * 2, 256);
+    pl.off_sk = pl.off_dy + align_up((int64_t)M * pl.Np * 2, 256);
+    pl.sk_bytes = plan_splitk_fwd(M, K, (int)pl.Np).bytes;
+    pl.total = pl.off_sk + pl.sk_bytes;
+    return pl;
 }
-extern "C" int64_t modcr_linear_splitk_workspace(int32_t M, int32_t N, int32_t K);
-extern "C" int modcr_linear_splitk_fwd(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C,
-                                       int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t act, int32_t out_dtype,
-                                       void* workspace, int64_t workspace_bytes, modcr_stream_t stream);
-extern "C" int64_t modcr_linear_bwd_input_workspace(int32_t M, int32_t N, int32_t K) {
-    const int64_t Np = align_up(N, 64);
-    // W^T | bf16 dY | split-K partials of the few-row case (dX [M,K] = dY [M,Np] . W^T: the product (M, K, Np))
-    return align_up((int64_t)K * Np * 2, 256) + align_up((int64_t)M * Np * 2, 256) + modcr_linear_splitk_workspace(M, K, (int32_t)Np);
+
+struct BwdInputCall {
+    const void* dY; int64_t lddy; int dy_dtype; const void* W; int64_t ldw; const float* res; int64_t ldr; void* dX; int64_t lddx;
+    int M, N, K, dtype, out_dtype; void* workspace; int64_t workspace_bytes;
+};
+// form = MODCR_BWD_INPUT_*; dyb / lddyb = the product's bf16 dY operand: the cast-padded copy in the workspace or dY itself
+struct BwdInputRoute { int form, cast_pad; BwdInputPlan plan; bf16* wt; bf16* dyb; int64_t lddyb; };
+
+// The route of a dX call and its refusals: the one place the choice is made.  Launches nothing, dereferences nothing.
+int route_bwd_input(const BwdInputCall& c, BwdInputRoute& r) {
+    MODCR_REQUIRE(c.dY && c.W && c.dX && c.M > 0 && c.N > 0 && c.K > 0, "linear_bwd_input: bad arguments");
+    r.plan = plan_bwd_input(c.M, c.N, c.K);
+    r.form = MODCR_BWD_INPUT_F32; r.cast_pad = 0;
+    r.wt = (bf16*)((char*)c.workspace + r.plan.off_wt); r.dyb = (bf16*)c.dY; r.lddyb = c.lddy;
+    if (!c.workspace || c.workspace_bytes < r.plan.total || c.N < 64) return MODCR_OK;
+    if (c.dy_dtype == MODCR_F32) {
+        r.cast_pad = 1; r.dyb = (bf16*)((char*)c.workspace + r.plan.off_dy); r.lddyb = r.plan.Np;
+    } else {
+        // bf16 dY: pad columns by a transposing round trip is overkill; require N % 64 == 0
+        MODCR_REQUIRE(c.N % 64 == 0 && c.lddy % 8 == 0, "linear_bwd_input: bf16 dY needs N %% 64 == 0");
+    }
+    const bool few_rows = !c.res && r.plan.sk_bytes && (r.lddyb % 8) == 0 && modcr_aligned16(r.dyb);      // split-K over the chip
+    r.form = few_rows ? MODCR_BWD_INPUT_SPLITK : MODCR_BWD_INPUT_FWD;
+    return MODCR_OK;
 }
+}  // namespace
+
+extern "C" int64_t modcr_linear_bwd_input_workspace(int32_t M, int32_t N, int32_t K) { return plan_bwd_input(M, N, K).total; }
 
 extern "C" int modcr_linear_bwd_input(const void* dY, int64_t lddy, int32_t dy_dtype, const void* W,
                                       int64_t ldw, void* dX, int64_t lddx, int32_t M, int32_t N, int32_t K,
@@ -2817,43 +2835,171 @@ extern "C" int modcr_linear_bwd_input(const void* dY, int64_t lddy, int32_t dy_d
 int modcr_linear_bwd_input_res(const void* dY, int64_t lddy, int32_t dy_dtype, const void* W, int64_t ldw, const float* res,
                                int64_t ldr, void* dX, int64_t lddx, int32_t M, int32_t N, int32_t K, int32_t dtype,
                                int32_t out_dtype, void* workspace, int64_t workspace_bytes, modcr_stream_t stream) {
-    MODCR_REQUIRE(dY && W && dX && M > 0 && N > 0 && K > 0, "linear_bwd_input: bad arguments");
-    const int64_t Np = align_up(N, 64);
-    const int64_t off_sk = align_up((int64_t)K * Np * 2, 256) + align_up((int64_t)M * Np * 2, 256);
-    const int64_t sk_bytes = modcr_linear_splitk_workspace(M, K, (int32_t)Np);
-    const int64_t need = off_sk + sk_bytes;
-    if (workspace && workspace_bytes >= need && N >= 64) {
-        // dX[M,K] = dY[M,N] . W[N,K] = NT product of dY (bf16, N padded to 64) with W^T [K,N]
-        hipStream_t st = (hipStream_t)stream;
-        bf16* wt = (bf16*)workspace;
-        bf16* dyb = (bf16*)((char*)workspace + align_up((int64_t)K * Np * 2, 256));
-        int rc = transpose_to_bf16(W, dtype, ldw, wt, Np, N, K, (int)Np, st);
-        if (rc != MODCR_OK) return rc;
-        if (dy_dtype == MODCR_F32) {
-            rc = modcr_cast_pad((const float*)dY, lddy, dyb, Np, M, N, (int)Np, MODCR_BF16, stream);
-        } else {
-            // bf16 dY: pad columns by a transposing round trip is overkill; require N % 64 == 0
-            MODCR_REQUIRE(N % 64 == 0 && lddy % 8 == 0, "linear_bwd_input: bf16 dY needs N %% 64 == 0");
-            dyb = (bf16*)dY;
-        }
-        if (rc != MODCR_OK) return rc;
-        if (!res && sk_bytes && ((dy_dtype == MODCR_F32 ? Np : lddy) % 8) == 0 && modcr_aligned16(dyb))      // few rows: split-K over the chip
-            return modcr_linear_splitk_fwd(dyb, dy_dtype == MODCR_F32 ? Np : lddy, wt, Np, nullptr, dX, lddx, M, K, (int)Np,
-                                           MODCR_ACT_NONE, out_dtype, (char*)workspace + off_sk, sk_bytes, stream);
-        return modcr_linear_fwd(dyb, dy_dtype == MODCR_F32 ? Np : lddy, wt, Np, nullptr, res, ldr, MODCR_F32, dX, lddx, M, K,
-                                (int)Np, MODCR_ACT_NONE, MODCR_BF16, out_dtype, stream);
+    const BwdInputCall c = {dY, lddy, dy_dtype, W, ldw, res, ldr, dX, lddx, M, N, K, dtype, out_dtype, workspace, workspace_bytes};
+    BwdInputRoute r;
+    int rc = route_bwd_input(c, r);
+    if (rc != MODCR_OK) return rc;
+    if (r.form == MODCR_BWD_INPUT_F32) {
+        // dX[m,k] = sum_n dY[m,n] W[n,k]
+        GemmF32Args a;
+        a.A = dY; a.sam = lddy; a.sak = 1; a.a_dtype = dy_dtype;
+        a.B = W; a.sbk = ldw; a.sbn = 1; a.b_dtype = dtype;
+        a.bias = nullptr; a.res = res; a.ldr = ldr; a.res_dtype = MODCR_F32;
+        a.C = dX; a.ldc = lddx; a.out_dtype = out_dtype; a.M = M; a.N = K; a.K = N; a.act = 0;
+        a.accumulate = 0;
+        return launch_gemm_f32(a, (hipStream_t)stream);
     }
-    // dX[m,k] = sum_n dY[m,n] W[n,k]
-    GemmF32Args a;
-    a.A = dY; a.sam = lddy; a.sak = 1; a.a_dtype = dy_dtype;
-    a.B = W; a.sbk = ldw; a.sbn = 1; a.b_dtype = dtype;
-    a.bias = nullptr; a.res = res; a.ldr = ldr; a.res_dtype = MODCR_F32;
-    a.C = dX; a.ldc = lddx; a.out_dtype = out_dtype; a.M = M; a.N = K; a.K = N; a.act = 0;
-    a.accumulate = 0;
-    return launch_gemm_f32(a, (hipStream_t)stream);
+    const BwdInputPlan& pl = r.plan;
+    rc = transpose_to_bf16(W, dtype, ldw, r.wt, pl.Np, N, K, (int)pl.Np, (hipStream_t)stream);
+    if (rc != MODCR_OK) return rc;
+    if (r.cast_pad) {
+        rc = modcr_cast_pad((const float*)dY, lddy, r.dyb, pl.Np, M, N, (int)pl.Np, MODCR_BF16, stream);
+        if (rc != MODCR_OK) return rc;
+    }
+    if (r.form == MODCR_BWD_INPUT_SPLITK)
+        return modcr_linear_splitk_fwd(r.dyb, r.lddyb, r.wt, pl.Np, nullptr, dX, lddx, M, K, (int)pl.Np, MODCR_ACT_NONE, out_dtype,
+                                       (char*)workspace + pl.off_sk, pl.sk_bytes, stream);
+    return modcr_linear_fwd(r.dyb, r.lddyb, r.wt, pl.Np, nullptr, res, ldr, MODCR_F32, dX, lddx, M, K, (int)pl.Np, MODCR_ACT_NONE,
+                            MODCR_BF16, out_dtype, stream);
 }
 
+extern "C" int modcr_linear_bwd_input_route(const void* dY, int64_t lddy, int32_t dy_dtype, const void* W, int64_t ldw,
+                                            const float* residual, int64_t ldr, const void* dX, int64_t lddx, int32_t M, int32_t N,
+                                            int32_t K, int32_t dtype, int32_t out_dtype, const void* workspace,
+                                            int64_t workspace_bytes, int32_t* info) {
+    MODCR_REQUIRE(info, "linear_bwd_input_route: null info");
+    const BwdInputCall c = {dY, lddy, dy_dtype, W, ldw, residual, ldr, const_cast<void*>(dX), lddx, M, N, K, dtype, out_dtype,
+                            const_cast<void*>(workspace), workspace_bytes};
+    BwdInputRoute r;
+    const int rc = route_bwd_input(c, r);
+    if (rc != MODCR_OK) return rc;
+    info[0] = r.form; info[1] = r.cast_pad;
+    info[2] = info[3] = info[4] = info[5] = 0;
+    const BwdInputPlan& pl = r.plan;
+    if (r.form == MODCR_BWD_INPUT_FWD)
+        return modcr_linear_route(r.dyb, r.lddyb, r.wt, pl.Np, nullptr, residual, ldr, MODCR_F32, dX, lddx, M, K, (int)pl.Np,
+                                  MODCR_ACT_NONE, MODCR_BF16, out_dtype, info + 2);
+    return MODCR_OK;
+}
+
+// ---- dW[N,K] (+)= dY[M,N]^T . X[M,K], db[N] (+)= column sums of dY ------------------------------------------------------------
+// MFMA route: operands transposed to [*, Mp] bf16 where a form needs the contraction dim contiguous, a split-K product into
+// fp32 partials, a reduction.  route_bwd_weight chooses among the forms; modcr_linear_bwd_weight runs the one step sequence.
 namespace {
+struct BwdWeightCall {
+    const void* dY; int64_t lddy; int dy_dtype; const void* X; int64_t ldx; float* dW; float* db;
+    int M, N, K, accumulate, dtype; void* workspace; int64_t workspace_bytes;
+};
+// form, reduce, db: MODCR_BWD_WEIGHT_* / _REDUCE_* / _DB_*; launcher: MODCR_BWD_PRODUCT_*; plan: zero for the fp32 form
+struct BwdWeightRoute { int form; BwdWeightPlan plan; int launcher, direct_out, reduce, db; };
+
+// where a form keeps dY^T, X^T, the split-K partials and the bias-gradient partials in the workspace
+struct BwdWeightBuffers { bf16* dyt; bf16* xt; float* part; float* dbp; };
+BwdWeightBuffers bwd_weight_buffers(const BwdWeightCall& c, int form, const BwdWeightPlan& pl) {
+    char* ws = (char*)c.workspace;
+    // (the swapped form transposes X alone, into the first slot of its plan: the rows of its product)
+    return {(bf16*)ws, (bf16*)(ws + (form == MODCR_BWD_WEIGHT_SWAPPED ? 0 : pl.off_xt)), (float*)(ws + pl.off_part), (float*)(ws + pl.off_dbp)};
+}
+
+// the product of a form: into dW (direct_out) or into the partials
+LinearArgs bwd_weight_product(const BwdWeightCall& c, int form, const BwdWeightPlan& pl, bool direct_out) {
+    const BwdWeightBuffers b = bwd_weight_buffers(c, form, pl);
+    const void* out = direct_out ? c.dW : b.part;
+    const int Mp = (int)pl.Mp;
+    LinearArgs p;
+    if (form == MODCR_BWD_WEIGHT_TN)                // both operands token-major
+        p = linear_args(c.dY, c.lddy, c.X, c.ldx, out, c.K, MODCR_F32, c.N, c.K, c.M);
+    else if (form == MODCR_BWD_WEIGHT_SWAPPED)      // dW^T [K,N] = X^T . dY, dY token-major
+        p = linear_args(b.xt, pl.Mp, c.dY, c.lddy, out, c.N, MODCR_F32, c.K, c.N, Mp);
+    else if (form == MODCR_BWD_WEIGHT_HALF_TN)      // dW = dY^T . X, X token-major
+        p = linear_args(b.dyt, pl.Mp, c.X, c.ldx, out, c.K, MODCR_F32, c.N, c.K, Mp);
+    else                                            // NT: dW = dY^T . (X^T)^T
+        p = linear_args(b.dyt, pl.Mp, b.xt, pl.Mp, out, c.K, MODCR_F32, c.N, c.K, Mp);
+    if (form == MODCR_BWD_WEIGHT_SWAPPED || form == MODCR_BWD_WEIGHT_HALF_TN) p.kvalid = c.M;
+    p.vec_ok = form == MODCR_BWD_WEIGHT_NT ? (c.K % 4 == 0) : 1;
+    p.k_tiles_per_split = pl.kps; p.split_stride = (int64_t)c.N * c.K;
+    return p;
+}
+
+// The route of a dW call: the one place the form, its plan, the product's launcher, the reduction and the way db is formed are
+// chosen, and the only reader of MODCR_GEMM_TN / MODCR_GEMM_HALF_TN.  Launches nothing, dereferences nothing.  The forms are tried
+// in the order TN, SWAPPED, HALF_TN, NT, F32; one that fails a late condition (the persistent kernel's shapes, a workspace smaller
+// than its plan) falls to the next, so an undersized workspace ends in NT or F32 without an error.
+BwdWeightRoute route_bwd_weight(const BwdWeightCall& c) {
+    const int M = c.M, N = c.N, K = c.K;
+    const bool bf16_both = c.dy_dtype == MODCR_BF16 && c.dtype == MODCR_BF16;
+    // an operand the persistent kernel can stage token-major: 16-byte rows, 32-bit byte offsets within a K-tile
+    const bool dy_tm = (c.lddy % 8) == 0 && modcr_aligned16(c.dY) && (int64_t)64 * c.lddy * 2 + (int64_t)N * 2 < (1ll << 31);
+    const bool x_tm = (c.ldx % 8) == 0 && modcr_aligned16(c.X) && (int64_t)64 * c.ldx * 2 + (int64_t)K * 2 < (1ll << 31);
+    BwdWeightRoute r = {};
+    r.launcher = MODCR_BWD_PRODUCT_SPLITK;
+    r.reduce = MODCR_BWD_REDUCE_PLAIN;
+
+    // TN (opt-in, MODCR_GEMM_TN=1): both operands stay token-major (no transposes): the persistent 256 x 256 kernel
+    // stages [64 tokens][128 features] half-tiles and reads its MFMA fragments with transposed LDS reads.  Needs bf16
+    // operands, whole 256 x 256 output tiles and a token count that splits into equal even runs of 64-token K-tiles.
+    // Correct (tests) and conflict-free (PMC), but the product itself runs 25 % slower than the row-major form (209 vs
+    // 167 us averaged over the encoder shapes, twice the LDS read instructions) and its separate column-sum pass costs
+    // what the two transposes it saves cost: 323 vs 320 us per dW end to end -- off by default.
+    const int tn_on = modcr_knob_int("MODCR_GEMM_TN", 0);                 // tuning build only
+    if (tn_on && c.workspace && bf16_both && (N % 256) == 0 && (K % 256) == 0 && (M % 128) == 0 && dy_tm && x_tm) {
+        const BwdWeightPlan pt = plan_bwd_weight_tn(M, N, K);
+        if (pt.splits && pt.total <= c.workspace_bytes) {
+            r.form = MODCR_BWD_WEIGHT_TN; r.plan = pt;
+            r.db = c.db ? MODCR_BWD_DB_ATOMIC : MODCR_BWD_DB_NONE;
+            return r;
+        }
+    }
+    // SWAPPED, dY wider than X: the product is formed TRANSPOSED, dW^T [K,N] = X^T . dY, so that the wide operand is the one that
+    // stays token-major (as in the half-TN form below) and only X is transposed; a transposing reduction writes dW.  The bias
+    // gradient, which the transpose of dY used to carry, is a column-sum pass of its own when the caller wants it here
+    // (modcr_ffn_up_du_bwd has it from the producing GEMM's epilogue): [3072 x 768] 591 -> 465 us without it, [2304 x 768]
+    // 499 -> 363 us + the pass.
+    const int half_knob = modcr_knob_int("MODCR_GEMM_HALF_TN", 1);        // tuning build: 0 / 2 = never / whenever the shape allows
+    if (N > K && c.workspace && bf16_both && half_knob != 0 && (N % 256) == 0 && (K % 256) == 0 && K >= 256 && (M % 64) == 0 && M >= 256 && dy_tm) {
+        const BwdWeightPlan ps = plan_bwd_weight(M, K, N);              // rows of the product = X features
+        if (c.workspace_bytes >= ps.total && ps.kps >= 4 && !(ps.kps & 1) && (int64_t)K * ps.Mp < (1ll << 31) &&
+            p8_ok(bwd_weight_product(c, MODCR_BWD_WEIGHT_SWAPPED, ps, false))) {
+            r.form = MODCR_BWD_WEIGHT_SWAPPED; r.plan = ps;
+            r.reduce = MODCR_BWD_REDUCE_TRANSPOSED;
+            r.db = c.db ? MODCR_BWD_DB_BLOCK_FOLD : MODCR_BWD_DB_NONE;
+            return r;
+        }
+    }
+    const BwdWeightPlan pl = plan_bwd_weight(M, N, K);
+    if (!c.workspace || c.workspace_bytes < pl.total) {
+        r.form = MODCR_BWD_WEIGHT_F32;
+        r.launcher = MODCR_BWD_PRODUCT_F32; r.direct_out = 1; r.reduce = MODCR_BWD_REDUCE_NONE;
+        r.db = c.db ? MODCR_BWD_DB_COLSUM : MODCR_BWD_DB_NONE;
+        return r;
+    }
+    // dY is transposed.  db rides along with that pass (column sums of the tile the kernel holds) where its 16-byte path applies;
+    // one split: the product IS dW, no reduce pass
+    const bool fused_db = c.db && (N % 8) == 0 && (c.lddy % 8) == 0 && (pl.Mp % 64) == 0 && modcr_aligned16(c.dY) && modcr_aligned16(c.workspace);
+    r.plan = pl;
+    r.direct_out = pl.splits == 1 && !c.accumulate;
+    r.reduce = r.direct_out ? MODCR_BWD_REDUCE_NONE : MODCR_BWD_REDUCE_PLAIN;
+    r.db = !c.db ? MODCR_BWD_DB_NONE : !fused_db ? MODCR_BWD_DB_ROWSUM : r.direct_out ? MODCR_BWD_DB_FUSED_FOLD : MODCR_BWD_DB_FUSED_REDUCE;
+    // HALF_TN: X stays token-major, as the forward saved it (its transpose is the larger half of the transposed bytes of a
+    // layer: x, ctx, a and the [M, 4H] FFN intermediate) -- the 256 x 256 kernel stages [64 tokens][128 features] images of it
+    // and reads the fragments with ds_read_b64_tr_b16; dY^T is still transposed (the bias gradient rides on that pass and its
+    // zero padding covers the tokens past M, for which the kernel re-reads X's last K-tile).  The transposed reads make the
+    // product ~20 % slower (205 vs 170 us averaged over the encoder shapes at M = 92160), so the form is taken where X is at
+    // least as wide as dY (K >= N: the transpose it saves is at least as large as the one that stays) -- dW of BertSelfOutput
+    // 236 -> 190 us, of BertOutput 599 -> 470 us; [3072 x 768] (601 -> 644 us) and [2304 x 768] (490 -> 478 us) keep both
+    // transposes (tools/run_bench_dw.sh).
+    const bool half_tn = half_knob != 0 && (K >= N || half_knob == 2) && c.dtype == MODCR_BF16 && (N % 256) == 0 && N >= 256 && (K % 256) == 0 &&
+                         (M % 64) == 0 && M >= 256 && x_tm && pl.kps >= 4 && !(pl.kps & 1) && pl.splits >= 1 && (int64_t)N * pl.Mp < (1ll << 31);
+    if (half_tn && p8_ok(bwd_weight_product(c, MODCR_BWD_WEIGHT_HALF_TN, pl, false))) {     // (asked of the partials, also when the product writes dW)
+        r.form = MODCR_BWD_WEIGHT_HALF_TN;
+        return r;
+    }
+    // NT: both operands transposed; shapes the persistent kernel does not take go through the dispatcher
+    r.form = MODCR_BWD_WEIGHT_NT;
+    if (!p8_ok(bwd_weight_product(c, MODCR_BWD_WEIGHT_NT, pl, r.direct_out))) r.launcher = MODCR_BWD_PRODUCT_DISPATCH;
+    return r;
+}
+
 // the split-K reduction of a weight-gradient product (+ the bias-gradient fold as extra blocks, f.db != NULL)
 int launch_reduce_partials(const float* part, int splits, int64_t nel, float* dW, int accumulate, const DbFold& f, hipStream_t st) {
     const int nb_main = (int)((nel + 255) / 256), nb_fold = f.db ? (f.N + DBF_COLS - 1) / DBF_COLS : 0;
@@ -2866,167 +3012,111 @@ int launch_db_fold(const DbFold& f, hipStream_t st) {
 }
 }  // namespace
 
+extern "C" int64_t modcr_linear_bwd_weight_workspace(int32_t M, int32_t N, int32_t K) {
+    const int64_t a = plan_bwd_weight(M, N, K).total, b = plan_bwd_weight(M, K, N).total;       // (the swapped form of a dY wider than X)
+    return a > b ? a : b;
+}
+
 extern "C" int modcr_linear_bwd_weight(const void* dY, int64_t lddy, int32_t dy_dtype, const void* X,
                                        int64_t ldx, float* dW, float* db, int32_t M, int32_t N, int32_t K,
                                        int32_t accumulate, int32_t dtype, void* workspace, int64_t workspace_bytes,
                                        modcr_stream_t stream) {
     MODCR_REQUIRE(dY && X && dW && M > 0 && N > 0 && K > 0, "linear_bwd_weight: bad arguments");
-    // TN route (opt-in, MODCR_GEMM_TN=1): both operands stay token-major (no transposes): the persistent 256 x 256 kernel
-    // stages [64 tokens][128 features] half-tiles and reads its MFMA fragments with transposed LDS reads.  Needs bf16
-    // operands, whole 256 x 256 output tiles and a token count that splits into equal even runs of 64-token K-tiles.
-    // Correct (tests) and conflict-free (PMC), but the product itself runs 25 % slower than the row-major form (209 vs
-    // 167 us averaged over the encoder shapes, twice the LDS read instructions) and its separate column-sum pass costs
-    // what the two transposes it saves cost: 323 vs 320 us per dW end to end -- off by default.
-    const int tn_on = modcr_knob_int("MODCR_GEMM_TN", 0);                 // tuning build only
-    if (tn_on && workspace && dy_dtype == MODCR_BF16 && dtype == MODCR_BF16 && (N % 256) == 0 && (K % 256) == 0 && (M % 128) == 0 &&
-        (lddy % 8) == 0 && (ldx % 8) == 0 && modcr_aligned16(dY) && modcr_aligned16(X) &&
-        (int64_t)64 * lddy * 2 + (int64_t)N * 2 < (1ll << 31) && (int64_t)64 * ldx * 2 + (int64_t)K * 2 < (1ll << 31)) {
-        const int ktiles = M / 64, tiles = (N / 256) * (K / 256);
-        // splits: a divisor of ktiles with an even quotient >= 4, closest to ~2 rounds of 256 work items, at most 32
-        int best = 0;
-        for (int sp = 1; sp <= 32 && sp <= ktiles; ++sp) {
-            if (ktiles % sp) continue;
-            const int kps = ktiles / sp;
-            if ((kps & 1) || kps < 4) continue;
-            if (!best || abs(sp * tiles - 512) < abs(best * tiles - 512)) best = sp;
-        }
-        if (best && (int64_t)best * N * K * 4 <= workspace_bytes) {
-            hipStream_t st = (hipStream_t)stream;
-            float* part = (float*)workspace;
-            LinearArgs p;
-            p.A = (const bf16*)dY; p.lda = lddy; p.W = (const bf16*)X; p.ldw = ldx; p.bias = nullptr; p.res = nullptr; p.ldr = 0;
-            p.res_dtype = 0; p.C = part; p.ldc = K; p.out_dtype = MODCR_F32; p.M = N; p.N = K; p.K = M;
-            p.act = MODCR_ACT_NONE; p.tiles_m = p.tiles_n = 0; p.vec_ok = 1;
-            p.k_tiles_per_split = ktiles / best; p.split_stride = (int64_t)N * K;
-            int rc = launch_p8d<MODCR_ACT_NONE, 0, MODCR_F32, 1, 1>(p, st);
+    const BwdWeightCall c = {dY, lddy, dy_dtype, X, ldx, dW, db, M, N, K, accumulate, dtype, workspace, workspace_bytes};
+    int rc = MODCR_OK;
+    const BwdWeightRoute r = route_bwd_weight(c);
+    const BwdWeightPlan& pl = r.plan;
+    const BwdWeightBuffers b = bwd_weight_buffers(c, r.form, pl);
+    hipStream_t st = (hipStream_t)stream;
+    const DbFold no_fold = {nullptr, 0, 0, nullptr, 0};
+
+    // 1. dY^T [N, Mp], carrying the per-row-block column sums of dY when db is fused
+    const bool fused_db = r.db == MODCR_BWD_DB_FUSED_REDUCE || r.db == MODCR_BWD_DB_FUSED_FOLD;
+    int nblk = 0;
+    if (r.form == MODCR_BWD_WEIGHT_NT || r.form == MODCR_BWD_WEIGHT_HALF_TN) {
+        rc = transpose_to_bf16(dY, dy_dtype, lddy, b.dyt, pl.Mp, M, N, (int)pl.Mp, st, fused_db ? b.dbp : nullptr, &nblk);
+        if (rc != MODCR_OK) return rc;
+    }
+    const DbFold fold = fused_db ? DbFold{b.dbp, nblk, N, db, accumulate} : no_fold;
+
+    // 2. X^T [K, Mp]
+    if (r.form == MODCR_BWD_WEIGHT_NT || r.form == MODCR_BWD_WEIGHT_SWAPPED) {
+        rc = transpose_to_bf16(X, dtype, ldx, b.xt, pl.Mp, M, K, (int)pl.Mp, st);
+        if (rc != MODCR_OK) return rc;
+    }
+
+    // 3. the product: split-K partials, or dW itself
+    if (r.form == MODCR_BWD_WEIGHT_F32) {
+        // dW[n,k] = sum_m dY[m,n] X[m,k]
+        GemmF32Args a;
+        a.A = dY; a.sam = 1; a.sak = lddy; a.a_dtype = dy_dtype;
+        a.B = X; a.sbk = ldx; a.sbn = 1; a.b_dtype = dtype;
+        a.bias = nullptr; a.res = nullptr; a.ldr = 0; a.res_dtype = 0;
+        a.C = dW; a.ldc = K; a.out_dtype = MODCR_F32; a.M = N; a.N = K; a.K = M; a.act = 0;
+        a.accumulate = accumulate;
+        rc = launch_gemm_f32(a, st);
+    } else {
+        const LinearArgs p = bwd_weight_product(c, r.form, pl, r.direct_out);
+        if (r.form == MODCR_BWD_WEIGHT_TN) rc = launch_p8d<MODCR_ACT_NONE, 0, MODCR_F32, 1, 1>(p, st);
+        else if (r.form != MODCR_BWD_WEIGHT_NT) rc = launch_p8d<MODCR_ACT_NONE, 0, MODCR_F32, 1, 2>(p, st);
+        else rc = r.launcher == MODCR_BWD_PRODUCT_SPLITK ? launch_p8<MODCR_ACT_NONE, 0, MODCR_F32>(p, st) : dispatch_linear(p, st);
+    }
+    if (rc != MODCR_OK) return rc;
+
+    // 4. the reduction over the splits (the plain one folds the fused db partials in extra blocks)
+    if (r.reduce == MODCR_BWD_REDUCE_PLAIN) {
+        rc = launch_reduce_partials(b.part, pl.splits, (int64_t)N * K, dW, accumulate, fold, st);
+    } else if (r.reduce == MODCR_BWD_REDUCE_TRANSPOSED) {
+        hipLaunchKernelGGL(reduce_partials_transposed_kernel, dim3((unsigned)((N + 31) / 32), (unsigned)((K + 31) / 32)), dim3(256), 0, st,
+                           b.part, pl.splits, (int64_t)N * K, dW, K, N, accumulate);
+        rc = modcr_check_launch("reduce_partials_transposed");
+    }
+    if (rc != MODCR_OK) return rc;
+
+    // 5. db
+    switch (r.db) {
+        case MODCR_BWD_DB_FUSED_FOLD:       // no reduction to ride on: the fold of the transpose's partials as a launch of its own
+            return launch_db_fold(fold, st);
+        case MODCR_BWD_DB_ROWSUM:
+            hipLaunchKernelGGL(rowsum_bf16_kernel, dim3((N + 3) / 4), dim3(256), 0, st, b.dyt, pl.Mp, db, N, (int)pl.Mp, accumulate);
+            return modcr_check_launch("rowsum");
+        case MODCR_BWD_DB_BLOCK_FOLD: {
+            // per-256-row-block column sums of dY (plain stores) + their fold in block order -- two launches as the memset + atomic
+            // form it replaces, but reproducible; BEHIND the reduction: in front of the product, or between product and reduction
+            // (where the fold could ride on the reduction's grid), its 425-566 MB read of dY costs more than it saves
+            // (tools/ab_dw_bias.py: [2304 x 768] 421 -> 426 us; the reduction 14.6 -> 21.0 us with its partials evicted)
+            const int nb = (M + 255) / 256;
+            hipLaunchKernelGGL(colsum_bf16_block_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)nb), dim3(256), 0, st,
+                               (const bf16*)dY, lddy, b.dbp, M, N);
+            rc = modcr_check_launch("colsum_bf16_block");
             if (rc != MODCR_OK) return rc;
-            const int64_t nel = (int64_t)N * K;
-            rc = launch_reduce_partials(part, best, nel, dW, accumulate, DbFold{nullptr, 0, 0, nullptr, 0}, st);
-            if (rc != MODCR_OK || !db) return rc;
+            return launch_db_fold(DbFold{b.dbp, nb, N, db, accumulate}, st);
+        }
+        case MODCR_BWD_DB_ATOMIC:
             if (!accumulate && hipMemsetAsync(db, 0, (size_t)N * sizeof(float), st) != hipSuccess) {
                 modcr_set_error("linear_bwd_weight: hipMemsetAsync failed");
                 return MODCR_ERR_LAUNCH;
             }
             hipLaunchKernelGGL(colsum_bf16_kernel, dim3((N / 8 + 255) / 256, (M + 127) / 128), dim3(256), 0, st, (const bf16*)dY, lddy, db, M, N);
             return modcr_check_launch("colsum_bf16");
-        }
+        case MODCR_BWD_DB_COLSUM:
+            hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), dim3(256), 0, st, dY, lddy, (int)dy_dtype, db, M, N, accumulate);
+            return modcr_check_launch("colsum");
     }
-    // dY wider than X: the product is formed TRANSPOSED, dW^T [K,N] = X^T . dY, so that the wide operand is the one that stays
-    // token-major (half-TN form below) and only X is transposed; a transposing reduction writes dW.  The bias gradient, which the
-    // transpose of dY used to carry, is a column-sum pass of its own when the caller wants it here (modcr_ffn_up_du_bwd has it from
-    // the producing GEMM's epilogue): [3072 x 768] 591 -> 465 us without it, [2304 x 768] 499 -> 363 us + the pass.
-    if (N > K && workspace && dy_dtype == MODCR_BF16 && dtype == MODCR_BF16 && modcr_knob_int("MODCR_GEMM_HALF_TN", 1) != 0 &&
-        (N % 256) == 0 && (K % 256) == 0 && K >= 256 && (M % 64) == 0 && M >= 256 && (lddy % 8) == 0 && modcr_aligned16(dY) &&
-        (int64_t)64 * lddy * 2 + (int64_t)N * 2 < (1ll << 31)) {
-        const BwdWeightPlan ps = plan_bwd_weight(M, K, N);              // rows of the product = X features
-        if (workspace_bytes >= ps.total && ps.kps >= 4 && !(ps.kps & 1) && (int64_t)K * ps.Mp < (1ll << 31)) {
-            hipStream_t st = (hipStream_t)stream;
-            bf16* xt = (bf16*)workspace;                                    // (the plan's dY^T slot: X^T [K, Mp] here)
-            float* part = (float*)((char*)workspace + ps.off_part);
-            LinearArgs p;
-            p.A = xt; p.lda = ps.Mp; p.W = (const bf16*)dY; p.ldw = lddy; p.bias = nullptr; p.res = nullptr; p.ldr = 0;
-            p.res_dtype = 0; p.C = part; p.ldc = N; p.out_dtype = MODCR_F32; p.M = K; p.N = N; p.K = (int)ps.Mp; p.kvalid = M;
-            p.act = MODCR_ACT_NONE; p.tiles_m = p.tiles_n = 0; p.vec_ok = 1;
-            p.k_tiles_per_split = ps.kps; p.split_stride = (int64_t)N * K;
-            if (p8_ok(p)) {
-                int rc = transpose_to_bf16(X, dtype, ldx, xt, ps.Mp, M, K, (int)ps.Mp, st);
-                if (rc != MODCR_OK) return rc;
-                rc = launch_p8d<MODCR_ACT_NONE, 0, MODCR_F32, 1, 2>(p, st);
-                if (rc != MODCR_OK) return rc;
-                hipLaunchKernelGGL(reduce_partials_transposed_kernel, dim3((unsigned)((N + 31) / 32), (unsigned)((K + 31) / 32)), dim3(256), 0, st,
-                                   part, ps.splits, (int64_t)N * K, dW, K, N, accumulate);
-                rc = modcr_check_launch("reduce_partials_transposed");
-                if (rc != MODCR_OK || !db) return rc;
-                // bias gradient: per-256-row-block column sums of dY (plain stores) + their fold in block order -- two launches as the
-                // memset + atomic form it replaces, but reproducible; BEHIND the reduction: in front of the product, or between product and
-                // reduction (where the fold could ride on the reduction's grid), its 425-566 MB read of dY costs more than it saves
-                // (tools/ab_dw_bias.py: [2304 x 768] 421 -> 426 us; the reduction 14.6 -> 21.0 us with its partials evicted)
-                if ((N % 8) == 0) {
-                    float* dbp = (float*)((char*)workspace + ps.off_dbp);
-                    const int nblk = (M + 255) / 256;
-                    hipLaunchKernelGGL(colsum_bf16_block_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)nblk), dim3(256), 0, st,
-                                       (const bf16*)dY, lddy, dbp, M, N);
-                    rc = modcr_check_launch("colsum_bf16_block");
-                    if (rc != MODCR_OK) return rc;
-                    return launch_db_fold(DbFold{dbp, nblk, N, db, accumulate}, st);
-                }
-                hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), dim3(256), 0, st, dY, lddy, (int)dy_dtype, db, M, N, accumulate);
-                return modcr_check_launch("colsum");
-            }
-        }
-    }
-    const BwdWeightPlan pl = plan_bwd_weight(M, N, K);
-    if (workspace && workspace_bytes >= pl.total) {
-        hipStream_t st = (hipStream_t)stream;
-        bf16* dyt = (bf16*)workspace;
-        bf16* xt = (bf16*)((char*)workspace + pl.off_xt);
-        float* part = (float*)((char*)workspace + pl.off_part);
-        // db rides along with the transposition of dY (column sums of the tile the kernel holds) where the 16-byte path applies
-        const bool fused_db = db && (N % 8) == 0 && (lddy % 8) == 0 && (pl.Mp % 64) == 0 && modcr_aligned16(dY) && modcr_aligned16(dyt);
-        float* dbp = (float*)((char*)workspace + pl.off_dbp);
-        int nblk = 0;
-        int rc = transpose_to_bf16(dY, dy_dtype, lddy, dyt, pl.Mp, M, N, (int)pl.Mp, st, fused_db ? dbp : nullptr, &nblk);
-        if (rc != MODCR_OK) return rc;
-        const DbFold fold = fused_db ? DbFold{dbp, nblk, N, db, accumulate} : DbFold{nullptr, 0, 0, nullptr, 0};
-        // half-TN form: X stays token-major, as the forward saved it (its transpose is the larger half of the transposed bytes of a
-        // layer: x, ctx, a and the [M, 4H] FFN intermediate) -- the 256 x 256 kernel stages [64 tokens][128 features] images of it
-        // and reads the fragments with ds_read_b64_tr_b16; dY^T is still transposed (the bias gradient rides on that pass and its
-        // zero padding covers the tokens past M, for which the kernel re-reads X's last K-tile).  The transposed reads make the
-        // product ~20 % slower (205 vs 170 us averaged over the encoder shapes at M = 92160), so the form is taken where X is at
-        // least as wide as dY (K >= N: the transpose it saves is at least as large as the one that stays) -- dW of BertSelfOutput
-        // 236 -> 190 us, of BertOutput 599 -> 470 us; [3072 x 768] (601 -> 644 us) and [2304 x 768] (490 -> 478 us) keep both
-        // transposes (tools/run_bench_dw.sh).  MODCR_GEMM_HALF_TN = 0 / 2 (tuning build): never / whenever the shape allows.
-        const int half_knob = modcr_knob_int("MODCR_GEMM_HALF_TN", 1);
-        const bool half_tn = half_knob != 0 && (K >= N || half_knob == 2) && dtype == MODCR_BF16 && (N % 256) == 0 && N >= 256 && (K % 256) == 0 &&
-                             (M % 64) == 0 && M >= 256 && (ldx % 8) == 0 && modcr_aligned16(X) && pl.kps >= 4 && !(pl.kps & 1) && pl.splits >= 1 &&
-                             (int64_t)64 * ldx * 2 + (int64_t)K * 2 < (1ll << 31) && (int64_t)N * pl.Mp < (1ll << 31);
-        LinearArgs ph;
-        ph.A = dyt; ph.lda = pl.Mp; ph.W = (const bf16*)X; ph.ldw = ldx; ph.bias = nullptr; ph.res = nullptr; ph.ldr = 0;
-        ph.res_dtype = 0; ph.C = part; ph.ldc = K; ph.out_dtype = MODCR_F32; ph.M = N; ph.N = K; ph.K = (int)pl.Mp; ph.kvalid = M;
-        ph.act = MODCR_ACT_NONE; ph.tiles_m = ph.tiles_n = 0; ph.vec_ok = 1;
-        ph.k_tiles_per_split = pl.kps; ph.split_stride = (int64_t)N * K;
-        if (half_tn && p8_ok(ph)) {
-            LinearArgs& p = ph;
-            const bool direct_out = pl.splits == 1 && !accumulate;
-            if (direct_out) p.C = dW;
-            rc = launch_p8d<MODCR_ACT_NONE, 0, MODCR_F32, 1, 2>(p, st);
-            if (rc != MODCR_OK) return rc;
-            if (!direct_out) rc = launch_reduce_partials(part, pl.splits, (int64_t)N * K, dW, accumulate, fold, st);
-            else if (fused_db) rc = launch_db_fold(fold, st);
-            if (rc != MODCR_OK || !db || fused_db) return rc;
-            hipLaunchKernelGGL(rowsum_bf16_kernel, dim3((N + 3) / 4), dim3(256), 0, st, dyt, pl.Mp, db, N, (int)pl.Mp, accumulate);
-            return modcr_check_launch("rowsum");
-        }
-        rc = transpose_to_bf16(X, dtype, ldx, xt, pl.Mp, M, K, (int)pl.Mp, st);
-        if (rc != MODCR_OK) return rc;
-        LinearArgs p;
-        p.A = dyt; p.lda = pl.Mp; p.W = xt; p.ldw = pl.Mp; p.bias = nullptr; p.res = nullptr; p.ldr = 0;
-        p.res_dtype = 0; p.C = part; p.ldc = K; p.out_dtype = MODCR_F32; p.M = N; p.N = K; p.K = (int)pl.Mp;
-        p.act = MODCR_ACT_NONE; p.tiles_m = p.tiles_n = 0;
-        p.vec_ok = (K % 4 == 0); p.k_tiles_per_split = pl.kps; p.split_stride = (int64_t)N * K;
-        const bool direct_out = pl.splits == 1 && !accumulate;      // one split: the product IS dW, no reduce pass
-        if (direct_out) p.C = dW;
-        rc = p8_ok(p) ? launch_p8<MODCR_ACT_NONE, 0, MODCR_F32>(p, st) : dispatch_linear(p, st);
-        if (rc != MODCR_OK) return rc;
-        if (!direct_out) rc = launch_reduce_partials(part, pl.splits, (int64_t)N * K, dW, accumulate, fold, st);
-        else if (fused_db) rc = launch_db_fold(fold, st);
-        if (rc != MODCR_OK || !db || fused_db) return rc;
-        hipLaunchKernelGGL(rowsum_bf16_kernel, dim3((N + 3) / 4), dim3(256), 0, st, dyt, pl.Mp, db, N, (int)pl.Mp,
-                           accumulate);
-        return modcr_check_launch("rowsum");
-    }
-    // dW[n,k] = sum_m dY[m,n] X[m,k]
-    GemmF32Args a;
-    a.A = dY; a.sam = 1; a.sak = lddy; a.a_dtype = dy_dtype;
-    a.B = X; a.sbk = ldx; a.sbn = 1; a.b_dtype = dtype;
-    a.bias = nullptr; a.res = nullptr; a.ldr = 0; a.res_dtype = 0;
-    a.C = dW; a.ldc = K; a.out_dtype = MODCR_F32; a.M = N; a.N = K; a.K = M; a.act = 0;
-    a.accumulate = accumulate;
-    int rc = launch_gemm_f32(a, (hipStream_t)stream);
-    if (rc != MODCR_OK || !db) return rc;
-    hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), dim3(256), 0, (hipStream_t)stream, dY,
-                       lddy, (int)dy_dtype, db, M, N, accumulate);
-    return modcr_check_launch("colsum");
+    return MODCR_OK;        // no db, or folded by the reduction
+}
+
+extern "C" int modcr_linear_bwd_weight_route(const void* dY, int64_t lddy, int32_t dy_dtype, const void* X, int64_t ldx,
+                                             const float* dW, const float* db, int32_t M, int32_t N, int32_t K, int32_t accumulate,
+                                             int32_t dtype, const void* workspace, int64_t workspace_bytes, int32_t* info) {
+    MODCR_REQUIRE(info, "linear_bwd_weight_route: null info");
+    MODCR_REQUIRE(dY && X && dW && M > 0 && N > 0 && K > 0, "linear_bwd_weight: bad arguments");
+    const BwdWeightCall c = {dY, lddy, dy_dtype, X, ldx, const_cast<float*>(dW), const_cast<float*>(db), M, N, K, accumulate, dtype,
+                             const_cast<void*>(workspace), workspace_bytes};
+    const BwdWeightRoute r = route_bwd_weight(c);
+    info[0] = r.form; info[1] = r.plan.splits; info[2] = r.plan.kps; info[3] = r.launcher; info[4] = r.direct_out;
+    info[5] = r.reduce; info[6] = r.db;
+    return MODCR_OK;
 }
 
 // ---- LN(A.W^T + bias + residual): GEMM with fp32 pre-LN rows into the workspace, then row LN ----
@@ -3210,12 +3300,6 @@ extern "C" int modcr_ffn_down_residual_ln_bwd(const float* dY, const float* pre,
 // (dW1, dX) instead of three: the recompute GEMM of modcr_ffn_up_gelu_bwd (0.48 ms per layer at M = 92160) is gone for
 // +1 row of bf16 stores in the forward.  Shapes outside the persistent kernel's (small M, ragged H / I) keep the recompute route:
 // modcr_ffn_keep_supported says which.
-static void ffn_keep_args(LinearArgs& p, const void* x, const void* w1, const float* b1, void* out, void* pre_act, int32_t M, int32_t H, int32_t I) {
-    p.A = (const bf16*)x; p.lda = H; p.W = (const bf16*)w1; p.ldw = H; p.bias = b1;
-    p.res = nullptr; p.ldr = 0; p.res_dtype = 0; p.C = out; p.ldc = I; p.C2 = pre_act;
-    p.out_dtype = MODCR_BF16; p.M = M; p.N = I; p.K = H; p.act = MODCR_ACT_GELU_KEEP;
-    p.tiles_m = p.tiles_n = 0; p.vec_ok = 1; p.k_tiles_per_split = 0; p.split_stride = 0;
-}
 extern "C" int modcr_ffn_keep_supported(int32_t M, int32_t H, int32_t I, int32_t dtype) {
     if (dtype != MODCR_BF16 || M < 256 || (M % 8) != 0 || (H % 256) != 0 || H > 1024 || (I % 256) != 0) return 0;
     if ((int64_t)M * I >= (1ll << 30)) return 0;                // 32-bit byte offsets of the dX product's A operand
@@ -3226,8 +3310,8 @@ extern "C" int modcr_ffn_up_gelu_keep_fwd(const void* x, const void* w1, const f
                                           int32_t M, int32_t H, int32_t I, int32_t dtype, modcr_stream_t stream) {
     MODCR_REQUIRE(x && w1 && b1 && out && pre_act, "ffn_up_gelu_keep_fwd: null pointer");
     MODCR_REQUIRE(modcr_ffn_keep_supported(M, H, I, dtype), "ffn_up_gelu_keep_fwd: shape / dtype outside the kept-input route (see modcr_ffn_keep_supported)");
-    LinearArgs p;
-    ffn_keep_args(p, x, w1, b1, out, pre_act, M, H, I);
+    LinearArgs p = linear_args(x, H, w1, H, out, I, MODCR_BF16, M, I, H);
+    p.bias = b1; p.C2 = pre_act; p.act = MODCR_ACT_GELU_KEEP; p.vec_ok = 1;
     MODCR_REQUIRE(modcr_aligned16(x) && modcr_aligned16(w1) && modcr_aligned16(b1) && modcr_aligned16(pre_act) && p8_ok(p),
                   "ffn_up_gelu_keep_fwd: operands must be 16-byte aligned");
     // whole tiles: the seamless-ring kernel (linear_bf16_p8_kernel, SPEC)
@@ -3259,11 +3343,8 @@ extern "C" int modcr_ffn_down_residual_ln_gelu_bwd(const void* dY, int32_t dy_dt
     MODCR_REQUIRE(sub_bytes >= (int64_t)I * H * 2, "ffn_down_gelu_bwd: workspace too small");
     rc = transpose_to_bf16(w2, dtype, I, wt, H, H, I, H, st);
     if (rc != MODCR_OK) return rc;
-    LinearArgs a;
-    a.A = (const bf16*)dsub; a.lda = H; a.W = wt; a.ldw = H; a.bias = nullptr;
-    a.res = pre_act; a.ldr = I; a.res_dtype = MODCR_BF16; a.C = d_u; a.ldc = I;
-    a.out_dtype = MODCR_BF16; a.M = M; a.N = I; a.K = H; a.act = MODCR_ACT_MUL_GELU_GRAD;
-    a.tiles_m = a.tiles_n = 0; a.vec_ok = 1; a.k_tiles_per_split = 0; a.split_stride = 0;
+    LinearArgs a = linear_args(dsub, H, wt, H, d_u, I, MODCR_BF16, M, I, H);
+    a.res = pre_act; a.ldr = I; a.res_dtype = MODCR_BF16; a.act = MODCR_ACT_MUL_GELU_GRAD; a.vec_ok = 1;
     MODCR_REQUIRE(modcr_aligned16(pre_act) && modcr_aligned16(d_u) && p8_ok(a), "ffn_down_gelu_bwd: operands must be 16-byte aligned");
     if (db_u) {          // column sums of d_u (= the bias gradient of BertIntermediate) from the same epilogue
         if (hipMemsetAsync(db_u, 0, (size_t)I * sizeof(float), st) != hipSuccess) {
@@ -3313,11 +3394,8 @@ extern "C" int modcr_ffn_up_gelu_bwd(const void* dinter, int32_t dinter_dtype, c
         // bf16 route: d_u = gelu'(x.W1^T + b1) * d_inter inside the recompute GEMM's epilogue (d_inter rides in as the
         // residual operand, multiplied instead of added), written once as bf16: no fp32 pre-activation round trip,
         // no separate activation-backward or cast pass
-        LinearArgs p;
-        p.A = (const bf16*)x; p.lda = H; p.W = (const bf16*)w1; p.ldw = H; p.bias = b1;
-        p.res = dinter; p.ldr = I; p.res_dtype = MODCR_BF16; p.C = u; p.ldc = I;
-        p.out_dtype = MODCR_BF16; p.M = M; p.N = I; p.K = H; p.act = MODCR_ACT_GELU_GRAD;
-        p.tiles_m = p.tiles_n = 0; p.vec_ok = 1; p.k_tiles_per_split = 0; p.split_stride = 0;
+        LinearArgs p = linear_args(x, H, w1, H, u, I, MODCR_BF16, M, I, H);
+        p.bias = b1; p.res = dinter; p.ldr = I; p.res_dtype = MODCR_BF16; p.act = MODCR_ACT_GELU_GRAD; p.vec_ok = 1;
         if ((H % 64) == 0 && modcr_aligned16(x) && modcr_aligned16(w1) && modcr_aligned16(dinter) && p8_ok(p)) {
             int rc = launch_p8d<MODCR_ACT_GELU_GRAD, 1, MODCR_BF16, 0>(p, (hipStream_t)stream);
             if (rc != MODCR_OK) return rc;

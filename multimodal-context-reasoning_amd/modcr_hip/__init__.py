@@ -19,6 +19,13 @@ ACT_NONE, ACT_GELU, ACT_TANH = 0, 1, 2
 ROUTE_KERNELS = {1: "f32_tile", 2: "f32_rowdot", 3: "ring128", 4: "ring192", 5: "ring256", 6: "p8", 7: "t192", 8: "d4"}
 ROUTE_DIRECT, ROUTE_SPEC = 1, 2
 
+# modcr_linear_bwd_weight_route / modcr_linear_bwd_input_route (MODCR_BWD_*)
+BWD_WEIGHT_FORMS = {1: "f32", 2: "nt", 3: "half_tn", 4: "swapped", 5: "tn"}
+BWD_PRODUCTS = {0: "f32", 1: "splitk", 2: "dispatch"}
+BWD_REDUCTIONS = {0: "none", 1: "plain", 2: "transposed"}
+BWD_DB_METHODS = {0: "none", 1: "fused_reduce", 2: "fused_fold", 3: "rowsum", 4: "block_fold", 5: "atomic", 6: "colsum"}
+BWD_INPUT_FORMS = {1: "f32", 2: "fwd", 3: "splitk"}
+
 _c = ctypes
 _vp, _i32, _i64, _f32 = _c.c_void_p, _c.c_int32, _c.c_int64, _c.c_float
 
@@ -87,6 +94,9 @@ SIGNATURES = {
     "modcr_linear_bwd_input": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "modcr_linear_bwd_weight_workspace": (_i64, [_i32, _i32, _i32]),
     "modcr_linear_bwd_weight": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "modcr_linear_bwd_weight_route": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _c.POINTER(_i32)]),
+    "modcr_linear_bwd_input_route": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64,
+                                            _c.POINTER(_i32)]),
     "modcr_layernorm_bwd": (_i32, [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _i32, _vp]),
     "modcr_act_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]),
     "modcr_qkv_attn_bwd_workspace": (_i64, [_i32, _i32, _i32, _i32]),
@@ -303,6 +313,50 @@ def linear_route(a, w, bias=None, residual=None, out_dtype=None, act=ACT_NONE, l
     _check(lib().modcr_linear_route(pa, lda or sa or k, pw, ldw or sw or k, pb, pr, ldr or sr or n, rdt, pc, ldc or sc or n,
                                     m, n, k, act, dt, od, info), "modcr_linear_route")
     return LinearRoute(ROUTE_KERNELS[info[0]], int(bool(info[1] & ROUTE_DIRECT)), int(bool(info[1] & ROUTE_SPEC)), info[2], info[3])
+
+
+BwdWeightRoute = collections.namedtuple("BwdWeightRoute", "form splits kps product direct_out reduction db")
+BwdInputRoute = collections.namedtuple("BwdInputRoute", "form cast_pad inner")
+
+
+def _route_ptr(t):
+    """a tensor's address; a non-tensor stands for a 256-byte aligned allocation (truthy) or NULL"""
+    return t.data_ptr() if isinstance(t, torch.Tensor) else (256 if t else None)
+
+
+def linear_bwd_weight_route(m, n, k, dy_dtype=BF16, dtype=BF16, db=True, accumulate=False, workspace_bytes=None, lddy=None, ldx=None,
+                            dy=True, x=True, dw=True, workspace=True):
+    """The route modcr_linear_bwd_weight takes for dW [n, k] (+)= dY [m, n]^T . X [m, k] (modcr_linear_bwd_weight_route; nothing is
+    launched or read): BwdWeightRoute(form = a name of BWD_WEIGHT_FORMS, splits, kps = 64-token K-tiles per split, product = a name
+    of BWD_PRODUCTS, direct_out, reduction = a name of BWD_REDUCTIONS, db = a name of BWD_DB_METHODS).  Shapes, not tensors, so it
+    runs without a GPU: dy / x / dw / db / workspace are tensors (their addresses) or truthy for a 256-byte aligned allocation.
+    workspace_bytes: None = what modcr_linear_bwd_weight_workspace asks for, 0 = no workspace."""
+    if workspace_bytes is None:
+        workspace_bytes = lib().modcr_linear_bwd_weight_workspace(m, n, k)
+    info = (_i32 * 7)()
+    _check(lib().modcr_linear_bwd_weight_route(_route_ptr(dy), lddy or n, dy_dtype, _route_ptr(x), ldx or k, _route_ptr(dw), _route_ptr(db), m, n, k,
+                                               int(bool(accumulate)), dtype, _route_ptr(workspace) if workspace_bytes else None, workspace_bytes,
+                                               info), "modcr_linear_bwd_weight_route")
+    return BwdWeightRoute(BWD_WEIGHT_FORMS[info[0]], info[1], info[2], BWD_PRODUCTS[info[3]], info[4], BWD_REDUCTIONS[info[5]],
+                          BWD_DB_METHODS[info[6]])
+
+
+def linear_bwd_input_route(m, n, k, dy_dtype=BF16, dtype=BF16, out_dtype=None, residual=None, workspace_bytes=None, lddy=None, ldw=None,
+                           lddx=None, ldr=None, dy=True, w=True, dx=True, workspace=True):
+    """The route modcr_linear_bwd_input takes for dX [m, k] = dY [m, n] . W [n, k] (+ residual, the composites' fp32 rows)
+    (modcr_linear_bwd_input_route; nothing is launched or read): BwdInputRoute(form = a name of BWD_INPUT_FORMS, cast_pad,
+    inner = the LinearRoute of the product behind form "fwd", None otherwise).  Arguments as linear_bwd_weight_route."""
+    if workspace_bytes is None:
+        workspace_bytes = lib().modcr_linear_bwd_input_workspace(m, n, k)
+    info = (_i32 * 6)()
+    _check(lib().modcr_linear_bwd_input_route(_route_ptr(dy), lddy or n, dy_dtype, _route_ptr(w), ldw or k, _route_ptr(residual), ldr or k,
+                                              _route_ptr(dx), lddx or k, m, n, k, dtype, dtype if out_dtype is None else out_dtype,
+                                              _route_ptr(workspace) if workspace_bytes else None, workspace_bytes, info),
+           "modcr_linear_bwd_input_route")
+    inner = None
+    if BWD_INPUT_FORMS[info[0]] == "fwd":
+        inner = LinearRoute(ROUTE_KERNELS[info[2]], int(bool(info[3] & ROUTE_DIRECT)), int(bool(info[3] & ROUTE_SPEC)), info[4], info[5])
+    return BwdInputRoute(BWD_INPUT_FORMS[info[0]], info[1], inner)
 
 
 def layernorm(x, gamma, beta, eps, residual=None, out_dtype=None, out=None, rows_per_group=0,

@@ -31,7 +31,8 @@ def test_header_declares_the_survey_minimum_set():
     fns = header_functions()
     for name in ("modcr_qkv_attn_fwd", "modcr_chunk_mean_q_fwd", "modcr_proj_residual_ln_fwd",
                  "modcr_ffn_up_gelu_fwd", "modcr_ffn_down_residual_ln_fwd", "modcr_embed_ln_fwd",
-                 "modcr_align_attn_fwd", "modcr_align_attn_bwd", "modcr_mc_ce_fwd_bwd", "modcr_version"):
+                 "modcr_align_attn_fwd", "modcr_align_attn_bwd", "modcr_mc_ce_fwd_bwd", "modcr_version",
+                 "modcr_linear_bwd_weight_route", "modcr_linear_bwd_input_route"):
         assert name in fns, name
 
 

@@ -690,6 +690,45 @@ def test_gemm_route_table_on_the_host():
         mh.linear_route((4096, 200), (256, 200))
 
 
+def test_linear_bwd_route_tables_on_the_host(tuning_lib, monkeypatch):
+    """The GPU route tables of test_hip_linear_bwd_routes assert each case's route before they run; the route entries dereference
+    nothing, so the same tables are checked here without a GPU: a change to a dW / dX predicate that moves a case off its form
+    fails on the CPU box with the form's name.  Also: the tables reach every form of the product library, the tuning library's
+    knobs reach TN, and the queries return the compute entries' refusals."""
+    import modcr_hip as mh
+    import test_hip_linear_bwd_routes as T
+    mh.use_tuning_library(False)
+    for c in T.W_CASES:
+        assert T.weight_route(c) == c.route, c.id
+    assert {c.route.form for c in T.W_CASES} == set(mh.BWD_WEIGHT_FORMS.values()) - {"tn"}
+    assert {c.route.db for c in T.W_CASES} == set(mh.BWD_DB_METHODS.values()) - {"atomic"}
+    assert {c.route.reduction for c in T.W_CASES} == set(mh.BWD_REDUCTIONS.values())
+    assert {c.route.product for c in T.W_CASES} == set(mh.BWD_PRODUCTS.values())
+    for c in T.X_CASES:
+        ws = mh.lib().modcr_ffn_up_du_bwd_workspace(c.m, c.k, c.n) if c.res else None
+        got = mh.linear_bwd_input_route(c.m, c.n, c.k, out_dtype=c.out, residual=True, workspace_bytes=ws) if c.res else T.input_route(c)
+        assert got == c.route, (c.id, got)
+    assert {c.route.form for c in T.X_CASES} == set(mh.BWD_INPUT_FORMS.values())
+    m, n, k = T.X_REFUSED
+    with pytest.raises(mh.ModcrHipError, match=r"\(-1\): " + T.X_REFUSED_MESSAGE):
+        mh.linear_bwd_input_route(m, n, k)
+    with pytest.raises(mh.ModcrHipError, match="linear_bwd_input: bad arguments"):
+        mh.linear_bwd_input_route(0, n, k)
+    with pytest.raises(mh.ModcrHipError, match="linear_bwd_weight: bad arguments"):
+        mh.linear_bwd_weight_route(m, 0, k)
+    # the product library has no knobs: the environment changes nothing there; the tuning library takes TN, and NT with HALF_TN off
+    monkeypatch.setenv("MODCR_GEMM_TN", "1")
+    assert T.weight_route(T.TN_CASE).form == "half_tn"
+    mh.use_tuning_library(True)
+    assert T.weight_route(T.TN_CASE) == T.TN_CASE.route
+    assert mh.linear_bwd_weight_route(512, 256, 256, workspace_bytes=2 * 256 * 256 * 4).form == "tn"         # its plan: the partials alone
+    assert mh.linear_bwd_weight_route(512, 256, 256, workspace_bytes=2 * 256 * 256 * 4 - 1).form == "f32"
+    monkeypatch.delenv("MODCR_GEMM_TN")
+    monkeypatch.setenv("MODCR_GEMM_HALF_TN", "0")
+    assert T.weight_route(T.TN_CASE) == T.W("nt", 2, 4)
+    assert T.weight_route(T.W_CASES[7]).form == "nt"           # (swapped_1)
+
+
 def test_hidden_dropout_mask_restatement_properties():
     """helpers.hidden_drop_keep, the host statement of csrc/common.h's drop_words / drop_field / drop_threshold that the GPU tests of
     tests/test_hip_rowops.py hold every consumer of the hidden mask to: properties that need no device."""
