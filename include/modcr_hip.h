@@ -156,6 +156,23 @@ int modcr_qkv_attn_long_drop_fwd(const void* x, const void* hist, const void* wq
                                  void* ctx, float* probs, float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P,
                                  int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
                                  void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream);
+/* modcr_qkv_attn_long_drop_fwd with dense mask bits on top of the bias (opt-in: training seq_enc, whose layers 0-2 and 9-11 take dense
+ * phase masks, above 256 keys).  The arguments are modcr_qkv_attn_long_drop_fwd's, in its order, then
+ *   mask_bits u32 [N, S, ceil(S / 32)] as modcr_build_phase_mask / modcr_pack_mask_bits write them: bit j of row (n, i) clear adds
+ *             -10000 to the score of (query i, key j) in every head, on top of the bias -- the call with the bits folded into a
+ *             0 / -10000 [N,1,S,S] bias, bit for bit, at 32 KB instead of 1 MB per sequence at S = 512.  A query row hidden everywhere
+ *             is the uniform softmax.  With bits, bias and head_mask may both be NULL.
+ *   mask_bits == NULL: the call IS modcr_qkv_attn_long_drop_fwd -- same bits, same codes, same messages.
+ * With mask_bits: P > 0 or hist returns MODCR_ERR_INVALID, S <= 256 MODCR_ERR_UNSUPPORTED (modcr_qkv_attn_opt_fwd takes the bits
+ * there), a pointer off 4 bytes MODCR_ERR_INVALID; everything else is refused as modcr_qkv_attn_long_drop_fwd refuses it.  The
+ * workspace is modcr_qkv_attn_bias_workspace.  The backward is modcr_qkv_attn_long_align_bwd. */
+int modcr_qkv_attn_long_align_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                                  const float* bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                                  const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
+                                  void* ctx, float* probs, float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P,
+                                  int32_t H, int32_t A, float attn_p, uint64_t seed, uint64_t offset, int32_t flags,
+                                  void* workspace, int64_t workspace_bytes, int32_t dtype, modcr_stream_t stream,
+                                  const uint32_t* mask_bits);
 /* The forward over the LIVE-ROW layout of a frozen encoder pass.  Sequence n keeps only its first L_n rows (1 <= L_n <= S: the
  * rows behind them are padded image regions -- keys that every mask hides, queries that no consumer reads), and the kept rows of
  * all sequences lie back to back:
@@ -613,6 +630,29 @@ int modcr_qkv_attn_long_drop_bwd(const void* dctx, const void* x, const void* hi
                                  float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
                                  uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
                                  modcr_stream_t stream);
+/* modcr_qkv_attn_long_drop_bwd with dense mask bits and the gradient of the align map above 256 keys: the backward of
+ * modcr_qkv_attn_long_align_fwd.  The arguments are modcr_qkv_attn_long_drop_bwd's, in its order, then
+ *   mask_bits u32 [N, S, ceil(S / 32)] or NULL: the forward's bits (0 / -10000 on top of the bias); they satisfy "bias or head_mask".
+ *   d_align   fp32 [N, T, R] or NULL, T = align_t, R = S - T: the gradient of the forward's align_map, the same for every head.  With
+ *             E_ij = d_align[n, i, j - T] for i < T <= j, else 0:  dP = (dctx.V^T) o m / (1 - p) + E (flags has
+ *             MODCR_ATTN_SIDE_POST_DROPOUT and attn_p > 0: E o m / (1 - p)),  D_i = dctx_i . (P~.V)_i + sum_j A^side_ij E_ij, whose align
+ *             share is one more online accumulator of the query kernel's statistics sweep (no launch of its own); d_head_mask sums D.
+ *   flags     MODCR_ATTN_SIDE_POST_DROPOUT or 0, as the forward's.
+ * With neither mask_bits nor d_align the call IS modcr_qkv_attn_long_drop_bwd at every key count.  With either: P > 0 / hist / d_hist
+ * returns MODCR_ERR_INVALID, S <= 256 MODCR_ERR_UNSUPPORTED (modcr_qkv_attn_bwd serves them there from lse and the q|k|v dump),
+ * d_align without 0 < align_t < S and pointers off 4 bytes MODCR_ERR_INVALID; everything else is refused as
+ * modcr_qkv_attn_long_drop_bwd refuses it, before the first launch, nothing written.  _workspace and _route answer what that entry's
+ * answer (codes 0-4).  One lane per output element, no atomics, repeated calls bit-identical. */
+int64_t modcr_qkv_attn_long_align_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype);
+int modcr_qkv_attn_long_align_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype);
+int modcr_qkv_attn_long_align_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                                  const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                                  const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
+                                  const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv, int32_t accumulate,
+                                  float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
+                                  uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                                  modcr_stream_t stream, const uint32_t* mask_bits, const float* d_align, int32_t align_t,
+                                  int32_t flags);
 
 /* ---- backward of the encoder layer's GEMM blocks (autograd of BertSelfOutput / BertIntermediate / BertOutput,
  * a_bert:362-373, :425-437, :440-451).  Gradients of parameters are fp32; dgamma / dbeta are ACCUMULATED (caller

@@ -1785,8 +1785,8 @@ int attn_opt_checks(const AttnCall& c, bool has_mask, bool dump_aligned16) {
 }
 
 // modcr_qkv_attn_bias_fwd's own checks (b: its bias / head_mask arguments)
-int attn_bias_checks(const char* who, const AttnLongArgs& b) {
-    MODCR_REQUIRE(b.bias || b.head_mask, "%s: neither bias nor head_mask (that call belongs to modcr_qkv_attn_opt_fwd)", who);
+int attn_bias_checks(const char* who, const AttnLongArgs& b, bool bits = false) {
+    MODCR_REQUIRE(b.bias || b.head_mask || bits, "%s: neither bias nor head_mask (that call belongs to modcr_qkv_attn_opt_fwd)", who);
     MODCR_REQUIRE(b.bias_sn >= 0 && b.bias_sa >= 0 && b.bias_sq >= 0 && b.head_mask_sn >= 0, "%s: negative stride", who);
     MODCR_REQUIRE(((uintptr_t)b.bias & 3) == 0 && ((uintptr_t)b.head_mask & 3) == 0, "%s: bias / head_mask not 4-byte aligned", who);
     return MODCR_OK;
@@ -1972,7 +1972,7 @@ int attn_fwd(const void* x, const void* hist, const void* wqkv, const float* bqk
     c.wide_dropout = wide;
     int rc = attn_fwd_setup(c, x && wqkv && bqkv && ctx, hist != nullptr,
                             modcr_aligned16(x) && modcr_aligned16(wqkv) && modcr_aligned16(ctx) && (P == 0 || modcr_aligned16(hist)));
-    if (rc == MODCR_OK) rc = bias ? attn_bias_checks(c.who, *bias) : attn_opt_checks(c, key_mask || dense_mask_bits, modcr_aligned16(qkv_dump));
+    if (rc == MODCR_OK) rc = bias ? attn_bias_checks(c.who, *bias, dense_mask_bits != nullptr) : attn_opt_checks(c, key_mask || dense_mask_bits, modcr_aligned16(qkv_dump));
     if (rc != MODCR_OK) return rc;
     const AttnRoute r = attn_fwd_route(c);
     if (r.rc != MODCR_OK) return r.rc;
@@ -2022,6 +2022,7 @@ int attn_fwd(const void* x, const void* hist, const void* wqkv, const float* bqk
     g.ctx = ctx; g.probs = probs; g.align_map = align_map;
     g.N = N; g.S = S; g.P = P; g.H = H; g.A = A; g.align_t = align_t;
     g.drop_thr16 = d.thr16; g.drop_key = d.key; g.drop_keep = d.keep; g.side_post_drop = side_post_drop;
+    g.bits_on_bias = bias && dense_mask_bits;               // (modcr_qkv_attn_long_align_fwd only: the other bias entries pass no bits)
     hipEvent_t ev0 = g_time_start, ev1 = g_time_stop;       // the measurement hook times the core, not the projection
     g_time_start = g_time_stop = nullptr;
     return modcr_launch_attn_long(g, dtype, st, ev0, ev1);
@@ -2104,6 +2105,33 @@ extern "C" int modcr_qkv_attn_long_drop_fwd(const void* x, const void* hist, con
     b.head_mask = head_mask; b.head_mask_sn = head_mask_stride_n;
     return attn_fwd(x, hist, wqkv, bqkv, nullptr, nullptr, chunk_id, chunk_t, ctx, probs, align_map, align_t, nullptr, nullptr,
                     N, S, P, H, A, attn_p, seed, offset, flags, workspace, workspace_bytes, dtype, stream, &b, nullptr, true);
+}
+
+// modcr_qkv_attn_long_drop_fwd with the dense mask bits of modcr_build_phase_mask / modcr_pack_mask_bits on top of the bias (opt-in:
+// training seq_enc above 256 keys): the BITS instantiations of the streaming core, 0 / -10000 per (query, key) joined to the bias.
+// Without mask_bits it is modcr_qkv_attn_long_drop_fwd's call.
+extern "C" int modcr_qkv_attn_long_align_fwd(const void* x, const void* hist, const void* wqkv, const float* bqkv, const float* bias,
+                                             int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q, const float* head_mask,
+                                             int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t, void* ctx, float* probs,
+                                             float* align_map, int32_t align_t, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
+                                             uint64_t seed, uint64_t offset, int32_t flags, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                                             modcr_stream_t stream, const uint32_t* mask_bits) {
+    if (!mask_bits)
+        return modcr_qkv_attn_long_drop_fwd(x, hist, wqkv, bqkv, bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask, head_mask_stride_n,
+                                            chunk_id, chunk_t, ctx, probs, align_map, align_t, N, S, P, H, A, attn_p, seed, offset, flags, workspace,
+                                            workspace_bytes, dtype, stream);
+    MODCR_REQUIRE(P == 0 && !hist, "qkv_attn_long_align_fwd: no mask_bits with prefix rows (P=%d, hist %s)", P, hist ? "given" : "null");
+    if (S <= 256) {
+        modcr_set_error("qkv_attn_long_align_fwd: mask_bits on the bias route start above 256 keys (S=%d): up to 256 they belong to "
+                        "modcr_qkv_attn_opt_fwd", S);
+        return MODCR_ERR_UNSUPPORTED;
+    }
+    MODCR_REQUIRE(((uintptr_t)mask_bits & 3) == 0, "qkv_attn_long_align_fwd: mask_bits not 4-byte aligned");
+    AttnLongArgs b = {};
+    b.bias = bias; b.bias_sn = bias_stride_n; b.bias_sa = bias_stride_a; b.bias_sq = bias_stride_q;
+    b.head_mask = head_mask; b.head_mask_sn = head_mask_stride_n;
+    return attn_fwd(x, nullptr, wqkv, bqkv, nullptr, mask_bits, chunk_id, chunk_t, ctx, probs, align_map, align_t, nullptr, nullptr,
+                    N, S, 0, H, A, attn_p, seed, offset, flags, workspace, workspace_bytes, dtype, stream, &b, nullptr, true);
 }
 
 extern "C" int modcr_qkv_attn_route(int32_t present, int32_t chunk_t, int32_t align_t, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A,

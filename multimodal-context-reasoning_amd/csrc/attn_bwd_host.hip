@@ -1,7 +1,8 @@
-// Host side of the attention backward (CDNA4 / gfx950): the nine entries modcr_qkv_attn_bwd, _dropout_bwd, _lse_bwd, _opt_bwd (the mask
+// Host side of the attention backward (CDNA4 / gfx950): the ten entries modcr_qkv_attn_bwd, _dropout_bwd, _lse_bwd, _opt_bwd (the mask
 // family: key_mask / dense bits, S <= 256, no prefix rows) and _bias_bwd, _prefix_bwd, _gate_bwd, _long_bwd, _long_drop_bwd (the bias
 // family: additive bias and / or head mask, P >= 0 prefix rows, P + S <= 256, or <= 512 from _long_bwd -- without attention dropout
-// above 256 keys -- and _long_drop_bwd -- with it, the wide counter layout), their _workspace and _route companions.
+// above 256 keys --, _long_drop_bwd -- with it, the wide counter layout -- and _long_align_bwd -- with dense mask bits and the align
+// map's gradient on top, above 256 keys, no prefix rows), their _workspace and _route companions.
 // No kernel lives here: the cores are in attn_bwd.hip (five-product), attn_bwd_older.hip (older MFMA, exact), attn_bias_bwd.hip (bias MFMA, bias exact) and
 // attn_long_bwd.hip (stream, stream exact), behind the four launchers of attn_common.h.
 //
@@ -137,7 +138,7 @@ int attn_bwd_bias_checks(const AttnBwdCall& c, AttnBwdWs& ws, AttnBwdCore& core)
     MODCR_REQUIRE(!((int64_t)P + S > 256 && c.attn_p > 0.f) || (int64_t)N * A <= ATTN_DROP_WIDE_MAX_NA,
                   "%s: N * A = %lld (N=%d, A=%d) exceeds the 2^21 (sequence, head) pairs of the wide dropout counter", who, (long long)N * A, N, A);
     // (with d_head_mask a missing head_mask is a mask of ones: the head-importance call)
-    MODCR_REQUIRE(c.bias || c.head_mask || c.d_head_mask, "%s: neither bias nor head_mask%s", who,
+    MODCR_REQUIRE(c.bias || c.head_mask || c.d_head_mask || c.bits, "%s: neither bias nor head_mask%s", who,
                   P ? "" : " (that call belongs to modcr_qkv_attn_opt_bwd)");
     MODCR_REQUIRE(c.bias || !c.d_bias, "%s: d_bias without a bias", who);
     MODCR_REQUIRE(c.attn_p >= 0.f && c.attn_p < 1.f, "%s: attention dropout p=%g out of [0, 1)", who, c.attn_p);
@@ -198,6 +199,9 @@ AttnBiasBwdArgs attn_bwd_bias_args(const AttnBwdCall& c, void* qkv, void* dqkv, 
     b.drop_thr16 = d.thr16; b.drop_key = d.key; b.drop_keep = d.keep;
     b.N = c.N; b.S = c.S; b.P = c.P; b.H = c.H; b.A = c.A;
     b.stats = stats;
+    // (modcr_qkv_attn_long_align_bwd only: every other bias-family entry leaves them null / 0)
+    b.bits = c.bits; b.d_align = c.d_align; b.align_t = c.align_t;
+    b.side_post_drop = (c.attn_p > 0.f && (c.flags & MODCR_ATTN_SIDE_POST_DROPOUT)) ? 1 : 0;
     return b;
 }
 
@@ -456,4 +460,47 @@ extern "C" int modcr_qkv_attn_long_drop_bwd(const void* dctx, const void* x, con
     c.hist = hist; c.d_hist = d_hist; c.P = P; c.chunk_id = chunk_id; c.chunk_t = chunk_t; c.d_head_mask = d_head_mask;
     const int rc = attn_gate_precheck(c);
     return rc != MODCR_OK ? rc : attn_bwd(c);
+}
+
+// ---- modcr_qkv_attn_long_align_bwd: modcr_qkv_attn_long_drop_bwd with dense mask bits and the align map's gradient above 256 keys
+// (opt-in; the MASK / DALIGN instantiations of the streaming cores) ----
+extern "C" int64_t modcr_qkv_attn_long_align_bwd_workspace(int32_t N, int32_t S, int32_t P, int32_t H, int32_t dtype) {
+    return modcr_qkv_attn_long_drop_bwd_workspace(N, S, P, H, dtype);
+}
+
+extern "C" int modcr_qkv_attn_long_align_bwd_route(int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, int32_t dtype) {
+    return modcr_qkv_attn_long_drop_bwd_route(N, S, P, H, A, dtype);
+}
+
+extern "C" int modcr_qkv_attn_long_align_bwd(const void* dctx, const void* x, const void* hist, const void* wqkv, const float* bqkv,
+                                             const float* attn_bias, int64_t bias_stride_n, int64_t bias_stride_a, int64_t bias_stride_q,
+                                             const float* head_mask, int64_t head_mask_stride_n, const int32_t* chunk_id, int32_t chunk_t,
+                                             const float* dx_residual, void* dx, void* d_hist, float* dwqkv, float* dbqkv, int32_t accumulate,
+                                             float* d_bias, float* d_head_mask, int32_t N, int32_t S, int32_t P, int32_t H, int32_t A, float attn_p,
+                                             uint64_t seed, uint64_t offset, void* workspace, int64_t workspace_bytes, int32_t dtype,
+                                             modcr_stream_t stream, const uint32_t* mask_bits, const float* d_align, int32_t align_t,
+                                             int32_t flags) {
+    const char* who = "qkv_attn_long_align_bwd";
+    MODCR_REQUIRE((flags & ~MODCR_ATTN_SIDE_POST_DROPOUT) == 0, "%s: unknown flags 0x%x", who, flags);
+    // with neither it is modcr_qkv_attn_long_drop_bwd's call at every key count, by its names in the messages too
+    if (!mask_bits && !d_align)
+        return modcr_qkv_attn_long_drop_bwd(dctx, x, hist, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask,
+                                            head_mask_stride_n, chunk_id, chunk_t, dx_residual, dx, d_hist, dwqkv, dbqkv, accumulate, d_bias, d_head_mask,
+                                            N, S, P, H, A, attn_p, seed, offset, workspace, workspace_bytes, dtype, stream);
+    MODCR_REQUIRE(P == 0 && !hist && !d_hist, "%s: no mask_bits / d_align with prefix rows (P=%d, hist %s, d_hist %s)", who, P, hist ? "given" : "null",
+                  d_hist ? "given" : "null");
+    if (S <= 256) {
+        modcr_set_error("%s: mask_bits / d_align start above 256 keys (S=%d): up to 256 they belong to modcr_qkv_attn_bwd, which serves them "
+                        "from lse and the q|k|v dump", who, S);
+        return MODCR_ERR_UNSUPPORTED;
+    }
+    MODCR_REQUIRE(!d_align || (align_t > 0 && align_t < S), "%s: align_t=%d out of range", who, align_t);
+    MODCR_REQUIRE(((uintptr_t)mask_bits & 3) == 0 && ((uintptr_t)d_align & 3) == 0, "%s: mask_bits / d_align not 4-byte aligned", who);
+    AttnBwdCall c = attn_bias_call(who, dctx, x, wqkv, bqkv, attn_bias, bias_stride_n, bias_stride_a, bias_stride_q, head_mask, head_mask_stride_n,
+                                   dx_residual, dx, dwqkv, dbqkv, accumulate, d_bias, N, S, H, A, attn_p, seed, offset, workspace, workspace_bytes,
+                                   dtype, stream);
+    c.max_keys = 512; c.wide_dropout = true;
+    c.chunk_id = chunk_id; c.chunk_t = chunk_t; c.d_head_mask = d_head_mask;
+    c.bits = mask_bits; c.d_align = d_align; c.align_t = d_align ? align_t : 0; c.flags = flags;
+    return attn_bwd(c);
 }

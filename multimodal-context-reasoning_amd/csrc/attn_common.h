@@ -207,6 +207,15 @@ struct AttnBiasBwdArgs {
     // attn_long_bwd.hip only: the per-row statistics fp32 [N A][3][SP] (row max, 1 / row sum, D; SP = S rounded up to 64), 16-byte
     // aligned, written by its query kernel and read by its key kernel.  The whole-row cores never look at it.
     float* stats;
+    // modcr_qkv_attn_long_align_bwd, attn_long_bwd.hip only (P = 0, S > 256); at the end, so that every other field keeps its offset.
+    // bits: u32 [N, S, ceil(S / 32)] dense mask, bit j of row (n, i) clear = -10000 on top of the bias (the MASK instantiations), or
+    // NULL.  d_align: fp32 [N, T, R] gradient of the head-summed text -> region map, T = align_t, R = S - T (the DALIGN
+    // instantiations), or NULL: E_ij = d_align[n, i, j - T] for i < T <= j joins dP of every head -- under the keep mask with
+    // side_post_drop (the map summed the probabilities after the dropout), plainly without.
+    const uint32_t* bits;
+    const float* d_align;
+    int align_t;
+    int side_post_drop;
 };
 // core: 1 = attn_bias_bwd_mfma_kernel (bf16, P + S <= 192), 2 = attn_bias_bwd_f32_kernel (P + S <= 256); prefix rows where b.P > 0
 __attribute__((visibility("hidden"))) int modcr_launch_attn_bias_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype, hipStream_t stream);
@@ -230,6 +239,9 @@ struct AttnLongArgs {
     uint64_t drop_key;
     float drop_keep;
     int side_post_drop;
+    // modcr_qkv_attn_long_align_fwd: bits (no prefix rows, P + S > 256) is read by the BIAS variant, 0 / -10000 on top of the bias; with
+    // it the bits alone select that variant.  0: the bias variant never looks at bits.  Last, so that every other field keeps its offset.
+    int bits_on_bias;
 };
 // ev0 / ev1 (or NULL): stamped at the start and the end of the kernel (modcr_time_next_attn)
 __attribute__((visibility("hidden"))) int modcr_launch_attn_long(const AttnLongArgs& p, int32_t dtype, hipStream_t stream, hipEvent_t ev0,

@@ -39,6 +39,10 @@
 // [prefix ; x]; the lane's g is the layout's l4, so attn_drop8_rt clears the dropped bf16 pairs of the P^T fragments as in the tile
 // kernels.  The context is P o m / (1 - p); the side outputs are the un-dropped probabilities, or with side_post_drop the
 // post-dropout ones (the second sweep regenerates the keep bits).
+// Mask bits on the bias variant (template parameter BITS, modcr_qkv_attn_long_align_fwd; the instantiations without it compile as
+// before): bit j of bits[n, q, :] (u32 [N, S, ceil(S / 32)], no prefix rows) adds 0 or -10000 to the bias of (q, j) BEFORE the
+// multiplication by log2e, so a call with bits is bit for bit the call with the bits folded into a 0 / -10000 bias.  The two 32-key
+// words of a tile and query are loaded as MODE 0 loads them; a padded query row takes row S - 1's words.
 #include <hip/hip_ext.h>
 
 #include "common.h"
@@ -72,8 +76,9 @@ __device__ __forceinline__ uint32_t lg_half(const uint4& v, int e) {
 // MODE 0 = binary masks (key_mask / bits), 1 = bias / head mask, 2 = the same with dropout.  LDS admits four workgroups per CU = two
 // waves per SIMD; the bias instantiations are asked to stay inside that register budget (left alone they take 208-230 VGPRs beside 32
 // AGPRs and the ones with side outputs drop to one wave per SIMD; asked, 224-236 unified, no spill).  MODE 0 compiles as before.
-template <bool SIDE, int MODE>
+template <bool SIDE, int MODE, bool BITS = false>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MODE != 0 ? 2 : 1))) void attn_long_bf16_kernel(AttnLongArgs p) {
+    static_assert(!BITS || MODE != 0, "MODE 0 reads its bits itself");
     __shared__ __attribute__((aligned(16))) bf16 sm[2 * LG_BUF];
     const int S = p.S, L = p.P + S, H = p.H;
     const int n = blockIdx.z, a = blockIdx.y;
@@ -172,13 +177,28 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MODE != 0 ?
             }
         }
         if constexpr (MODE != 0) {
+            [[maybe_unused]] uint32_t wb[2][2];         // BITS: the two 32-key words of the tile per query (no prefix rows: L = S)
+            if constexpr (BITS) {
+                const int LW = (L + 31) >> 5;
+#pragma unroll
+                for (int qs = 0; qs < 2; ++qs) {
+                    const uint32_t* row = p.bits + ((int64_t)n * S + (qrow[qs] < S ? qrow[qs] : S - 1)) * LW;
+                    wb[qs][0] = row[2 * t];
+                    wb[qs][1] = 2 * t + 1 < LW ? row[2 * t + 1] : 0u;
+                }
+            }
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const bool in = t * 64 + kb * 16 + 4 * g + i < L;
+                    const int j = t * 64 + kb * 16 + 4 * g + i;
+                    const bool in = j < L;
 #pragma unroll
-                    for (int qs = 0; qs < 2; ++qs) s[qs][kb][i] = in ? fmaf(s[qs][kb][i], sc, bb[qs][kb][i] * LOG2E) : -INFINITY;
+                    for (int qs = 0; qs < 2; ++qs) {
+                        float bv = bb[qs][kb][i];
+                        if constexpr (BITS) bv += ((wb[qs][kb >> 1] >> (j & 31)) & 1u) ? 0.f : MODCR_NEG;
+                        s[qs][kb][i] = in ? fmaf(s[qs][kb][i], sc, bv * LOG2E) : -INFINITY;
+                    }
                 }
             return;
         }
@@ -358,8 +378,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MODE != 0 ?
 }
 
 // fp32 parity core: 4 waves x 16 queries per (64-query block, head, sequence); K and V tiles of 64 keys in LDS
-template <bool BIAS>
+template <bool BIAS, bool BITS = false>
 __global__ __launch_bounds__(256) void attn_long_f32_kernel(AttnLongArgs p) {
+    static_assert(!BITS || BIAS, "the binary variant reads its bits itself");
     __shared__ float sK[64 * 65], sV[64 * 65], sQ[4 * 16 * 64], sP[4 * 64];
     const int S = p.S, L = p.P + S, H = p.H;
     const int n = blockIdx.z, a = blockIdx.y;
@@ -397,6 +418,11 @@ __global__ __launch_bounds__(256) void attn_long_f32_kernel(AttnLongArgs p) {
         const int q = q0 + qi < S ? q0 + qi : S - 1;
         if constexpr (BIAS) {
             if (j >= L) return -INFINITY;
+            if constexpr (BITS) {                   // 0 / -10000 joins the bias before log2e: the folded call, bit for bit
+                const bool see = (p.bits[((int64_t)n * S + q) * ((L + 31) >> 5) + (j >> 5)] >> (j & 31)) & 1u;
+                const float bv = (p.bias ? p.bias[n * p.bias_sn + a * p.bias_sa + q * p.bias_sq + j] : 0.f) + (see ? 0.f : MODCR_NEG);
+                return fmaf(s, sc, bv * LOG2E);
+            }
             return p.bias ? fmaf(s, sc, p.bias[n * p.bias_sn + a * p.bias_sa + q * p.bias_sq + j] * LOG2E) : s * sc;
         } else {
             return j < L ? s * sc + lg_mask(p, n, q, j, L) : -INFINITY;
@@ -475,9 +501,18 @@ void lg_launch(K kernel, dim3 grid, dim3 block, hipStream_t st, hipEvent_t ev0, 
 int modcr_launch_attn_long(const AttnLongArgs& p, int32_t dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     const dim3 grid((p.S + 63) / 64, p.A, p.N);
     const bool side = p.probs || p.align_map;
-    const int mode = !(p.bias || p.head_mask) ? 0 : p.drop_thr16 ? 2 : 1;
+    const bool bits = p.bits_on_bias && p.bits;     // (modcr_qkv_attn_long_align_fwd: the bits select the bias variant by themselves)
+    const int mode = !(p.bias || p.head_mask || bits) ? 0 : p.drop_thr16 ? 2 : 1;
     if (dtype == MODCR_BF16) {
-        if (mode == 0) {
+        if (bits) {
+            if (mode == 1) {
+                if (side) lg_launch(attn_long_bf16_kernel<true, 1, true>, grid, dim3(128), st, ev0, ev1, p);
+                else lg_launch(attn_long_bf16_kernel<false, 1, true>, grid, dim3(128), st, ev0, ev1, p);
+            } else {
+                if (side) lg_launch(attn_long_bf16_kernel<true, 2, true>, grid, dim3(128), st, ev0, ev1, p);
+                else lg_launch(attn_long_bf16_kernel<false, 2, true>, grid, dim3(128), st, ev0, ev1, p);
+            }
+        } else if (mode == 0) {
             if (side) lg_launch(attn_long_bf16_kernel<true, 0>, grid, dim3(128), st, ev0, ev1, p);
             else lg_launch(attn_long_bf16_kernel<false, 0>, grid, dim3(128), st, ev0, ev1, p);
         } else if (mode == 1) {
@@ -489,6 +524,8 @@ int modcr_launch_attn_long(const AttnLongArgs& p, int32_t dtype, hipStream_t st,
         }
     } else if (mode == 0) {
         lg_launch(attn_long_f32_kernel<false>, grid, dim3(256), st, ev0, ev1, p);
+    } else if (bits) {
+        lg_launch((attn_long_f32_kernel<true, true>), grid, dim3(256), st, ev0, ev1, p);
     } else {
         lg_launch(attn_long_f32_kernel<true>, grid, dim3(256), st, ev0, ev1, p);
     }

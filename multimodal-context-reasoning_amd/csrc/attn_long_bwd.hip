@@ -43,6 +43,21 @@
 //   key kernel: the key lies on the lane, its four values are four QUERIES -- four counter rows, but one l4 and one pair of word
 //     multipliers, fixed for the whole kernel.  Each lane of a quad hashes the row of one of the quad's four queries and the words
 //     travel by quad broadcasts (attn_bias_bwd_mfma_kernel's scheme): three multiply-folds per lane and 16-query block.
+//
+// Dense mask bits and the align map's gradient (template parameters MASK and DALIGN, modcr_qkv_attn_long_align_bwd, P = 0; the
+// instantiations without them compile as before):
+//   MASK: bit j of bits[n, i, :] clear adds -10000 to the bias of (i, j) before the multiplication by log2e, as the forward's BITS
+//     variant does; the query kernel loads the two words of a tile and query, the key kernel one word per query row and picks the
+//     lane's bit.  A padded query row takes row S - 1's words in both kernels.
+//   DALIGN: G = d_align [N, T, R] is the gradient of align_map[n, i, r] = sum_a hm A^side_{i, T + r} (i < T), A^side = P, or P~ with
+//     side_post_drop.  E_ij = G[n, i, j - T] for i < T <= j, else 0:
+//         dP_ij = (dctx_i . v_j) m_ij / (1 - p) + E_ij (post ? m_ij / (1 - p) : 1)        D_i = dctx_i . (P~.V)_i + sum_j A^side_ij E_ij
+//     The align share of D_i is one more online accumulator of sweep 1: c_i = sum_j e_ij E_ij (keep factor), e_ij the tile's
+//     exponentials, rescaled by the running max's alpha like the row sum, reduced over the row's four lanes and divided by the row sum
+//     at the end -- no pass of its own.  It is skipped for query blocks at or beyond T and key tiles below T (both uniform); sweep 2
+//     and the key kernel add E to dP.  A lane's four E values are consecutive floats in the query kernel (one 16-byte load when the
+//     address is aligned and the four are inside the row, scalar loads otherwise) and four query rows of one key, R floats apart, in
+//     the key kernel.  hm stays a common factor (the map carries it too), so d_hm = sum_i D_i with both shares.
 #include "common.h"
 #include "attn_common.h"
 
@@ -75,8 +90,18 @@ __device__ __forceinline__ f32x4 alb_bias4(const float* row, bool vec, int j, in
     return v;
 }
 
+// the lane's four align-map gradients grow[jr .. jr + 3] of one text row (jr = key - T; outside [0, R): 0)
+__device__ __forceinline__ f32x4 alb_dalign4(const float* grow, int jr, int R) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (jr >= 0 && jr + 3 < R && (reinterpret_cast<uintptr_t>(grow + jr) & 15) == 0) return *reinterpret_cast<const f32x4*>(grow + jr);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (jr + i >= 0 && jr + i < R) v[i] = grow[jr + i];
+    return v;
+}
+
 // ---- bf16 core, query kernel: statistics sweep + query sweep of one 64-query block -----------------------------------------
-template <bool BIAS, bool DBIAS, bool DROP>
+template <bool BIAS, bool DBIAS, bool DROP, bool MASK = false, bool DALIGN = false>
 __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[ALB::SMEM];
     const int S = p.S, P = p.P, L = S + P, H = p.H;
@@ -115,6 +140,30 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
         dthr2 = attn_thrm1_2(p.drop_thr16);
     }
 
+    // MASK: the query's row of words (P = 0: L = S keys).  DALIGN: the query's row of G; text rows only, in blocks that hold one
+    [[maybe_unused]] const uint32_t* wrow = nullptr;
+    [[maybe_unused]] const int LW = (L + 31) >> 5;
+    if constexpr (MASK) wrow = p.bits + ((int64_t)n * S + qc) * LW;
+    [[maybe_unused]] const int T = DALIGN ? p.align_t : 0, R = S - T;
+    [[maybe_unused]] const bool ablock = DALIGN && (int)blockIdx.x * 64 < T;
+    [[maybe_unused]] const float* grow = nullptr;
+    if constexpr (DALIGN) grow = p.d_align + ((int64_t)n * T + min(qrow, T - 1)) * R;
+    [[maybe_unused]] const bool apost = DALIGN && DROP && p.side_post_drop;
+    // E (x the keep factor when the map took the dropped probabilities) of the lane's four keys of block kb of tile t
+    [[maybe_unused]] auto align4 = [&](int t, int kb) {
+        f32x4 e4 = alb_dalign4(grow, t * 64 + kb * 16 + 4 * g - T, R);
+        if (qrow >= T) e4 = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (DROP) {
+            if (apost) {
+                const uint32_t hx = attn_drop_word(dbase, 2 * (4 * t + kb), p.drop_key);
+                const uint32_t hy = attn_drop_word(dbase, 2 * (4 * t + kb) + 1, p.drop_key);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) e4[i] = attn_keep_field(hx, hy, i, p.drop_thr16) ? e4[i] * p.drop_keep : 0.f;
+            }
+        }
+        return e4;
+    };
+
     // staging: piece r of thread t = row (t + 256 r) >> 3 of the tile, 16-byte chunk t & 7; zeros beyond L
     bf16x8 kreg[2], vreg[2];
     auto load = [&](int t) {
@@ -148,6 +197,11 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb) bb[kb] = alb_bias4(brow, bvec, t * 64 + kb * 16 + 4 * g, L);
         }
+        [[maybe_unused]] uint32_t wb[2];                    // MASK: the tile's two 32-key words of the query
+        if constexpr (MASK) {
+            wb[0] = wrow[2 * t];
+            wb[1] = 2 * t + 1 < LW ? wrow[2 * t + 1] : 0u;
+        }
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
             const bf16x8 k0 = *reinterpret_cast<const bf16x8*>(K + swz128(kb * 16 + l15, g));
@@ -158,7 +212,10 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const bool in = t * 64 + kb * 16 + 4 * g + i < L;
-                if constexpr (BIAS) s[kb][i] = in ? fmaf(c[i], SC, bb[kb][i] * LOG2E) : -INFINITY;
+                if constexpr (MASK) {                       // 0 / -10000 joins the bias before log2e, as in the forward
+                    const float hide = ((wb[kb >> 1] >> ((kb & 1) * 16 + 4 * g + i)) & 1u) ? 0.f : MODCR_NEG;
+                    s[kb][i] = in ? fmaf(c[i], SC, (BIAS ? bb[kb][i] + hide : hide) * LOG2E) : -INFINITY;
+                } else if constexpr (BIAS) s[kb][i] = in ? fmaf(c[i], SC, bb[kb][i] * LOG2E) : -INFINITY;
                 else s[kb][i] = in ? c[i] * SC : -INFINITY;
             }
         }
@@ -179,6 +236,7 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
 
     // ---- sweep 1: row max, row sum, context accumulators (online softmax) ------------------------------------------
     float m = -INFINITY, lsum = 0.f;
+    [[maybe_unused]] float asum = 0.f;                      // DALIGN: sum_j e_ij E_ij (keep factor), on the row sum's scale
     f32x4 o[4];
 #pragma unroll
     for (int db = 0; db < 4; ++db) o[db] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -197,15 +255,24 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
         const float alpha = __builtin_amdgcn_exp2f(m - ms);
         m = mn;
         float sum = 0.f;
+        [[maybe_unused]] float asub = 0.f;
+        [[maybe_unused]] const bool atile = ablock && t * 64 + 63 >= T;       // (uniform: the block holds text rows, the tile region keys)
         bf16x8 pb[2];                                       // P^T fragments: step ks = keys 32 ks + (4 g + e | 16 + 4 g + e)
 #pragma unroll
-        for (int kb = 0; kb < 4; ++kb)
+        for (int kb = 0; kb < 4; ++kb) {
+            [[maybe_unused]] f32x4 e4 = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (DALIGN) {
+                if (atile) e4 = align4(t, kb);
+            }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const float e = __builtin_amdgcn_exp2f(s[kb][i] - ms);
                 sum += e;
+                if constexpr (DALIGN) asub = fmaf(e, e4[i], asub);
                 pb[kb >> 1][(kb & 1) * 4 + i] = (bf16)e;
             }
+        }
+        if constexpr (DALIGN) asum = asum * alpha + asub;
         if constexpr (DROP) {                               // the row sum keeps the un-dropped weights; the context takes P o m
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) pb[ks] = attn_drop8_rt(pb[ks], dbase, 2 * t + ks, p.drop_key, dthr2);
@@ -236,6 +303,11 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
     dl += __shfl_xor(dl, 16, 64);
     dl += __shfl_xor(dl, 32, 64);
     dl *= DROP ? inv * p.drop_keep : inv;
+    if constexpr (DALIGN) {                                 // the align share of D: the accumulator over the row's four lanes / row sum
+        asum += __shfl_xor(asum, 16, 64);
+        asum += __shfl_xor(asum, 32, 64);
+        dl = fmaf(asum, inv, dl);
+    }
     if (g == 0) { stats[qrow] = mf; stats[SP + qrow] = inv; stats[2 * SP + qrow] = dl; }
 
     // ---- sweep 2: dS, d_bias, dQ ------------------------------------------------------------------------------------
@@ -266,6 +338,9 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
                 const uint32_t hy = attn_drop_word(dbase, 2 * (4 * t + kb) + 1, p.drop_key);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) dp[i] = attn_keep_field(hx, hy, i, p.drop_thr16) ? dp[i] * p.drop_keep : 0.f;
+            }
+            if constexpr (DALIGN) {                         // + E, under the keep mask when the map took the dropped probabilities
+                if (ablock && t * 64 + 63 >= T) dp += align4(t, kb);
             }
             f32x4 ds;
 #pragma unroll
@@ -301,8 +376,10 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_kernel(AttnBiasBwdArgs p)
 }
 
 // ---- bf16 core, key kernel: dK | dV of one 64-key block over the streamed query tiles ----------------------------------------
-template <bool BIAS, bool DROP>
-__global__ __launch_bounds__(256) void attn_long_bwd_k_kernel(AttnBiasBwdArgs p) {
+// (DALIGN without DROP: asked to stay inside the two waves per SIMD its twins have -- 218-253 registers, no spill; with DROP the same
+// request spills 7-30 registers, so those are left alone: 252-292 registers, three of the four at one wave per SIMD)
+template <bool BIAS, bool DROP, bool MASK = false, bool DALIGN = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DALIGN && !DROP ? 2 : 1))) void attn_long_bwd_k_kernel(AttnBiasBwdArgs p) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[ALB::SMEM];
     const int S = p.S, P = p.P, L = S + P, H = p.H;
     const int n = blockIdx.z, a = blockIdx.y;
@@ -341,6 +418,16 @@ __global__ __launch_bounds__(256) void attn_long_bwd_k_kernel(AttnBiasBwdArgs p)
         dcx = attn_drop_const(2 * (key >> 4));
         dcy = attn_drop_const(2 * (key >> 4) + 1);
     }
+    // MASK: the key's word column and bit (P = 0: L = S).  DALIGN: the key's column of G; region keys only, in blocks that hold one
+    [[maybe_unused]] const int LW = (L + 31) >> 5;
+    [[maybe_unused]] const uint32_t* wcol = nullptr;
+    if constexpr (MASK) wcol = p.bits + (int64_t)n * S * LW + (keyc >> 5);
+    [[maybe_unused]] const int T = DALIGN ? p.align_t : 0, R = S - T;
+    [[maybe_unused]] const bool ablock = DALIGN && (int)blockIdx.x * 64 + 63 >= T;
+    [[maybe_unused]] const bool akey = DALIGN && key >= T && key < L;
+    [[maybe_unused]] const float* gcol = nullptr;
+    if constexpr (DALIGN) gcol = p.d_align + (int64_t)n * T * R + (akey ? key - T : 0);
+    [[maybe_unused]] const bool apost = DALIGN && DROP && p.side_post_drop;
     // staging of query tile t: Q | dO rows, zeros beyond S
     bf16x8 qreg[2], dreg[2];
     auto load = [&](int t) {
@@ -384,6 +471,19 @@ __global__ __launch_bounds__(256) void attn_long_bwd_k_kernel(AttnBiasBwdArgs p)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) bq[e] = bias[(uint32_t)min(q0 + e, S - 1) * bsq + (uint32_t)keyc];
             }
+            [[maybe_unused]] f32x4 hide;                    // MASK: 0 / -10000 of (query q0 + e, key): one word per query row, the lane's bit
+            if constexpr (MASK) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) hide[e] = ((wcol[(uint32_t)min(q0 + e, S - 1) * (uint32_t)LW] >> (keyc & 31)) & 1u) ? 0.f : MODCR_NEG;
+            }
+            [[maybe_unused]] f32x4 e4 = {0.f, 0.f, 0.f, 0.f};   // DALIGN: E of the lane's four queries, R floats apart (text rows, region key)
+            if constexpr (DALIGN) {
+                if (ablock && t * 64 < T) {                 // (uniform: the block holds region keys, the tile text rows)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (akey && q0 + e < T) e4[e] = gcol[(uint32_t)(q0 + e) * (uint32_t)R];
+                }
+            }
             const bf16x8 fq0 = *reinterpret_cast<const bf16x8*>(Q + swz128(qb * 16 + l15, g));
             const bf16x8 fq1 = *reinterpret_cast<const bf16x8*>(Q + swz128(qb * 16 + l15, 4 + g));
             const bf16x8 fd0 = *reinterpret_cast<const bf16x8*>(D + swz128(qb * 16 + l15, g));
@@ -405,15 +505,19 @@ __global__ __launch_bounds__(256) void attn_long_bwd_k_kernel(AttnBiasBwdArgs p)
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float sv = (BIAS ? fmaf(c[e], SC, bq[e] * LOG2E) : c[e] * SC) + kpad;
+                float sv;
+                if constexpr (MASK) sv = fmaf(c[e], SC, (BIAS ? bq[e] + hide[e] : hide[e]) * LOG2E) + kpad;
+                else sv = (BIAS ? fmaf(c[e], SC, bq[e] * LOG2E) : c[e] * SC) + kpad;
                 const float pe = __builtin_amdgcn_exp2f(sv - m4[e]) * i4[e];
                 if constexpr (DROP) {
                     const float mk = attn_keep_field(xq[e], yq[e], key & 3, p.drop_thr16) ? p.drop_keep : 0.f;   // of (query q0 + e, key)
                     pB[qb >> 1][(qb & 1) * 4 + e] = (bf16)(pe * mk);        // dV takes the masked probabilities
-                    dsB[qb >> 1][(qb & 1) * 4 + e] = (bf16)(pe * (mk * dp[e] - d4[e]));
+                    if constexpr (DALIGN) dsB[qb >> 1][(qb & 1) * 4 + e] = (bf16)(pe * ((apost ? mk * (dp[e] + e4[e]) : fmaf(mk, dp[e], e4[e])) - d4[e]));
+                    else dsB[qb >> 1][(qb & 1) * 4 + e] = (bf16)(pe * (mk * dp[e] - d4[e]));
                 } else {
                     pB[qb >> 1][(qb & 1) * 4 + e] = (bf16)pe;
-                    dsB[qb >> 1][(qb & 1) * 4 + e] = (bf16)(pe * (dp[e] - d4[e]));
+                    if constexpr (DALIGN) dsB[qb >> 1][(qb & 1) * 4 + e] = (bf16)(pe * (dp[e] + e4[e] - d4[e]));
+                    else dsB[qb >> 1][(qb & 1) * 4 + e] = (bf16)(pe * (dp[e] - d4[e]));
                 }
             }
         }
@@ -452,7 +556,7 @@ __global__ __launch_bounds__(64) void attn_long_bwd_dhm_kernel(const float* stat
 }
 
 // ---- exact fp32 core, query kernel: 4 waves x 16 queries; K, V tiles of 64 keys in LDS ----------------------------------------
-template <bool DROP>
+template <bool DROP, bool MASK = false, bool DALIGN = false>
 __global__ __launch_bounds__(256) void attn_long_bwd_q_f32_kernel(AttnBiasBwdArgs p) {
     extern __shared__ float sm[];
     float* sK = sm;                          // [64][65]
@@ -500,6 +604,10 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_f32_kernel(AttnBiasBwdArg
 #pragma unroll 8
         for (int d = 0; d < 64; ++d) s = fmaf(q_img[qi * 64 + d], sK[lane * 65 + d], s);
         const int q = min(q0 + qi, S - 1);
+        if constexpr (MASK) {                   // 0 / -10000 joins the bias before log2e, as in the forward
+            const bool see = (p.bits[((int64_t)n * S + q) * ((L + 31) >> 5) + (j >> 5)] >> (j & 31)) & 1u;
+            return fmaf(s, SC, ((bias ? bias[(int64_t)q * p.bias_sq + j] : 0.f) + (see ? 0.f : MODCR_NEG)) * LOG2E);
+        }
         return bias ? fmaf(s, SC, bias[(int64_t)q * p.bias_sq + j] * LOG2E) : s * SC;
     };
     // DROP: keep / (1 - p) or 0 of key 64 t + lane for query q0 + qi (the wide layout)
@@ -509,10 +617,27 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_f32_kernel(AttnBiasBwdArg
         attn_drop_words(attn_drop_row(n, p.A, a, q0 + qi, L), j >> 2, p.drop_key, hx, hy);
         return attn_keep_field(hx, hy, j & 3, p.drop_thr16) ? p.drop_keep : 0.f;
     };
+    // DALIGN: E of (query q0 + qi, key 64 t + lane), x the keep factor when the map took the dropped probabilities
+    [[maybe_unused]] const int T = DALIGN ? p.align_t : 0, R = S - T;
+    [[maybe_unused]] const float* galign = DALIGN ? p.d_align + ((int64_t)n * T + q0) * R - T : nullptr;    // row q0 of G, indexed by the key
+    [[maybe_unused]] auto ealign = [&](int t, int qi) {
+        const int q = q0 + qi, j = t * 64 + lane;
+        if (q >= T || j < T || j >= L) return 0.f;
+        float e = galign[(uint32_t)qi * (uint32_t)R + (uint32_t)j];
+        if constexpr (DROP) {
+            if (p.side_post_drop) e *= keep(t, qi);
+        }
+        return e;
+    };
     // ---- sweep 1: statistics --------------------------------------------------------------------------------
     float m[16], lsum[16], o[16];
+    [[maybe_unused]] float al[DALIGN ? 16 : 1];     // the align share of D: sum_j e_ij E_ij (keep factor), on the row sum's scale
 #pragma unroll
     for (int qi = 0; qi < 16; ++qi) { m[qi] = -INFINITY; lsum[qi] = 0.f; o[qi] = 0.f; }
+    if constexpr (DALIGN) {
+#pragma unroll
+        for (int qi = 0; qi < 16; ++qi) al[qi] = 0.f;
+    }
     for (int t = 0; t < ntiles; ++t) {
         load(t);
 #pragma unroll
@@ -523,6 +648,10 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_f32_kernel(AttnBiasBwdArg
             const float alpha = exp2f(m[qi] - ms);
             const float e = exp2f(s - ms);
             lsum[qi] = lsum[qi] * alpha + wave_sum(e);
+            if constexpr (DALIGN) {             // (uniform: the wave holds text rows, the tile region keys)
+                if (q0 < T && t * 64 + 63 >= T) al[qi] = al[qi] * alpha + wave_sum(e * ealign(t, qi));
+                else al[qi] *= alpha;
+            }
             m[qi] = mn;
             if constexpr (DROP) p_img[lane] = e * keep(t, qi);      // the row sum keeps the un-dropped weights
             else p_img[lane] = e;
@@ -541,6 +670,7 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_f32_kernel(AttnBiasBwdArg
         if (m[qi] == -INFINITY) m[qi] = 0.f;
         lsum[qi] = inv;
         o[qi] = wave_sum(o[qi] * d_img[qi * 64 + lane]) * inv;
+        if constexpr (DALIGN) o[qi] = fmaf(al[qi], inv, o[qi]);
         if (lane == 0) { stats[q0 + qi] = m[qi]; stats[SP + q0 + qi] = inv; stats[2 * SP + q0 + qi] = o[qi]; }
     }
     // ---- sweep 2: dS, d_bias, dQ ------------------------------------------------------------------------------
@@ -557,6 +687,9 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_f32_kernel(AttnBiasBwdArg
 #pragma unroll 8
             for (int d = 0; d < 64; ++d) dp = fmaf(d_img[qi * 64 + d], sV[lane * 65 + d], dp);
             if constexpr (DROP) dp *= keep(t, qi);
+            if constexpr (DALIGN) {
+                if (q0 < T && t * 64 + 63 >= T) dp += ealign(t, qi);
+            }
             const float ds = exp2f(s - m[qi]) * lsum[qi] * (dp - o[qi]);
             if (dbias && q < S && j < L) dbias[(int64_t)q * L + j] = ds * hm;
             p_img[lane] = ds;
@@ -575,7 +708,7 @@ __global__ __launch_bounds__(256) void attn_long_bwd_q_f32_kernel(AttnBiasBwdArg
 }
 
 // ---- exact fp32 core, key kernel: 4 waves x 16 keys; Q, dO tiles of 64 queries in LDS -----------------------------------------
-template <bool DROP>
+template <bool DROP, bool MASK = false, bool DALIGN = false>
 __global__ __launch_bounds__(256) void attn_long_bwd_k_f32_kernel(AttnBiasBwdArgs p) {
     extern __shared__ float sm[];
     float* sQ = sm;                          // [64][65]
@@ -596,6 +729,7 @@ __global__ __launch_bounds__(256) void attn_long_bwd_k_f32_kernel(AttnBiasBwdArg
     const float* stats = p.stats + ((int64_t)n * p.A + a) * 3 * SP;
     const float hm = p.head_mask ? p.head_mask[(int64_t)n * p.head_mask_sn + a] : 1.0f;
     const int k0 = blockIdx.x * 64 + wave * 16;
+    [[maybe_unused]] const int T = DALIGN ? p.align_t : 0;
     float* k_img = sK + wave * 16 * 64;
     float* v_img = sV + wave * 16 * 64;
     float* wp = sW + wave * 128;
@@ -621,6 +755,11 @@ __global__ __launch_bounds__(256) void attn_long_bwd_k_f32_kernel(AttnBiasBwdArg
         __syncthreads();
         const int i = t * 64 + lane;
         const float mi = sSt[lane], ii = sSt[64 + lane], di = sSt[128 + lane];
+        // DALIGN: the lane's text row of G, shifted so that the key indexes it (null: a region row, or no text row in this tile)
+        [[maybe_unused]] const float* galign = nullptr;
+        if constexpr (DALIGN) {
+            if (i < T) galign = p.d_align + ((int64_t)n * T + i) * (S - T) - T;
+        }
 #pragma unroll
         for (int kj = 0; kj < 16; ++kj) {
             const int j = k0 + kj;
@@ -631,9 +770,27 @@ __global__ __launch_bounds__(256) void attn_long_bwd_k_f32_kernel(AttnBiasBwdArg
                 dp = fmaf(sD[lane * 65 + d], v_img[kj * 64 + d], dp);
             }
             float sv = -INFINITY;
-            if (j < L) sv = bias ? fmaf(s, SC, bias[(int64_t)min(i, S - 1) * p.bias_sq + j] * LOG2E) : s * SC;
+            if constexpr (MASK) {               // 0 / -10000 joins the bias before log2e, as in the forward
+                if (j < L) {
+                    const int ic = min(i, S - 1);
+                    const bool see = (p.bits[((int64_t)n * S + ic) * ((L + 31) >> 5) + (j >> 5)] >> (j & 31)) & 1u;
+                    sv = fmaf(s, SC, ((bias ? bias[(int64_t)ic * p.bias_sq + j] : 0.f) + (see ? 0.f : MODCR_NEG)) * LOG2E);
+                }
+            } else {
+                if (j < L) sv = bias ? fmaf(s, SC, bias[(int64_t)min(i, S - 1) * p.bias_sq + j] * LOG2E) : s * SC;
+            }
             const float pe = exp2f(sv - mi) * ii;
-            if constexpr (DROP) {               // keep / (1 - p) or 0 of (query i, key j): dV takes the masked probabilities
+            if constexpr (DALIGN) {             // + E of (query i, key j), under the keep mask when the map took the dropped probabilities
+                const float ea = galign && j >= T && j < L && k0 + 15 >= T ? galign[j] : 0.f;
+                float mk = 1.f;
+                if constexpr (DROP) {
+                    uint32_t hx, hy;
+                    attn_drop_words(attn_drop_row(n, p.A, a, i, L), j >> 2, p.drop_key, hx, hy);
+                    mk = attn_keep_field(hx, hy, j & 3, p.drop_thr16) ? p.drop_keep : 0.f;
+                }
+                wp[lane] = pe * mk;
+                ws[lane] = pe * ((DROP && p.side_post_drop ? mk * (dp + ea) : fmaf(mk, dp, ea)) - di);
+            } else if constexpr (DROP) {        // keep / (1 - p) or 0 of (query i, key j): dV takes the masked probabilities
                 uint32_t hx, hy;
                 attn_drop_words(attn_drop_row(n, p.A, a, i, L), j >> 2, p.drop_key, hx, hy);
                 const float mk = attn_keep_field(hx, hy, j & 3, p.drop_thr16) ? p.drop_keep : 0.f;
@@ -677,32 +834,52 @@ int alb_configure(K kernel, int bytes, bool& configured) {
     return MODCR_OK;
 }
 
-template <bool DROP>
+template <bool DROP, bool MASK = false, bool DALIGN = false>
 int launch_bf16(const AttnBiasBwdArgs& b, hipStream_t st) {
     const dim3 gq((b.S + 63) / 64, b.A, b.N), gk((b.S + b.P + 63) / 64, b.A, b.N);
-    if (!b.bias) hipLaunchKernelGGL((attn_long_bwd_q_kernel<false, false, DROP>), gq, dim3(ALB::NT), 0, st, b);
-    else if (!b.d_bias) hipLaunchKernelGGL((attn_long_bwd_q_kernel<true, false, DROP>), gq, dim3(ALB::NT), 0, st, b);
-    else hipLaunchKernelGGL((attn_long_bwd_q_kernel<true, true, DROP>), gq, dim3(ALB::NT), 0, st, b);
+    if (!b.bias) hipLaunchKernelGGL((attn_long_bwd_q_kernel<false, false, DROP, MASK, DALIGN>), gq, dim3(ALB::NT), 0, st, b);
+    else if (!b.d_bias) hipLaunchKernelGGL((attn_long_bwd_q_kernel<true, false, DROP, MASK, DALIGN>), gq, dim3(ALB::NT), 0, st, b);
+    else hipLaunchKernelGGL((attn_long_bwd_q_kernel<true, true, DROP, MASK, DALIGN>), gq, dim3(ALB::NT), 0, st, b);
     int rc = modcr_check_launch("attn_long_bwd_q");
     if (rc != MODCR_OK) return rc;
-    if (b.bias) hipLaunchKernelGGL((attn_long_bwd_k_kernel<true, DROP>), gk, dim3(ALB::NT), 0, st, b);
-    else hipLaunchKernelGGL((attn_long_bwd_k_kernel<false, DROP>), gk, dim3(ALB::NT), 0, st, b);
+    if (b.bias) hipLaunchKernelGGL((attn_long_bwd_k_kernel<true, DROP, MASK, DALIGN>), gk, dim3(ALB::NT), 0, st, b);
+    else hipLaunchKernelGGL((attn_long_bwd_k_kernel<false, DROP, MASK, DALIGN>), gk, dim3(ALB::NT), 0, st, b);
     return modcr_check_launch("attn_long_bwd_k");
 }
 
-template <bool DROP>
+template <bool DROP, bool MASK = false, bool DALIGN = false>
 int launch_f32(const AttnBiasBwdArgs& b, hipStream_t st) {
     static bool configured_q[MODCR_MAX_DEV] = {}, configured_k[MODCR_MAX_DEV] = {};
-    int rc = alb_configure(&attn_long_bwd_q_f32_kernel<DROP>, ALB::F32_Q, configured_q[modcr_device_index()]);
+    int rc = alb_configure(&attn_long_bwd_q_f32_kernel<DROP, MASK, DALIGN>, ALB::F32_Q, configured_q[modcr_device_index()]);
     if (rc != MODCR_OK) return rc;
-    rc = alb_configure(&attn_long_bwd_k_f32_kernel<DROP>, ALB::F32_K, configured_k[modcr_device_index()]);
+    rc = alb_configure(&attn_long_bwd_k_f32_kernel<DROP, MASK, DALIGN>, ALB::F32_K, configured_k[modcr_device_index()]);
     if (rc != MODCR_OK) return rc;
     const dim3 gq((b.S + 63) / 64, b.A, b.N), gk((b.S + b.P + 63) / 64, b.A, b.N);
-    hipLaunchKernelGGL(attn_long_bwd_q_f32_kernel<DROP>, gq, dim3(256), ALB::F32_Q, st, b);
+    hipLaunchKernelGGL((attn_long_bwd_q_f32_kernel<DROP, MASK, DALIGN>), gq, dim3(256), ALB::F32_Q, st, b);
     rc = modcr_check_launch("attn_long_bwd_q_f32");
     if (rc != MODCR_OK) return rc;
-    hipLaunchKernelGGL(attn_long_bwd_k_f32_kernel<DROP>, gk, dim3(256), ALB::F32_K, st, b);
+    hipLaunchKernelGGL((attn_long_bwd_k_f32_kernel<DROP, MASK, DALIGN>), gk, dim3(256), ALB::F32_K, st, b);
     return modcr_check_launch("attn_long_bwd_k_f32");
+}
+
+// the instantiation of a call: DROP from the dropout threshold, MASK / DALIGN from the pointers
+template <bool DROP>
+int launch_core(const AttnBiasBwdArgs& b, int core, hipStream_t st) {
+    const int v = (b.bits ? 1 : 0) | (b.d_align ? 2 : 0);
+    if (core == 3) {
+        switch (v) {
+        case 0: return launch_bf16<DROP>(b, st);
+        case 1: return launch_bf16<DROP, true, false>(b, st);
+        case 2: return launch_bf16<DROP, false, true>(b, st);
+        }
+        return launch_bf16<DROP, true, true>(b, st);
+    }
+    switch (v) {
+    case 0: return launch_f32<DROP>(b, st);
+    case 1: return launch_f32<DROP, true, false>(b, st);
+    case 2: return launch_f32<DROP, false, true>(b, st);
+    }
+    return launch_f32<DROP, true, true>(b, st);
 }
 
 }  // namespace
@@ -710,8 +887,11 @@ int launch_f32(const AttnBiasBwdArgs& b, hipStream_t st) {
 int modcr_launch_attn_long_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype, hipStream_t stream) {
     const bool prefix = b.P > 0;
     MODCR_REQUIRE(b.qkv && b.dctx && b.dqkv && b.stats && (b.kvh != nullptr) == prefix && (b.dkvh != nullptr) == prefix &&
-                      (b.bias || b.head_mask || b.d_head_mask) && (b.bias || !b.d_bias),
+                      (b.bias || b.head_mask || b.d_head_mask || b.bits) && (b.bias || !b.d_bias),
                   "attn_long_bwd: null pointer");
+    // (the bits and the align map's gradient: no prefix rows, a text block and a region block)
+    MODCR_REQUIRE(!(b.bits || b.d_align) || (b.P == 0 && b.S > 256), "attn_long_bwd: mask bits / d_align need P = 0 and S > 256 (S=%d P=%d)", b.S, b.P);
+    MODCR_REQUIRE(!b.d_align || (b.align_t > 0 && b.align_t < b.S), "attn_long_bwd: align_t=%d out of range", b.align_t);
     MODCR_REQUIRE((core == 3 || core == 4) && b.N > 0 && b.N <= 65535 && b.A > 0 && b.A <= 65535 && b.H == b.A * 64 && b.S > 0 && b.P >= 0 &&
                       (int64_t)b.S + b.P <= 512,
                   "attn_long_bwd: unsupported call (core=%d S=%d P=%d dropout %s)", core, b.S, b.P, b.drop_thr16 ? "on" : "off");
@@ -724,10 +904,10 @@ int modcr_launch_attn_long_bwd(const AttnBiasBwdArgs& b, int core, int32_t dtype
         MODCR_REQUIRE(dtype == MODCR_BF16 && modcr_aligned16(b.qkv) && modcr_aligned16(b.kvh) && modcr_aligned16(b.dctx) && modcr_aligned16(b.dqkv) &&
                           modcr_aligned16(b.dkvh),
                       "attn_long_bwd: the MFMA core takes 16-byte aligned bf16 rows");
-        rc = b.drop_thr16 ? launch_bf16<true>(b, stream) : launch_bf16<false>(b, stream);
+        rc = b.drop_thr16 ? launch_core<true>(b, core, stream) : launch_core<false>(b, core, stream);
     } else {
         MODCR_REQUIRE(dtype == MODCR_F32, "attn_long_bwd: the exact core takes fp32 rows and fp32 dctx (bf16 above 256 keys runs the MFMA core)");
-        rc = b.drop_thr16 ? launch_f32<true>(b, stream) : launch_f32<false>(b, stream);
+        rc = b.drop_thr16 ? launch_core<true>(b, core, stream) : launch_core<false>(b, core, stream);
     }
     if (rc != MODCR_OK || !b.d_head_mask) return rc;
     hipLaunchKernelGGL(attn_long_bwd_dhm_kernel, dim3(b.N * b.A), dim3(64), 0, stream, b.stats, b.d_head_mask, b.S, (b.S + 63) & ~63);

@@ -49,6 +49,8 @@ SIGNATURES = {
                                        _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _i32, _vp, _i64, _i32, _vp]),
     "modcr_qkv_attn_long_drop_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i32,
                                             _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _i32, _vp, _i64, _i32, _vp]),
+    "modcr_qkv_attn_long_align_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i32,
+                                             _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _i32, _vp, _i64, _i32, _vp, _vp]),
     "modcr_qkv_attn_route": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i64, _i32, _i32, _c.POINTER(_i32)]),
     "modcr_linear_splitk_workspace": (_i64, [_i32, _i32, _i32]),
     "modcr_linear_splitk_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
@@ -128,6 +130,11 @@ SIGNATURES = {
     "modcr_qkv_attn_long_drop_bwd_route": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "modcr_qkv_attn_long_drop_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
                                             _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp]),
+    "modcr_qkv_attn_long_align_bwd_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_long_align_bwd_route": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "modcr_qkv_attn_long_align_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
+                                             _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _c.c_uint64, _c.c_uint64, _vp, _i64, _i32, _vp,
+                                             _vp, _vp, _i32, _i32]),
     "modcr_linear_residual_ln_bwd_workspace": (_i64, [_i32, _i32, _i32]),
     "modcr_linear_residual_ln_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
                                             _vp, _i64, _i32, _vp]),
@@ -478,11 +485,14 @@ ATTN_MAX_KEYS = 512
 # keys up to which the opt-in wide dropout counter layout (csrc/attn_common.h: row stride 512 above 256 keys) carries the
 # attention-probability dropout: qkv_attn(wide_dropout=True) / qkv_attn_long_bwd(wide_dropout=True)
 ATTN_DROPOUT_WIDE_MAX_KEYS = 512
+# keys up to which the opt-in dense mask bits on the bias route and the align map's gradient are served above 256 keys:
+# qkv_attn(dense_bits=) / qkv_attn_long_bwd(dense_bits=, d_align=) (modcr_qkv_attn_long_align_fwd / _bwd; no prefix rows)
+ATTN_LONG_ALIGN_MAX_KEYS = 512
 
 
 def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=None, want_probs=False,
              align_map=None, align_t=0, num_heads=None, workspace=None, out=None, attn_dropout=None, lse=None, dump=None,
-             side_post_dropout=False, attn_bias=None, head_mask=None, row_start=None, wide_dropout=False):
+             side_post_dropout=False, attn_bias=None, head_mask=None, row_start=None, wide_dropout=False, dense_bits=None):
     """Fused QKV projection + attention.  x [N,S,H]; returns (ctx [N,S,H], probs or None).
     row_start: int32 [N+1] device table of the live-row layout (LiveRows; modcr_qkv_attn_rows_fwd): x and ctx are [N,S,H] BUFFERS
     whose first row_start[N] rows hold the sequences' live rows back to back.  No hist / probs / lse / dump / attn_bias there; a
@@ -493,6 +503,9 @@ def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=N
     P + S <= 512, dropout up to 256 keys); they replace key_mask / mask_bits and do not combine with lse / dump.
     wide_dropout (that route only): the call goes to modcr_qkv_attn_long_drop_fwd, which carries the dropout on to 512 keys under the
     wide counter layout; at P + S <= 256 or without dropout it changes nothing.
+    dense_bits (that route only, and by itself it selects the route): int32 [N, S, ceil(S / 32)] dense mask bits (build_phase_mask /
+    pack_mask_bits) read ON TOP of attn_bias, a clear bit = -10000 -- modcr_qkv_attn_long_align_fwd, 256 < S <= 512, no hist; the
+    backward is qkv_attn_long_bwd(dense_bits=).  mask_bits keeps its meaning: the binary route, never together with attn_bias.
     attn_dropout = (p, seed, offset): training-mode dropout of the attention probabilities.
     side_post_dropout: probs / align_map are the probabilities AFTER that dropout, P o m / (1 - p), as the reference's modules
     return them (modeling_bert.py:69-74); default: the un-dropped ones (and no probs output under dropout).
@@ -518,15 +531,15 @@ def qkv_attn(x, wqkv, bqkv, key_mask=None, mask_bits=None, hist=None, chunk_id=N
     p = 0 if hist is None else hist.shape[1]
     if p + s > ATTN_MAX_KEYS:
         raise ValueError("qkv_attn: P + S = %d keys exceeds the %d-key limit of the attention forward" % (p + s, ATTN_MAX_KEYS))
-    if wide_dropout and attn_bias is None and head_mask is None:
+    if wide_dropout and attn_bias is None and head_mask is None and dense_bits is None:
         raise ValueError("qkv_attn: wide_dropout belongs to the attn_bias / head_mask route (fold a binary key mask with fold_key_mask)")
-    if attn_bias is not None or head_mask is not None:
+    if attn_bias is not None or head_mask is not None or dense_bits is not None:
         if key_mask is not None or mask_bits is not None:
             raise ValueError("qkv_attn: attn_bias / head_mask replace key_mask / mask_bits (fold a binary mask into the bias as 0 / -10000)")
         if lse is not None or dump is not None:
             raise ValueError("qkv_attn: no row statistics (lse) / q|k|v dump on the attn_bias / head_mask route (forward only)")
         return _qkv_attn_bias(x, wqkv, bqkv, attn_bias, head_mask, hist, chunk_id, want_probs, align_map, align_t, a, workspace, out,
-                              attn_dropout, side_post_dropout, wide_dropout)
+                              attn_dropout, side_post_dropout, wide_dropout, dense_bits)
     if (dt == BF16 and attn_dropout is not None and attn_dropout[0] > 0.0 and side_post_dropout and (want_probs or align_map is not None)
             and not side_outputs_on_tiles(s, p, h, a)):
         # post-dropout side outputs are served by the bf16 TILE kernels only (modcr_qkv_attn_opt_fwd returns MODCR_ERR_UNSUPPORTED on
@@ -596,9 +609,18 @@ def _head_mask_2d(head_mask, n, a):
     return hm, (0 if hm.shape[0] == 1 else a)
 
 
+def _dense_bits(bits, who, n, s):
+    """dense mask bits of the bias route: a contiguous int32 [N, S, ceil(S / 32)] tensor (build_phase_mask / pack_mask_bits), as it is"""
+    if bits.dtype != torch.int32 or tuple(bits.shape) != (n, s, (s + 31) // 32) or not bits.is_contiguous():
+        raise ValueError("%s: dense_bits must be a contiguous int32 [N, S, ceil(S / 32)] = [%d, %d, %d] tensor, got %s %s" %
+                         (who, n, s, (s + 31) // 32, tuple(bits.shape), bits.dtype))
+    return bits
+
+
 def _qkv_attn_bias(x, wqkv, bqkv, attn_bias, head_mask, hist, chunk_id, want_probs, align_map, align_t, a, workspace, out, attn_dropout,
-                   side_post_dropout, wide_dropout=False):
-    """qkv_attn with attn_bias / head_mask: modcr_qkv_attn_bias_fwd, or with wide_dropout modcr_qkv_attn_long_drop_fwd"""
+                   side_post_dropout, wide_dropout=False, dense_bits=None):
+    """qkv_attn with attn_bias / head_mask: modcr_qkv_attn_bias_fwd, or with wide_dropout modcr_qkv_attn_long_drop_fwd, or with
+    dense_bits modcr_qkv_attn_long_align_fwd (the drop entry's arguments, then the bits)"""
     dt = dt_of(x)
     n, s, h = x.shape
     p = 0 if hist is None else hist.shape[1]
@@ -615,11 +637,12 @@ def _qkv_attn_bias(x, wqkv, bqkv, attn_bias, head_mask, hist, chunk_id, want_pro
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=x.device)
     chunk_t = 0 if chunk_id is None else chunk_id.shape[1]
-    entry = "modcr_qkv_attn_long_drop_fwd" if wide_dropout else "modcr_qkv_attn_bias_fwd"
+    entry = "modcr_qkv_attn_long_align_fwd" if dense_bits is not None else "modcr_qkv_attn_long_drop_fwd" if wide_dropout else "modcr_qkv_attn_bias_fwd"
+    more = () if dense_bits is None else (_ptr(_dense_bits(dense_bits, "qkv_attn", n, s)),)
     _check(getattr(lib(), entry)(_ptr(x), _ptr(hist), _ptr(_contig(wqkv)), _ptr(bqkv), _ptr(bias), bsn, bsa, bsq, _ptr(hm), hsn,
                                  _ptr(chunk_id), chunk_t, _ptr(ctx), _ptr(probs), _ptr(align_map), align_t, n, s, p, h, a,
                                  float(ap), seed, off, ATTN_SIDE_POST_DROPOUT if side_post_dropout else 0,
-                                 _ptr(workspace), need, dt, _stream()),
+                                 _ptr(workspace), need, dt, _stream(), *more),
            entry)
     return ctx, probs
 
@@ -1170,7 +1193,7 @@ def qkv_attn_gate_bwd_route(n, s, p, h, a, dtype=BF16):
     return _attn_bwd_route("modcr_qkv_attn_gate_bwd", ATTN_BIAS_BWD_CORES, n, s, p, h, a, dtype)
 
 
-def _attn_bias_bwd_operands(who, x, hist, attn_bias, head_mask, d_bias, d_head_mask, a, max_keys):
+def _attn_bias_bwd_operands(who, x, hist, attn_bias, head_mask, d_bias, d_head_mask, a, max_keys, bits=False):
     """the checks the bias / prefix / gate backward and qkv_attn_long_bwd share, before any tensor is touched:
     -> (P, fp32 bias or None, its three element strides, [1 or N, A] head mask or None, its sequence stride)"""
     n, s, h = x.shape
@@ -1183,7 +1206,7 @@ def _attn_bias_bwd_operands(who, x, hist, attn_bias, head_mask, d_bias, d_head_m
     if l > max_keys:
         raise ValueError(("%s: P + S = %d keys exceeds the %d-key limit of the attention backward" if p else
                           "%s: S = %d exceeds the %d-key limit of the attention backward") % (who, l, max_keys))
-    if attn_bias is None and head_mask is None and d_head_mask is None:
+    if attn_bias is None and head_mask is None and d_head_mask is None and not bits:        # (dense bits stand in for a bias)
         raise ValueError("%s: hist needs attn_bias, key_mask or head_mask" % who if p else "%s: d_bias without attn_bias" % who)
     bias, strides = (None, (0, 0, 0)) if attn_bias is None else _bias_strides(attn_bias, n, a, s, l)
     hm, hsn = (None, 0) if head_mask is None else _head_mask_2d(head_mask, n, a)
@@ -1205,38 +1228,52 @@ _ATTN_BIAS_BWD_ARGS = {
     "gate": _GATE_BWD_ARGS,
     "long": _GATE_BWD_ARGS,
     "long_drop": _GATE_BWD_ARGS,
+    "long_align": _GATE_BWD_ARGS + ("bits", "d_align", "align_t", "flags"),
 }
 
 
 def _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, a, accumulate, attn_dropout, dx_residual,
-                       d_head_mask=None, long=False, wide_dropout=False):
+                       d_head_mask=None, long=False, wide_dropout=False, dense_bits=None, d_align=None, align_t=0, side_post_dropout=False):
     """The bias family of the attention backward, one marshalling path for its five C entries: long (qkv_attn_long_bwd) ->
     modcr_qkv_attn_long_bwd, or with wide_dropout modcr_qkv_attn_long_drop_bwd, else with d_head_mask -> modcr_qkv_attn_gate_bwd, else with hist -> modcr_qkv_attn_prefix_bwd, else
-    modcr_qkv_attn_bias_bwd.  Returns dx, or (dx, d_hist) with hist."""
+    modcr_qkv_attn_bias_bwd.  long with dense_bits / d_align -> modcr_qkv_attn_long_align_bwd (the long_drop entry's arguments, then
+    bits, d_align, align_t, flags).  Returns dx, or (dx, d_hist) with hist."""
     who = "qkv_attn_long_bwd" if long else "qkv_attn_bwd"
     dt = dt_of(x)
     n, s, h = x.shape
+    align = long and (dense_bits is not None or d_align is not None)
+    if align:
+        if dense_bits is not None:
+            _dense_bits(dense_bits, who, n, s)
+        if d_align is not None and (d_align.dtype != torch.float32 or tuple(d_align.shape) != (n, align_t, s - align_t) or not d_align.is_contiguous()):
+            raise ValueError("%s: d_align must be a contiguous fp32 [N, align_t, S - align_t] tensor, got %s %s (align_t=%d)" %
+                             (who, tuple(d_align.shape), d_align.dtype, align_t))
+        if attn_bias is None and head_mask is None and d_head_mask is None and dense_bits is None:      # d_align alone: the zero bias
+            attn_bias = torch.zeros((1, 1, 1, s if hist is None else hist.shape[1] + s), dtype=torch.float32, device=x.device)
     p, bias, (bsn, bsa, bsq), hm, hsn = _attn_bias_bwd_operands(who, x, hist, attn_bias, head_mask, d_bias, d_head_mask, a,
-                                                                ATTN_BWD_LONG_MAX_KEYS if long else ATTN_BWD_MAX_KEYS)
+                                                                ATTN_BWD_LONG_MAX_KEYS if long else ATTN_BWD_MAX_KEYS,
+                                                                bits=align and dense_bits is not None)
     ap, seed, off = attn_dropout if attn_dropout is not None else (0.0, 0, 0)
     if long and p + s > ATTN_BWD_MAX_KEYS and ap > 0 and not wide_dropout:
         raise ValueError("%s: attention-probability dropout (p=%g) is not implemented above %d keys (P + S = %d)" % (who, ap, ATTN_BWD_MAX_KEYS, p + s))
-    entry = ("long_drop" if wide_dropout else "long") if long else "gate" if d_head_mask is not None else "prefix" if p else "bias"
+    entry = ("long_align" if align else "long_drop" if wide_dropout else "long") if long else "gate" if d_head_mask is not None else "prefix" if p else "bias"
     fn, ws_fn = {"bias": (lib().modcr_qkv_attn_bias_bwd, lib().modcr_qkv_attn_bias_bwd_workspace),
                  "prefix": (lib().modcr_qkv_attn_prefix_bwd, lib().modcr_qkv_attn_prefix_bwd_workspace),
                  "gate": (lib().modcr_qkv_attn_gate_bwd, lib().modcr_qkv_attn_gate_bwd_workspace),
                  "long": (lib().modcr_qkv_attn_long_bwd, lib().modcr_qkv_attn_long_bwd_workspace),
-                 "long_drop": (lib().modcr_qkv_attn_long_drop_bwd, lib().modcr_qkv_attn_long_drop_bwd_workspace)}[entry]
+                 "long_drop": (lib().modcr_qkv_attn_long_drop_bwd, lib().modcr_qkv_attn_long_drop_bwd_workspace),
+                 "long_align": (lib().modcr_qkv_attn_long_align_bwd, lib().modcr_qkv_attn_long_align_bwd_workspace)}[entry]
     x, dctx = _contig(x), _contig(dctx)
     dx = torch.empty_like(x)
     hist = _contig(hist) if p else None
     d_hist = torch.empty_like(hist) if p else None
     need = ws_fn(n, s, h, dt) if entry == "bias" else ws_fn(n, s, p, h, dt)
     tensors = dict(dctx=dctx, x=x, hist=hist, wqkv=_contig(wqkv), bqkv=bqkv, bias=bias, hm=hm, chunk_id=chunk_id, dx=dx, d_hist=d_hist, dwqkv=dwqkv,
-                   dbqkv=dbqkv, d_bias=d_bias, d_head_mask=d_head_mask, ws=_workspace("attn_bwd", need, x.device),
+                   dbqkv=dbqkv, d_bias=d_bias, d_head_mask=d_head_mask, ws=_workspace("attn_bwd", need, x.device), bits=dense_bits, d_align=d_align,
                    res=_contig(dx_residual, torch.float32) if dx_residual is not None else None)
     v = dict(n=n, s=s, p=p, h=h, a=a, dt=dt, bsn=bsn, bsa=bsa, bsq=bsq, hsn=hsn, ap=float(ap), seed=seed, off=off, need=need,
-             chunk_t=0 if chunk_id is None else chunk_id.shape[1], accumulate=1 if accumulate else 0)
+             chunk_t=0 if chunk_id is None else chunk_id.shape[1], accumulate=1 if accumulate else 0,
+             align_t=int(align_t) if d_align is not None else 0, flags=ATTN_SIDE_POST_DROPOUT if side_post_dropout else 0)
     v.update((k, _ptr(t)) for k, t in tensors.items())          # (a tensor that is not on the GPU is refused here, before the stream is asked for)
     v["stream"] = _stream()
     _check(fn(*[v[k] for k in _ATTN_BIAS_BWD_ARGS[entry]]), "modcr_qkv_attn_%s_bwd" % entry)
@@ -1253,15 +1290,29 @@ def qkv_attn_long_bwd_route(n, s, p, h, a, dtype=BF16):
     return _attn_bwd_route("modcr_qkv_attn_long_bwd", ATTN_LONG_BWD_CORES, n, s, p, h, a, dtype)
 
 
+def qkv_attn_long_align_bwd_route(n, s, p, h, a, dtype=BF16):
+    """The core modcr_qkv_attn_long_align_bwd runs for this shape (nothing is launched): what qkv_attn_long_bwd_route answers."""
+    return _attn_bwd_route("modcr_qkv_attn_long_align_bwd", ATTN_LONG_BWD_CORES, n, s, p, h, a, dtype)
+
+
 def qkv_attn_long_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, chunk_id=None, num_heads=None, accumulate=False, attn_dropout=None,
-                      dx_residual=None, attn_bias=None, head_mask=None, d_bias=None, hist=None, d_head_mask=None, wide_dropout=False):
+                      dx_residual=None, attn_bias=None, head_mask=None, d_bias=None, hist=None, d_head_mask=None, wide_dropout=False, **align):
     """qkv_attn_bwd's attn_bias / head_mask / hist route with the key limit 512 instead of 256 (modcr_qkv_attn_long_bwd): the backward
     of a forward that ran qkv_attn(attn_bias=, head_mask=, hist=) at P + S <= 512 keys.  Returns dx, or (dx, d_hist) with hist.  At
     P + S <= 256 the call is modcr_qkv_attn_gate_bwd's, bit for bit; above, the streaming cores run and attention dropout is refused.
     A binary key_mask [N, L] is folded into a [N,1,1,L] 0 / -10000 bias (fold the forward the same way); chunk_id only without hist.
     wide_dropout: the backward of a forward that ran qkv_attn(wide_dropout=True) (modcr_qkv_attn_long_drop_bwd): above 256 keys the
     streaming cores regenerate that forward's keep mask from attn_dropout = (p, seed, offset) under the wide counter layout; at
-    P + S <= 256 or without dropout it changes nothing."""
+    P + S <= 256 or without dropout it changes nothing.
+    dense_bits / d_align / align_t / side_post_dropout: the backward of a forward that ran qkv_attn(dense_bits=, align_map=, align_t=,
+    side_post_dropout=) above 256 keys (modcr_qkv_attn_long_align_bwd, S <= ATTN_LONG_ALIGN_MAX_KEYS, no hist): the bits are read on
+    top of attn_bias; d_align fp32 [N, align_t, S - align_t] is the gradient of that forward's align map.  A folded key_mask combines
+    with both.  With either, dropout above 256 keys is carried as with wide_dropout.  (The four are keyword-only and taken through
+    **align: the named parameters stay those of the bias / prefix / gate route, which tests/test_attn_long_bwd_host.py pins.)"""
+    unknown = set(align) - {"dense_bits", "d_align", "align_t", "side_post_dropout"}
+    if unknown:
+        raise TypeError("qkv_attn_long_bwd() got an unexpected keyword argument %r" % sorted(unknown)[0])
+    dense_bits, d_align = align.get("dense_bits"), align.get("d_align")
     if hist is not None and chunk_id is not None:
         raise ValueError("qkv_attn_long_bwd: hist (prefix rows) does not combine with chunk_id")
     if key_mask is not None:
@@ -1269,7 +1320,9 @@ def qkv_attn_long_bwd(dctx, x, wqkv, bqkv, dwqkv, dbqkv, key_mask=None, chunk_id
             raise ValueError("qkv_attn_long_bwd: attn_bias replaces key_mask")
         attn_bias = fold_key_mask(key_mask)
     return _qkv_attn_bias_bwd(dctx, x, hist, wqkv, bqkv, dwqkv, dbqkv, attn_bias, head_mask, d_bias, chunk_id, num_heads, accumulate,
-                              attn_dropout, dx_residual, d_head_mask, long=True, wide_dropout=bool(wide_dropout))
+                              attn_dropout, dx_residual, d_head_mask, long=True,
+                              wide_dropout=bool(wide_dropout) or dense_bits is not None or d_align is not None, dense_bits=dense_bits,
+                              d_align=d_align, align_t=align.get("align_t", 0), side_post_dropout=bool(align.get("side_post_dropout", False)))
 
 
 def fold_key_mask(key_mask):

@@ -25,14 +25,18 @@ LONG_BACKWARD = False      # True = trainable layers above 256 keys run the stre
                            # attention-probability dropout there); opt-in, set by the run scripts' --modcr_long_backward
 LONG_DROPOUT = False       # True (with LONG_BACKWARD) = attention-probability dropout is carried above 256 keys too, under the wide
                            # counter layout (modcr_qkv_attn_long_drop_fwd / _bwd); opt-in, --modcr_long_dropout
+LONG_ALIGN = False         # True (with LONG_BACKWARD) = dense mask bits and the align map with its gradient are carried above 256 keys
+                           # too (modcr_qkv_attn_long_align_fwd / _bwd: seq_enc's layers); opt-in, --modcr_long_align
 
 
-def set_long_backward(flag, dropout=False):
+def set_long_backward(flag, dropout=False, align=False):
     """flag: trainable layers above 256 keys run the streaming attention backward; dropout (only with flag): they also apply the
-    attention-probability dropout there.  set_long_backward(True) and set_long_backward(False) leave the dropout switch off."""
-    global LONG_BACKWARD, LONG_DROPOUT
+    attention-probability dropout there; align (only with flag): they also take mask_bits and the align map there.
+    set_long_backward(True) and set_long_backward(False) leave both switches off."""
+    global LONG_BACKWARD, LONG_DROPOUT, LONG_ALIGN
     LONG_BACKWARD = bool(flag)
     LONG_DROPOUT = bool(flag) and bool(dropout)
+    LONG_ALIGN = bool(flag) and bool(align)
 
 
 def _w_for(x, w):
@@ -400,7 +404,7 @@ def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, par
             raise NotImplementedError("attention-probability dropout (p=%g) in a trainable layer needs %s <= %d (%s = %d): set "
                                       "attention_probs_dropout_prob = 0 to train above %d keys" %
                                       (attn_p, what, mh.ATTN_TILE_KEYS, what, s, mh.ATTN_TILE_KEYS))
-        if mask_bits is not None or align is not None:
+        if (mask_bits is not None or align is not None) and not LONG_ALIGN:
             raise NotImplementedError("the streaming attention backward (%s = %d > %d keys) takes no %s: the dense phase masks and the "
                                       "align-map gradient stay at %d keys" %
                                       (what, s, mh.ATTN_TILE_KEYS, "mask_bits" if mask_bits is not None else "align map", mh.ATTN_TILE_KEYS))
@@ -415,7 +419,7 @@ def _bert_layer_forward(ctx, x, chunk_id, num_heads, eps, p, attn_p, packed, par
                                               attn_bias=None if attn_bias is None else attn_bias.detach(),
                                               head_mask=None if head_mask is None else head_mask.detach(),
                                               hist=None if hist is None else hist.detach(), long_backward=long_bwd,
-                                              long_dropout=long_bwd and LONG_DROPOUT)
+                                              long_dropout=long_bwd and LONG_DROPOUT, long_align=long_bwd and LONG_ALIGN)
     ctx.saved, ctx.packed = saved, packed
     ctx.holder = align[2] if align is not None else None
     ctx.params = params                  # (the Parameter objects: the gradient sink writes into their .grad views)

@@ -184,7 +184,7 @@ def attn_dropout_supported(x, num_heads):
 
 def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None, chunk_id=None, p=0.0, attn_p=0.0,
                         align_map=None, align_t=0, side_post_dropout=True, attn_bias=None, head_mask=None, hist=None, long_backward=False,
-                        long_dropout=False):
+                        long_dropout=False, long_align=False):
     """p: hidden_dropout_prob of BertSelfOutput / BertOutput in training mode (a_bert:369-373, :446-451);
     attn_p: attention_probs_dropout_prob (modeling_bert.py:69), applied inside the attention kernels;
     align_map [N,T,R] fp32 (+= head-summed text->region probabilities of this layer, v10:982), align_t = T;
@@ -202,22 +202,29 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
     nothing.
     long_dropout (with long_backward, above 256 keys): attn_p > 0 is served there too -- the DROPOUT counters are taken as below 256
     keys (n A s (P + S) of them), the forward runs mh.qkv_attn(wide_dropout=True) under the wide counter layout and layer_backward
-    regenerates its mask (mh.qkv_attn_long_bwd(wide_dropout=True))."""
+    regenerates its mask (mh.qkv_attn_long_bwd(wide_dropout=True)).
+    long_align (with long_backward, above 256 keys, no hist): mask_bits and align_map / align_t are accepted there, with chunk_id -- the
+    bits ride on top of the (folded key_mask) bias (mh.qkv_attn(dense_bits=), modcr_qkv_attn_long_align_fwd), the align map and
+    side_post_dropout are what they are below 256 keys, and layer_backward(d_align=) runs mh.qkv_attn_long_bwd(dense_bits=, d_align=)."""
     n, s, h = x.shape
     pl = 0 if hist is None else hist.shape[1]
     long_backward = bool(long_backward) and pl + s > mh.ATTN_BWD_MAX_KEYS
     long_dropout = bool(long_dropout) and long_backward and attn_p > 0.0
+    long_align = bool(long_align) and long_backward and hist is None and (mask_bits is not None or align_map is not None)
+    dense_bits = None
     if long_backward:
         if attn_p > 0.0 and not long_dropout:
             raise NotImplementedError("attention-probability dropout in a trainable layer needs P + S <= 256 (S=%d, P=%d): set "
                                       "attention_probs_dropout_prob = 0 to train above 256 keys" % (s, pl))
-        if mask_bits is not None or align_map is not None:
+        if (mask_bits is not None or align_map is not None) and not long_align:
             raise NotImplementedError("layer_forward_train: no mask_bits and no align map above 256 keys (long_backward)")
         if key_mask is not None:
             if attn_bias is not None:
                 raise ValueError("layer_forward_train: attn_bias replaces key_mask")
             attn_bias, key_mask = mh.fold_key_mask(key_mask), None
-        if attn_bias is None and head_mask is None:      # no mask at all: the biased route under a zero bias
+        if long_align:                                   # the bits leave the binary route: they ride on top of the bias
+            dense_bits, mask_bits = mask_bits, None
+        if attn_bias is None and head_mask is None and dense_bits is None:      # no mask at all: the biased route under a zero bias
             attn_bias = torch.zeros((1, 1, 1, pl + s), dtype=torch.float32, device=x.device)
     if hist is not None:
         if mask_bits is not None or chunk_id is not None or align_map is not None:
@@ -228,10 +235,10 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
             attn_bias, key_mask = mh.fold_key_mask(key_mask), None
         if attn_bias is None and head_mask is None:
             raise ValueError("layer_forward_train: hist needs key_mask, attn_bias or head_mask")
-    biased = attn_bias is not None or head_mask is not None
+    biased = attn_bias is not None or head_mask is not None or dense_bits is not None
     if biased and (key_mask is not None or mask_bits is not None):
         raise ValueError("layer_forward_train: attn_bias / head_mask replace key_mask / mask_bits")
-    if biased and align_map is not None:
+    if biased and align_map is not None and not long_align:
         raise ValueError("layer_forward_train: no align map (and no align-map gradient) on the attn_bias / head_mask route")
     adrop = None
     if attn_p > 0.0:
@@ -247,7 +254,11 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
     if lse is not None and SAVE_QKV:
         dump = torch.empty((mh.qkv_dump_numel(n, s, num_heads),), dtype=torch.bfloat16, device=x.device)
     post = bool(side_post_dropout and adrop is not None and align_map is not None)
-    if biased:
+    if long_align:
+        ctx, _ = mh.qkv_attn(x, layer["wqkv"], layer["bqkv"], chunk_id=chunk_id, num_heads=num_heads, attn_dropout=adrop,
+                             attn_bias=attn_bias, head_mask=head_mask, dense_bits=dense_bits, align_map=align_map, align_t=align_t,
+                             side_post_dropout=post, wide_dropout=long_dropout)
+    elif biased:
         ctx, _ = mh.qkv_attn(x, layer["wqkv"], layer["bqkv"], chunk_id=chunk_id, num_heads=num_heads, attn_dropout=adrop,
                              attn_bias=attn_bias, head_mask=head_mask, hist=hist, **({"wide_dropout": True} if long_dropout else {}))
     else:
@@ -268,7 +279,8 @@ def layer_forward_train(layer, x, num_heads, eps, key_mask=None, mask_bits=None,
     saved = dict(x=x, ctx=ctx, pre1=pre1, a=a, inter=inter, u=u, pre2=pre2, num_heads=num_heads, eps=eps,
                  key_mask=key_mask, mask_bits=mask_bits, chunk_id=chunk_id, drop1=drop1, drop2=drop2, adrop=adrop,
                  align_t=align_t if align_map is not None else 0, lse=lse, dump=dump, side_post=post,
-                 attn_bias=attn_bias, head_mask=head_mask, hist=hist, long_backward=long_backward, long_dropout=long_dropout)
+                 attn_bias=attn_bias, head_mask=head_mask, hist=hist, long_backward=long_backward, long_dropout=long_dropout,
+                 dense_bits=dense_bits, long_align=long_align)
     return y.view(n, s, h), saved
 
 
@@ -350,7 +362,7 @@ def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None, want_d_
     dwqkv, dbqkv = outs.get("attention.self.qkv.weight"), outs.get("attention.self.qkv.bias")      # (spans of the flat gradient buffer)
     dwqkv = dwqkv.view(3 * h, h) if dwqkv is not None else torch.empty(3 * h, h, dtype=f32, device=dev)
     dbqkv = dbqkv if dbqkv is not None else torch.empty(3 * h, dtype=f32, device=dev)
-    if saved.get("attn_bias") is not None or saved.get("head_mask") is not None:
+    if saved.get("attn_bias") is not None or saved.get("head_mask") is not None or saved.get("long_align"):
         if want_d_bias and saved.get("attn_bias") is None:
             raise ValueError("layer_backward: want_d_bias for a layer that ran without attn_bias")
         hist = saved.get("hist")
@@ -365,7 +377,10 @@ def layer_backward(layer, saved, dy, mfma=True, d_align=None, outs=None, want_d_
         dx = attn_bwd(d_ctx.view(n, s, h), x, layer["wqkv"], layer["bqkv"], dwqkv, dbqkv, chunk_id=saved["chunk_id"],
                       num_heads=saved["num_heads"], attn_dropout=saved.get("adrop"), dx_residual=d_pre1.view(n, s, h),
                       attn_bias=saved.get("attn_bias"), head_mask=saved.get("head_mask"), d_bias=d_bias, hist=hist,
-                      d_head_mask=d_hm, **({"wide_dropout": True} if saved.get("long_dropout") else {}))
+                      d_head_mask=d_hm, **({"wide_dropout": True} if saved.get("long_dropout") else {}),
+                      # (a layer that ran with long_align: its bits and the align map's gradient, modcr_qkv_attn_long_align_bwd)
+                      **(dict(dense_bits=saved.get("dense_bits"), d_align=d_align if saved.get("align_t") else None, align_t=saved.get("align_t", 0),
+                              side_post_dropout=bool(saved.get("side_post"))) if saved.get("long_align") else {}))
         if hist is not None:
             dx, g["history_state"] = dx
         if want_d_bias:

@@ -264,6 +264,10 @@ def get_args(argv=None):
                    help="(this build) implies --modcr_long_backward; trainable layers at 256 < S + P <= 512 keys also apply the "
                         "attention-probability dropout (the reference's live nn.Dropout on the softmax output), forward and backward; "
                         "default off = attention dropout above 256 keys is refused")
+    p.add_argument("--modcr_long_align", action="store_true",
+                   help="(this build) implies --modcr_long_backward; seq_enc's trainable layers at 256 < S <= 512 keys also take their dense "
+                        "phase masks, chunk-mean queries and the align map with its gradient (config 3, the enc4-align model); combines with "
+                        "--modcr_long_dropout; default off = mask bits and the align map above 256 keys are refused under grad mode")
     p.add_argument("--roberta_body", default="standin", choices=["standin", "large"],
                    help="large = the 24-layer prefix RoBERTa-large on the HIP kernels, trainable (run_PMR_ModCR.py:772-781; "
                         "random init: local_transformers/roberta-large is not in the reference tree)")
@@ -281,7 +285,7 @@ def get_args(argv=None):
                    help="allow --do_eval / --do_test without a checkpoint (random weights; smoke runs only)")
     p.add_argument("--device", default="cuda", type=str)
     args = p.parse_args(argv)
-    args.modcr_long_backward = args.modcr_long_backward or args.modcr_long_dropout
+    args.modcr_long_backward = args.modcr_long_backward or args.modcr_long_dropout or args.modcr_long_align
     given = set()
     for a in (sys.argv[1:] if argv is None else argv):
         if a.startswith("--"):
@@ -377,7 +381,7 @@ def main(argv=None):
         logger.info("modcr_backward_memory=%s -> %s", args.modcr_backward_memory, chosen)
     if args.modcr_long_backward:
         from modeling import hip_autograd
-        hip_autograd.set_long_backward(True, dropout=args.modcr_long_dropout)
+        hip_autograd.set_long_backward(True, dropout=args.modcr_long_dropout, align=args.modcr_long_align)
     mh.DROPOUT.manual_seed(args.seed + 7919 * getattr(args, "rank", 0))   # different masks per rank (different data anyway)
     if args.do_test or (args.do_eval and not args.do_train):
         if os.path.isfile(args.eval_model_dir):

@@ -37,7 +37,7 @@ def freeze_roberta_body(model):
     return frozen
 
 
-get_args = pmr.get_args        # one parser for both entry points: every "(this build)" switch, --modcr_long_backward and --modcr_long_dropout among them
+get_args = pmr.get_args        # one parser for both entry points: every "(this build)" switch, --modcr_long_backward, --modcr_long_dropout and --modcr_long_align among them
 
 
 def main(argv=None):

@@ -36,9 +36,11 @@ def r16(t):
     return t.float().to(torch.bfloat16).double()
 
 
-def rounded_restatement(shape, bias, hm, keep=None, pd=0.0, c=None):
+def rounded_restatement(shape, bias, hm, keep=None, pd=0.0, c=None, e=None, post=False):
     """(ctx, dx, d_hist or None, dWqkv, dbqkv, dS, d_hm) of the bf16 route's arithmetic in float64 with its roundings; keep [N, A, S, L]
-    (0 / 1) and pd: the attention-probability dropout of the DROP instantiations; c: another case than the shape's"""
+    (0 / 1) and pd: the attention-probability dropout of the DROP instantiations; c: another case than the shape's;
+    e [N, 1, S, L] (zero outside text rows x region keys) and post: the align map's gradient of the DALIGN instantiations -- it joins dP
+    in fp32 (under keep / (1 - p) with post) and D through the fp32 exponentials of sweep 1, neither of them a bf16 operand"""
     n, s, p, h, a = shape
     c = T.case(shape) if c is None else c
     w, b, x = (t.double() for t in c[:3])
@@ -66,6 +68,10 @@ def rounded_restatement(shape, bias, hm, keep=None, pd=0.0, c=None):
         dp = do @ v.transpose(-1, -2) * keep * inv
         dl = ((r16(P) * keep) @ v * do).sum(-1, keepdim=True) * inv
         Pv = r16(P * inv) * keep
+    if e is not None:
+        ek = e.double() * (keep / (1.0 - pd) if (post and keep is not None) else 1.0)
+        dp = dp + ek
+        dl = dl + (P * ek).sum(-1, keepdim=True)
     ds = P * (dp - dl)
     dq = r16(back(r16(ds) @ k * hmv * 0.125))
     dk = r16(back(r16(ds).transpose(-1, -2) @ q * hmv * 0.125))
@@ -139,13 +145,64 @@ def main_drop(out):
         f.write(text)
 
 
+def main_align(out):
+    import attn_wide_drop as W
+    import test_hip_attn_long_align as A
+    names = ("ctx", "dx", "d_hist", "dwqkv", "dbqkv", "d_bias", "d_head_mask")
+    lines = ["bf16-rounded restatement of the attention backward from 257 to 512 keys WITH DENSE MASK BITS AND THE ALIGN MAP'S GRADIENT",
+             "(modcr_qkv_attn_long_align_bwd; bits as a 0 / -10000 additive mask, d_align ~ N(0, 1), dropout p = %g under the wide counter layout)" % A.DROP[0],
+             "against float64 (CPU): PREDICTED share of each bound of tests/test_hip_attn_long_align.py used by the number formats alone.",
+             "max|err| / max(1, max|ref|) against 2e-2; relative L2 against 2e-2; key-bias slice against 2e-2 x scale x sqrt(N S) / 4.  Shapes are",
+             "(N, S, T, H, A).  The chunk-mean case (2, 320, 64, 256, 4) is not restated: the chunk mean adds no rounding site that the bits or the",
+             "align map's gradient touch.  d_align has unit variance in every case.  One case is rescaled, the bound is not: at (1, 258, 257) the first",
+             "pass predicted 104.9 - 115.6 % of the d_head_mask bound (a sum of 258 terms of either sign under +-10 scores whose bf16 q | k rows move",
+             "every probability by percents), so that case takes flat-score rows (the query projection scaled to a score deviation of 0.4:",
+             "tests/test_hip_attn_long_align.py, batch()); the figures below are with those rows.", ""]
+    worst = {}
+    cases = []
+    for shape in A.SHAPES:
+        cases += [(shape, "bits phase 1", 1, False, None, False, False), (shape, "bits phase 3", 3, False, None, False, False),
+                  (shape, "d_align, soft bias", 0, True, None, False, True),
+                  (shape, "bits + d_align p=0.1", 3, False, A.DROP, False, True), (shape, "bits + d_align p=0.1 post", 3, False, A.DROP, True, True)]
+    for shape, what, phase, soft, drop, post, align in cases:
+        n, s, t, h, a = shape
+        hm = T.head_mask(n, a)
+        add = A.soft(shape) if soft else A.phase_add(shape, phase)
+        ref = A.reference(shape, add, hm, drop=drop, post=post, with_align=align)
+        if not soft:
+            ref[5] = None
+        e = None
+        if align:
+            e = torch.zeros(n, 1, s, s, dtype=torch.float64)
+            e[:, 0, :t, t:] = A.batch(shape)[4].double()
+        keep = W.keep_of_call(n, a, s, 0, drop).double() if drop else None
+        got = rounded_restatement((n, s, 0, h, a), add, hm, keep, drop[0] if drop else 0.0, c=A.batch(shape)[3], e=e, post=post)
+        row = uses(names, got, ref[:7], (n, s, 0, h, a))
+        for nm, use in row:
+            worst[nm] = max(worst.get(nm, (0.0, None)), (use, (shape, what)))
+        lines.append("%-24s %-26s %s" % (shape, what, "  ".join("%s %4.1f %%" % (nm, 100 * u) for nm, u in row)))
+    lines += ["", "worst predicted use of each bound:"]
+    for nm, (use, where) in worst.items():
+        lines.append("  %-20s %5.1f %%  at %s %s" % (nm, 100 * use, where[0], where[1]))
+    top = max(u for u, _ in worst.values())
+    lines += ["", "largest predicted share: %.1f %% -- %s" % (100 * top, "below every bound: inputs and bounds stand" if top < 1.0 else
+                                                              "ABOVE A BOUND: rescale that case's inputs")]
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    with open(out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--drop", action="store_true", help="the dropout cases of tests/test_hip_attn_long_drop.py")
+    ap.add_argument("--align", action="store_true", help="the mask-bits / align-map-gradient cases of tests/test_hip_attn_long_align.py")
     args = ap.parse_args()
     if args.drop:
         return main_drop(args.out or os.path.join(ROOT, "profiles", "attn_long_drop_tolerance_report.txt"))
+    if args.align:
+        return main_align(args.out or os.path.join(ROOT, "profiles", "attn_long_align_tolerance_report.txt"))
     args.out = args.out or os.path.join(ROOT, "profiles", "attn_long_bwd_tolerance_report.txt")
     lines = ["bf16-rounded restatement of the attention backward from 257 to 512 keys against float64 (CPU): share of each bound of",
              "tests/test_hip_attn_long_bwd.py used by the number formats alone.  Soft-bias case: head mask (1, 0.5), no dropout.",
